@@ -15,15 +15,24 @@ collective; PSNR rows and the ids of failed frames are gathered once at the end 
 `python bench.py --gpus N` without a launcher starts its own N ranks (a child `python -m torch.distributed.run`,
 before anything touches a GPU) and exits with their status.
 
-Rank 0 prints ONE JSON line (contract in the task statement): `value` = frames per second over all ranks,
-`ms_per_step` (the four-frame step) and `ms_per_frame`; `roofline` (the kernel group with the largest share of the
-kernel time, HIP events on the launch stream during the timed steps; PMC traffic from the committed passes of this
-command); `step_model` per frame: the reference-decomposition bound, this build's OWN bound (`own_frac`) and
-`hbm_util`; `psnr_cpu / psnr_gpu / abs_dpsnr` of frame 0 against the reference's own CPU run of that frame
-(tests/golden fixture); `failed_image_ids`; `cpu_baseline` (the CPU oracle on the host cores over a bounded sample,
-N=1 only) and, at N=1, two reference legs measured in child processes: `value_exact_f32` (every GEMM on the
-f32-input MFMA, IRM_GEMM_EXACT=1) and `value_pcie_inclusive` (the reference-shaped get_model_prediction call:
+Rank 0 prints ONE JSON line: `value` = frames per second over all ranks, `ms_per_step` (one timed step: the
+four-frame step) and `ms_per_frame`, `psnr_db_mean / psnr_db_std` over the timed frames and `failed_image_ids`.
+A plain run does only what that line needs: set-up, --warmup steps, the --steps timed steps (the per-batch forward
+replayed from its HIP graph, as users get it), --dump-outputs, the line.
+
+--full adds everything else, each part as before:
+`roofline` (the kernel group with the largest share of the kernel time, HIP events on the launch stream around its
+launches during the timed steps, which then run eager; PMC traffic from the committed passes of this command) and
+`kernels` (an un-timed profile step with events on every launch); `step_model` per frame: the reference-decomposition
+bound, this build's OWN bound (`own_frac`) and `hbm_util`; `psnr_cpu / psnr_gpu / abs_dpsnr` of frame 0 against the
+reference's own CPU run of that frame (tests/golden fixture); `cpu_baseline` (the CPU oracle on the host cores over a
+bounded sample, N=1 only) and, at N=1, two reference legs measured in child processes: `value_exact_f32` (every GEMM
+on the f32-input MFMA, IRM_GEMM_EXACT=1) and `value_pcie_inclusive` (the reference-shaped get_model_prediction call:
 numpy uint8 in host memory -> numpy uint8).
+
+--dump-outputs DIR: after the timed steps rank 0 writes what its last timed step returned, DIR/frames.npy (the uint8
+output frames as float32, [frames, 720, 1280, 3], the first DUMP_MAX_FRAMES of them) and DIR/sse.npy (float64, each
+frame's squared error against its target).  Inputs and weights are seeded: the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -55,6 +64,7 @@ PEAK_HBM_GBS = 8000.0             # HBM3E spec peak
 REF_STEP_GBYTES, REF_STEP_TFLOP = 271.1, 7.54
 H, W, C = 720, 1280, 3
 N_FRAMES = 4                      # distinct synthetic frames per rank, cycled over the steps
+DUMP_MAX_FRAMES = 5               # --dump-outputs: 5 x 720 x 1280 x 3 float32 = 55 MB (< 64 MB in all)
 
 
 def parse():
@@ -62,18 +72,26 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle leg (profiling runs)")
-    ap.add_argument("--no-kernel-timer", action="store_true", help="no per-launch events in the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline / kernel table / step model, PSNR parity against the reference's CPU frame, "
+                         "the CPU baseline and the exact-f32 / PCIe-inclusive legs (a plain run: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write rank 0's last-step outputs as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle leg (profiling runs)")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full: no per-launch events in the timed steps")
     ap.add_argument("--streams", type=int, default=1, help="tile groups run on this many HIP streams")
     ap.add_argument("--frames-per-step", type=int, default=4,
                     help="frames whose tiles form one batch (one pass of the hot path = one step)")
-    ap.add_argument("--detail", default=None, help="write a per-shape kernel table (json) to this path")
+    ap.add_argument("--detail", default=None, help="--full: write a per-shape kernel table (json) to this path")
     ap.add_argument("--all-launch-events", action="store_true",
-                    help="diagnostic: HIP events around EVERY launch of the timed steps (the behaviour before the end of round 3)")
-    ap.add_argument("--cpu-tile", type=int, default=512, help="tile edge of the CPU-baseline sample")
-    ap.add_argument("--no-legs", action="store_true", help="skip the exact-f32 / PCIe-inclusive child legs")
+                    help="--full diagnostic: HIP events around EVERY launch of the timed steps (the behaviour before the end of round 3)")
+    ap.add_argument("--cpu-tile", type=int, default=512, help="--full: tile edge of the CPU-baseline sample")
+    ap.add_argument("--no-legs", action="store_true", help="--full: skip the exact-f32 / PCIe-inclusive child legs")
     ap.add_argument("--leg", choices=["pcie"], default=None, help=argparse.SUPPRESS)     # child process mode
-    return ap.parse_args()
+    args = ap.parse_args()
+    if (args.detail or args.all_launch_events) and not args.full:
+        ap.error("--detail and --all-launch-events belong to the kernel table: they need --full")
+    return args
 
 
 def _free_port():
@@ -162,6 +180,19 @@ def psnr_parity(frame0, target_u8):
             "frame0_u8_bytes_differing_from_cpu_reference": int((diff > 0).sum()), "frame0_u8_max_diff": int(diff.max()),
             "psnr_parity_source": "frame 0 (rank 0); CPU side = the reference's run_model_inference + reference Restormer "
                                   "(tests/golden/restormer_fullsize_frame.npz, oracle/gen_golden.py --only fullsize_frame)"}
+
+
+def dump_outputs(out_dir, results, steps):
+    """--dump-outputs: what the last timed step returned to its caller - the uint8 frames (as float32, the first
+    DUMP_MAX_FRAMES) and each frame's SSE against its target (as float64) - for output-by-output comparisons of builds."""
+    if not results or results[-1][0] != steps - 1:
+        raise SystemExit(f"--dump-outputs: the last timed step (step {steps - 1}) did not complete")
+    pairs = results[-1][1]
+    os.makedirs(out_dir, exist_ok=True)
+    frames = torch.stack([o for o, _ in pairs[:DUMP_MAX_FRAMES]]).cpu().numpy().astype(np.float32)
+    sse = np.array([float(s.item()) for _, s in pairs], dtype=np.float64)
+    np.save(os.path.join(out_dir, "frames.npy"), frames)
+    np.save(os.path.join(out_dir, "sse.npy"), sse)
 
 
 def pmc_step_totals():
@@ -292,8 +323,8 @@ def main():
                                                 pad8=True, targets_dev=[targets[j] for j in ids],
                                                 max_batch=model.max_tiles_per_batch, keep_tiles=keep)
 
-    keep = []
-    frame0 = None                                   # (uint8 frame, SSE) of frame 0: the PSNR-parity record below
+    keep = [] if args.full else None                # --full: tile 0 of the first warm-up step for the CPU baseline's comparison
+    frame0 = None                                   # (uint8 frame, SSE) of frame 0: the PSNR-parity record below (--full)
     for i in range(args.warmup):
         r = step(i, keep if i == 0 else None)
         if i == 0:
@@ -302,10 +333,10 @@ def main():
 
     # Per-launch events on EVERY launch (~600 per step) belong to an un-timed profile step: on some hosts of the pool they slow the
     # step itself by up to 60 % (same box, alternating processes - 71 ... 75 ms per frame with them, 46.3 ... 46.5
-    # without, host enqueue time 125 instead of 9 ms per step).  The timed steps carry events around the launches of the ROOFLINE
+    # without, host enqueue time 125 instead of 9 ms per step).  Under --full the timed steps carry events around the launches of the ROOFLINE
     # kernel only (the group with the largest share in the profile step: 24 launches per step).
     ks_all, timer = None, None
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         prof = ops.KernelTimer(detail=args.detail is not None)
         ops.TIMER = prof
         step(0)
@@ -347,7 +378,9 @@ def main():
     elapsed, table, failed_all = parallel.gather_results(elapsed, rows, dev, failed_ids=failed)
     psnr = table[:, 1].numpy() if table.shape[0] else np.array([float("nan")])
     n_done = int(table.shape[0])
-    if frame0 is None and rank == 0:                # --warmup 0: frame 0 for the parity record, outside the timed region
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, results, args.steps)
+    if args.full and frame0 is None and rank == 0:  # --warmup 0: frame 0 for the parity record, outside the timed region
         frame0 = step(0, keep)[0]
 
     if rank == 0:
@@ -371,7 +404,8 @@ def main():
             "psnr_db_mean": float(psnr.mean()), "psnr_db_std": float(psnr.std()),
             "failed_image_ids": failed_all,
         }
-        out.update(psnr_parity(frame0, host_frames[0][1]))
+        if args.full:
+            out.update(psnr_parity(frame0, host_frames[0][1]))
         if timer is not None:
             kd = timer.summary()                           # the roofline kernel in the timed steps
             ks = ks_all                                    # every kernel in the profile step
@@ -470,7 +504,7 @@ def main():
                         "at this build's kernel boundaries after fusion (timer rows); own_* = this build's own boundary bytes / "
                         "8 TB/s vs its issued matrix work (3 fp16 MFMA passes per emulated fp32 product) / 2.5 PFLOP/s; "
                         "hbm_util = HBM bytes per frame measured by the committed PMC passes / (step time x 8 TB/s)"}
-        if world == 1 and not args.no_legs and not os.environ.get("IRM_GEMM_EXACT"):
+        if args.full and world == 1 and not args.no_legs and not os.environ.get("IRM_GEMM_EXACT"):
             # reference legs, each in its own process (the emulation switch is read when the weights are packed)
             torch.cuda.synchronize()
             ex = child_leg(["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-kernel-timer", "--no-legs"],
@@ -481,7 +515,7 @@ def main():
             out["value_pcie_inclusive"] = None if pc is None else pc["value"]
             out["value_pcie_inclusive_note"] = ("get_model_prediction(model, numpy_frame, device, **patch_config): uint8 frame in "
                                                 "host memory -> uint8 frame in host memory, synchronous, 8 frames")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             gpu_tile = keep[0][0] if keep else None
             out["cpu_baseline"] = cpu_baseline(model, host_frames[0][0], gpu_tile, args.cpu_tile)
         print(json.dumps(out))

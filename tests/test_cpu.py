@@ -340,7 +340,9 @@ def test_asan_host_build_rejects_bad_arguments(tmp_path):
         "    if rc != -1: bad.append((name, rc))\n"
         "print('checked', len(_hip.SIGNATURES) - 1, 'bad', bad)\n"
         "sys.exit(1 if bad else 0)\n" % (os.path.dirname(os.path.dirname(_hip.LIB_PATH)), lib))
-    env = dict(os.environ, LD_PRELOAD=rt[-1], ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=99")
+    # the ASan runtime first, whatever the environment already preloads after it
+    preload = " ".join([rt[-1]] + ([os.environ["LD_PRELOAD"]] if os.environ.get("LD_PRELOAD") else []))
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=99")
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert "ERROR: AddressSanitizer" not in r.stderr
@@ -381,6 +383,37 @@ def test_bench_self_launch_command(monkeypatch):
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and "--nproc-per-node=4" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_full_option_and_output_dump(monkeypatch, tmp_path):
+    """bench.py: --full is off by default (the kernel-table options refuse to run without it), --steps is taken as
+    given, and --dump-outputs writes the last timed step's frames (float32, bounded) and SSEs (float64); checked on host tensors."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert not args.full and args.steps == 3 and args.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--detail", "k.json"])
+    assert bench.parse().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--detail", "k.json"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+    def fake_step(i, n):
+        g = torch.Generator().manual_seed(i)
+        return [(torch.randint(0, 256, (bench.H, bench.W, bench.C), generator=g, dtype=torch.uint8),
+                 torch.tensor([1000 * i + k], dtype=torch.int64)) for k in range(n)]
+    results = [(i, fake_step(i, 7)) for i in range(3)]
+    bench.dump_outputs(str(tmp_path / "d"), results, 3)
+    frames, sse = np.load(tmp_path / "d" / "frames.npy"), np.load(tmp_path / "d" / "sse.npy")
+    assert frames.dtype == np.float32 and frames.shape == (bench.DUMP_MAX_FRAMES, bench.H, bench.W, bench.C)
+    assert frames.nbytes + sse.nbytes <= 64 * 10 ** 6
+    assert np.array_equal(frames, torch.stack([o for o, _ in results[-1][1][:bench.DUMP_MAX_FRAMES]]).numpy())
+    assert sse.dtype == np.float64 and sse.tolist() == [2000.0 + k for k in range(7)]
+    with pytest.raises(SystemExit):                # the last timed step failed: nothing to compare, no silent dump
+        bench.dump_outputs(str(tmp_path / "e"), results[:2], 3)
 
 
 def test_split_range_guard_falls_back_per_layer():

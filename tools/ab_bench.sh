@@ -5,7 +5,7 @@ OUT=$1; shift
 : > $OUT
 for round in 1 2 3; do
   for lib in "$@"; do
-    IRM_HIP_LIB=$lib python3 bench.py --steps 6 --warmup 2 --no-legs --no-cpu-baseline 2>/dev/null | python3 -c "
+    IRM_HIP_LIB=$lib python3 bench.py --full --steps 6 --warmup 2 --no-legs --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({'lib':'$lib','round':$round,'ms_per_frame':d['ms_per_frame'],'kernels':{k:round(v['ms_per_frame'],3) for k,v in d['kernels'].items()}}))" >> $OUT

@@ -6,7 +6,7 @@ OUT=$1; shift
 for round in 1 2 3; do
   for setting in "$@"; do
     if [ -n "$setting" ]; then export "$setting"; fi
-    python3 bench.py --steps 6 --warmup 2 --no-legs --no-cpu-baseline 2>/dev/null | python3 -c "
+    python3 bench.py --full --steps 6 --warmup 2 --no-legs --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(json.dumps({'setting':'$setting','round':$round,'ms_per_frame':d['ms_per_frame'],'abs_dpsnr':d.get('abs_dpsnr'),'kernels':{k:round(v['ms_per_frame'],3) for k,v in d['kernels'].items()}}))" >> $OUT

@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/profiles/$(dirname $NAME); mkdir -p $OUT
 BASE=$(basename $NAME)
 export TMPDIR=/tmp IRM_GIT_SHA=$SHA
-CMD="python3 $ROOT/bench.py --steps 4 --warmup 2 --no-legs"
+CMD="python3 $ROOT/bench.py --full --steps 4 --warmup 2 --no-legs"
 cd /tmp
 rm -rf /tmp/prof_kt /tmp/prof_f /tmp/prof_w
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- $CMD > $OUT/${BASE}_bench_profiled.json 2> /tmp/prof_kt.err
@@ -25,5 +25,5 @@ cd $ROOT
 python3 tools/pmc_traffic.py /tmp/prof_f /tmp/prof_w $OUT/${BASE}_pmc_traffic.json
 # the bench line itself (un-profiled), reading the traffic file just written
 mkdir -p profiles/$(dirname $NAME); cp $OUT/${BASE}_pmc_traffic.json profiles/${NAME}_pmc_traffic.json
-python3 bench.py > $OUT/${BASE}_bench.json 2> $OUT/${BASE}_bench.err
+python3 bench.py --full > $OUT/${BASE}_bench.json 2> $OUT/${BASE}_bench.err
 tail -c 400 $OUT/${BASE}_bench.json

@@ -8,7 +8,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/profiles/$(dirname $NAME); mkdir -p $OUT
 BASE=$(basename $NAME)
 export TMPDIR=/tmp
-CMD="python3 $ROOT/bench.py --steps 2 --warmup 1 --no-legs --no-cpu-baseline"
+CMD="python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-legs --no-cpu-baseline"
 cd /tmp
 rm -rf /tmp/sq1 /tmp/sq2
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d /tmp/sq1 -- $CMD > /dev/null 2> /tmp/sq1.err
