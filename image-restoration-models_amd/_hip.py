@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libirm_hip.so")
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_SILU, ACT_RELU6 = 0, 1, 2, 3, 4
 LN_NONE, LN_WITHBIAS, LN_BIASFREE = 0, 1, 2
 
-_P, _L, _I, _F = C.c_void_p, C.c_long, C.c_int, C.c_float
+_P, _L, _I, _F, _D = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_double
 
 #: symbol -> argtypes, mirrors include/irm_hip.h one to one
 SIGNATURES = {
@@ -63,6 +63,7 @@ SIGNATURES = {
     "irm_selective_scan_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "irm_losh_combine_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P],
     "irm_window_blend": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P],
+    "irm_frame_metrics": [_P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _L, _P],
 }
 
 _lib = None

@@ -8,9 +8,11 @@ import csv
 import os
 
 import numpy as np
+import torch
 
 from . import synth
-from .utils import calculate_metrics, get_model_prediction, get_model_total_parameters
+from .utils import (_get_model_prediction, calculate_metrics, calculate_metrics_device, get_model_prediction,
+                    get_model_total_parameters)
 
 COLUMNS = ['Task', 'Type', 'Dataset', 'Sigma', 'Model', 'Model_Params', 'PSNR', 'SSIM', 'Std_PSNR', 'Std_SSIM',
            'Avg_Time_ms', 'Std_Time_ms']
@@ -24,24 +26,39 @@ def synthetic_loader(n_images: int, h: int = 720, w: int = 1280, c: int = 3, see
 
 
 def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: str, dataset: str, model_name: str,
-             sigma='N/A', need_degradation=False, noise_level=None, with_ssim=True, skip_failed=True) -> dict:
+             sigma='N/A', need_degradation=False, noise_level=None, with_ssim=True, skip_failed=True,
+             metrics="host") -> dict:
     """One results_table row (scripts/tests.py:399-412).
 
     The reference's loop lets any exception of a frame end the whole sweep (only a missing weight file is caught,
     tests.py:48-50).  Here a frame that raises is recorded and skipped (report the failed image
     ids instead of losing the run): the row's extra key 'Failed' lists (name, error) pairs and the statistics are
     taken over the frames that ran; `skip_failed=False` restores the reference's behaviour (the exception
-    propagates).  Out-of-memory errors always propagate (src/utils.py:91-93 reports them to the caller)."""
+    propagates).  Out-of-memory errors always propagate (src/utils.py:91-93 reports them to the caller).
+
+    metrics="host" scores the downloaded prediction with calculate_metrics (numpy / scipy); metrics="device" scores the
+    restored frame while it is still on the GPU (calculate_metrics_device, uint8 / uint16 frames only): the target is
+    uploaded, and PSNR / SSIM differ from the host's by rounding only (the tests allow 1e-9).  Either way the prediction and the timed work (input
+    upload through output download) are the same, and the metrics are not timed."""
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
     psnr_list, ssim_list, time_list, failed = [], [], [], []
     for input_img, target_img, name in loader:
         try:
-            pred, ms = get_model_prediction(model, input_img, device, **patch_config, need_degradation=need_degradation,
-                                            noise_level=noise_level)
-            if with_ssim:
-                p, s = calculate_metrics(pred, target_img)
+            if metrics == "device":
+                pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
+                                                           need_degradation=need_degradation, noise_level=noise_level)
+                p, s = _device_metrics(pred, pred_dev, target_img, device)
+                if not with_ssim:
+                    s = float('nan')
             else:
-                from .utils import psnr
-                p, s = psnr(target_img, pred, 255 if pred.dtype == np.uint8 else 65535), float('nan')
+                pred, ms = get_model_prediction(model, input_img, device, **patch_config,
+                                                need_degradation=need_degradation, noise_level=noise_level)
+                if with_ssim:
+                    p, s = calculate_metrics(pred, target_img)
+                else:
+                    from .utils import psnr
+                    p, s = psnr(target_img, pred, 255 if pred.dtype == np.uint8 else 65535), float('nan')
         except Exception as e:                                  # noqa: BLE001 (reported, not swallowed)
             if not skip_failed or "out of memory" in str(e).lower():
                 raise
@@ -55,6 +72,19 @@ def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: s
                     model_name=model_name, params=get_model_total_parameters(model))
     row['Failed'] = failed
     return row
+
+
+def _device_metrics(pred, pred_dev, target_img, device):
+    """(psnr, ssim) of one frame on the GPU: pred_dev is the pipeline's output tensor (None after the host tile loop:
+    the prediction is uploaded), the target goes up as the input did (uint16 as its int16 bit pattern)."""
+    if not isinstance(target_img, np.ndarray) or target_img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("metrics='device' needs uint8 or uint16 target frames")
+    if pred_dev is None:
+        pred_dev = torch.from_numpy(np.ascontiguousarray(pred.view(np.int16) if pred.dtype == np.uint16 else pred))
+        pred_dev = pred_dev.to(device)
+    tgt = target_img.view(np.int16) if target_img.dtype == np.uint16 else target_img
+    tgt_dev = torch.from_numpy(np.ascontiguousarray(tgt)).to(pred_dev.device)
+    return calculate_metrics_device(pred_dev, tgt_dev)
 
 
 def aggregate(psnr_list, ssim_list, time_list, *, task, subtask, dataset, sigma, model_name, params) -> dict:

@@ -185,6 +185,86 @@ def calculate_metrics(pred: np.ndarray, target: np.ndarray, data_range=None):
     return psnr_value, ssim_value
 
 
+#: output tile of irm_frame_metrics (csrc/metrics.hip): 16 rows x 192 values (pixels x channels), one partial each
+_METRICS_TILE_ROWS, _METRICS_TILE_VALUES = 16, 192
+#: int16 is read as the uint16 bit pattern, as the tiler does (its uint16 frames travel as int16 tensors)
+_METRICS_DTYPES = (torch.uint8, torch.uint16, torch.int16)
+
+
+def _metrics_frame_shape(pred, target) -> tuple:
+    """(H, W, C) of a prediction / target pair for the device metrics; ValueError before any GPU call otherwise."""
+    if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise ValueError("device metrics take torch tensors (use calculate_metrics for numpy arrays)")
+    if tuple(pred.shape) != tuple(target.shape) or pred.dtype != target.dtype:
+        raise ValueError(f"prediction {tuple(pred.shape)} {pred.dtype} and target {tuple(target.shape)} "
+                         f"{target.dtype} differ in shape or dtype")
+    if pred.dtype not in _METRICS_DTYPES:
+        raise ValueError(f"device metrics take uint8 or uint16 frames, not {pred.dtype}")
+    if pred.dim() == 2:
+        (h, w), c = pred.shape, 1
+    elif pred.dim() == 3:
+        h, w, c = pred.shape
+    else:
+        raise ValueError(f"device metrics take HW or HWC frames, not shape {tuple(pred.shape)}")
+    if c not in (1, 3):
+        raise ValueError(f"device metrics take 1 or 3 channels, not {c}")
+    if min(h, w) < 7:
+        raise ValueError(f"frame {h}x{w}: both sides must be at least 7, the SSIM window (skimage refuses it too)")
+    if not pred.is_cuda or not target.is_cuda:
+        raise ValueError("device metrics need GPU tensors; there is no CPU fallback (calculate_metrics takes host arrays)")
+    if pred.device != target.device:
+        raise ValueError(f"prediction on {pred.device}, target on {target.device}")
+    return h, w, c
+
+
+def frame_metrics_device(preds, targets, data_range=None):
+    """Device SSE and SSIM of K prediction / target frames of one shape (irm_frame_metrics): lists of uint8 or uint16
+    HW / HWC (C = 1 or 3) GPU tensors, e.g. the tiler's outputs.  Returns device tensors (sse [K] int64, exact;
+    ssim [K] float64, the values of `ssim` above: channel mean for C = 3) without synchronising with the host.  Same
+    data_range rule as calculate_metrics.  A frame's values are bitwise the same whatever K and on every call."""
+    preds, targets = list(preds), list(targets)
+    if not preds or len(preds) != len(targets):
+        raise ValueError(f"{len(preds)} predictions and {len(targets)} targets: need the same number, at least one")
+    h, w, c = _metrics_frame_shape(preds[0], targets[0])
+    for p, t in zip(preds, targets):
+        if (_metrics_frame_shape(p, t) != (h, w, c) or p.shape != preds[0].shape or p.dtype != preds[0].dtype
+                or p.device != preds[0].device):
+            raise ValueError("the frames of one call must share shape, dtype and device")
+    is_u16 = preds[0].dtype != torch.uint8
+    if data_range is None:
+        data_range = 65535 if is_u16 else 255
+    if not (np.isfinite(data_range) and data_range > 0):
+        raise ValueError(f"data_range must be positive and finite, not {data_range}")
+    # uint16 as its int16 bit pattern: the copies below need no uint16 kernels
+    as_bits = (lambda x: x.view(torch.int16)) if preds[0].dtype == torch.uint16 else (lambda x: x)
+    k, dev = len(preds), preds[0].device
+    with torch.cuda.device(dev):
+        if k == 1:
+            p, t = as_bits(preds[0]).contiguous(), as_bits(targets[0]).contiguous()
+        else:
+            p, t = torch.stack([as_bits(x) for x in preds]), torch.stack([as_bits(x) for x in targets])
+        tiles = -(-(h - 6) // _METRICS_TILE_ROWS) * -(-(w - 6) // (_METRICS_TILE_VALUES // c))
+        ws = torch.empty(2 * k * tiles, dtype=torch.float64, device=dev)
+        sse = torch.empty(k, dtype=torch.int64, device=dev)
+        ssim_dev = torch.empty(k, dtype=torch.float64, device=dev)
+        _hip.call("irm_frame_metrics", _hip.ptr(p), _hip.ptr(t), int(is_u16), k, h, w, c, float(data_range),
+                  _hip.ptr(sse), _hip.ptr(ssim_dev), _hip.ptr(ws), ws.numel())
+    return sse, ssim_dev
+
+
+def calculate_metrics_device(pred_dev: torch.Tensor, target_dev: torch.Tensor, data_range=None):
+    """Device twin of calculate_metrics for uint8 / uint16 GPU frames (HWC with 3 channels: channel-mean SSIM; HW1 and
+    HW: grey): (psnr, ssim) as Python floats after one synchronising copy.  PSNR is inf for identical frames."""
+    h, w, c = _metrics_frame_shape(pred_dev, target_dev)
+    if data_range is None:
+        data_range = 255 if pred_dev.dtype == torch.uint8 else 65535
+    sse, ssim_dev = frame_metrics_device([pred_dev], [target_dev], data_range)
+    host = torch.stack([sse, ssim_dev.view(torch.int64)]).cpu()       # the one host synchronisation
+    sse_v, ssim_v = int(host[0, 0]), float(host[1].view(torch.float64)[0])
+    err = sse_v / (h * w * c)
+    return (float('inf') if sse_v == 0 else float(10 * np.log10((data_range ** 2) / err))), ssim_v
+
+
 # ---------------------------------------------------------------------------
 # tiled-patch inference
 # ---------------------------------------------------------------------------
@@ -404,7 +484,18 @@ def run_model_inference(model: Module, input_img: np.ndarray, device: torch.devi
     pipeline; anything else (float images, custom hooks) takes a per-tile loop
     with the reference's host-side blend - the model forward is the HIP path
     in both."""
+    output_img, ms, _ = _run_model_inference(model, input_img, device, normalize, patch_size, patch_overlap,
+                                             need_degradation, noise_level, pad, postprocess)
+    return output_img, ms
+
+
+def _run_model_inference(model, input_img, device, normalize=normalize, patch_size=None, patch_overlap=32,
+                         need_degradation=False, noise_level=None, pad=None, postprocess=None):
+    """run_model_inference that also hands back the device pipeline's output tensor (uint8, or uint16 as int16 bits;
+    None after the per-tile host loop): (prediction, inference_time_ms, out_dev).  The time covers the same work as
+    run_model_inference's, input upload through output download."""
     start_time = time.time()
+    out = None
     dg = (normalize is deblurganv2.normalize and pad is deblurganv2.pad and postprocess is deblurganv2.postprocess
           and input_img.dtype == np.uint8)
     stock = dg or (normalize is globals()['normalize'] and (pad is None or pad is globals()['pad'])
@@ -424,7 +515,7 @@ def run_model_inference(model: Module, input_img: np.ndarray, device: torch.devi
         else:
             output_img = _run_tiles_on_host(model, input_img, device, normalize, patch_size, patch_overlap,
                                             need_degradation, noise_level, pad, postprocess)
-    return output_img, (time.time() - start_time) * 1000
+    return output_img, (time.time() - start_time) * 1000, out
 
 
 def _run_tiles_on_host(model, input_img, device, normalize_fn, patch_size, patch_overlap, need_degradation,
@@ -470,11 +561,19 @@ def _run_tiles_on_host(model, input_img, device, normalize_fn, patch_size, patch
 def get_model_prediction(model: Module, input_image: np.ndarray, device: torch.device, patch_size: int,
                          patch_overlap: int, need_degradation=False, noise_level=None, progress_bar=None):
     """src/utils.py:270-311: dispatch on the model class (reflect-pad-to-8 models vs plain)."""
+    pred, ms, _ = _get_model_prediction(model, input_image, device, patch_size, patch_overlap, need_degradation,
+                                        noise_level)
+    return pred, ms
+
+
+def _get_model_prediction(model, input_image, device, patch_size, patch_overlap, need_degradation=False,
+                          noise_level=None):
+    """get_model_prediction through _run_model_inference: (prediction, inference_time_ms, out_dev or None)."""
     kw = dict(patch_size=patch_size, patch_overlap=patch_overlap, need_degradation=need_degradation,
-              noise_level=noise_level, progress_bar=progress_bar)
+              noise_level=noise_level)
     if isinstance(model, (FPNMobileNet,)):                      # utils.py:280-291
-        return run_model_inference(model, input_image, device, normalize=deblurganv2.normalize, pad=deblurganv2.pad,
-                                   postprocess=deblurganv2.postprocess, **kw)
+        return _run_model_inference(model, input_image, device, normalize=deblurganv2.normalize, pad=deblurganv2.pad,
+                                    postprocess=deblurganv2.postprocess, **kw)
     if isinstance(model, _PAD8_MODELS):
-        return run_model_inference(model, input_image, device, pad=pad, **kw)
-    return run_model_inference(model, input_image, device, **kw)
+        return _run_model_inference(model, input_image, device, pad=pad, **kw)
+    return _run_model_inference(model, input_image, device, **kw)

@@ -369,6 +369,20 @@ int irm_window_blend(const float* pred, const int* origins, const float* window,
                      const void* target, unsigned long long* sse, int H, int W, int Co, int Cp, int th, int tw,
                      int ph, int pw, int ps, int T, float post_scale, float post_shift, irm_stream_t stream);
 
+/* Per-frame PSNR / SSIM inputs of the benchmark loop (src/utils.py:134-156, calculate_metrics: PSNR and
+ * skimage structural_similarity with its defaults) for K frames of one shape: pred and target
+ * [K][H][W][C] interleaved, both uint8 (is_u16 = 0) or both uint16 (is_u16 = 1), C = 1 or 3, H, W >= 7,
+ * H*W*C < 2^31.  Writes, per frame k:
+ *   sse[k]  = exact sum of squared differences over all H*W*C values (device, 64-bit);
+ *   ssim[k] = SSIM (7x7 uniform window, K1 = 0.01, K2 = 0.03 on data_range, sample covariance 49/48)
+ *             averaged over the interior pixels S[3:H-3][3:W-3] and, for C = 3, over the channels.
+ * Window moments are exact integers, the per-pixel ratio is fp64.  Bitwise reproducible: per-workgroup
+ * partials are written to ws and summed in a fixed order by a second launch (no atomics), so a frame's
+ * values do not depend on K.  Workspace of 8-byte words:
+ *   ws_words >= 2 * K * ceil((H - 6) / 16) * ceil((W - 6) / (192 / C)). */
+int irm_frame_metrics(const void* pred, const void* target, int is_u16, int K, int H, int W, int C, double data_range,
+                      unsigned long long* sse, double* ssim, void* ws, long ws_words, irm_stream_t stream);
+
 /* --- DeblurGANv2 FPN-MobileNet (train-mode norms = per-(sample, channel) statistics) ---
  * stats[b][c] = {mean, 1/sqrt(biased var + eps)} over the H*W plane: BatchNorm2d in train mode on one
  * tile (mobilenet_v2.py:5-57 with deblurganv2/__init__.py:38) and InstanceNorm2d (fpn_mobilenet.py:96-104). */
