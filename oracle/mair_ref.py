@@ -1,6 +1,6 @@
 """ORACLE (test infrastructure only - never imported by the product path).
 
-CPU restatement (functional PyTorch fp32) of MaIRUNet's forward
+CPU restatement (functional PyTorch fp32; float64 throughout when given float64 inputs and parameters) of MaIRUNet's forward
 (src/mair/realDenoising/basicsr/models/archs/mairunet_arch.py:21-739), its scan-index tables
 (shift_scanf_util.py:67-244; MaIRUNet never passes shift_size, :476-581, the flat MaIR alternates) and of the
 third-party selective scan it calls (mamba_ssm==2.2.5 `selective_scan_fn`, NOT in the reference tree).
@@ -56,22 +56,23 @@ def selective_scan(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_sof
     b, kd, L = u.shape
     k, n = B.shape[1], A.shape[1]
     d = kd // k
-    u, delta = u.float(), delta.float()
+    f = u.dtype if u.dtype == torch.float64 else torch.float32     # float64 in -> float64 throughout, else fp32
+    u, delta = u.to(f), delta.to(f)
     if delta_bias is not None:
-        delta = delta + delta_bias.float().view(1, -1, 1)
+        delta = delta + delta_bias.to(f).view(1, -1, 1)
     if delta_softplus:
         delta = F.softplus(delta)
-    Bx = B.float().repeat_interleave(d, dim=1)          # (b, kd, n, L)
-    Cx = C.float().repeat_interleave(d, dim=1)
-    h = torch.zeros(b, kd, n, dtype=torch.float32)
+    Bx = B.to(f).repeat_interleave(d, dim=1)            # (b, kd, n, L)
+    Cx = C.to(f).repeat_interleave(d, dim=1)
+    h = torch.zeros(b, kd, n, dtype=f)
     ys = []
     for t in range(L):
         dt = delta[:, :, t].unsqueeze(-1)
-        h = torch.exp(dt * A.float().unsqueeze(0)) * h + dt * Bx[:, :, :, t] * u[:, :, t].unsqueeze(-1)
+        h = torch.exp(dt * A.to(f).unsqueeze(0)) * h + dt * Bx[:, :, :, t] * u[:, :, t].unsqueeze(-1)
         ys.append((h * Cx[:, :, :, t]).sum(-1))
     y = torch.stack(ys, dim=-1)
     if D is not None:
-        y = y + D.float().view(1, -1, 1) * u
+        y = y + D.to(f).view(1, -1, 1) * u
     return y
 
 
@@ -94,8 +95,9 @@ def losh2d(x, p, pre, ids, inv):
     x_dbl = torch.einsum("bkdl,kcd->bkcl", xs, Wx)
     dts, Bs, Cs = torch.split(x_dbl, [R, N, N], dim=2)
     dts = torch.einsum("bkrl,kdr->bkdl", dts, Wdt)
-    y = selective_scan(xs.reshape(B, -1, L), dts.reshape(B, -1, L), -torch.exp(p[pre + "A_logs"].float()),
-                       Bs, Cs, p[pre + "Ds"].float(), delta_bias=p[pre + "dt_projs_bias"].float().reshape(-1),
+    f = xs.dtype if xs.dtype == torch.float64 else torch.float32
+    y = selective_scan(xs.reshape(B, -1, L), dts.reshape(B, -1, L), -torch.exp(p[pre + "A_logs"].to(f)),
+                       Bs, Cs, p[pre + "Ds"].to(f), delta_bias=p[pre + "dt_projs_bias"].to(f).reshape(-1),
                        delta_softplus=True).view(B, K, Dn, L)
     y = torch.cat([y[:, k].index_select(-1, inv[k]) for k in range(K)], dim=1).reshape(B, K * Dn, H, W)
     # ShuffleAttn gate (:21-60): per d a 4x4 mix of the four directions' global means

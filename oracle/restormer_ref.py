@@ -74,8 +74,9 @@ def _conv3(x, w, b=None):
     return F.conv2d(x, w, b, padding=1)
 
 
-def restormer_forward(x, p, heads=(1, 2, 4, 8), dual_pixel_task=False):
-    """restormer.py:245-284.  x: (B, C_in, H, W) float32, H and W multiples of 8."""
+def restormer_forward(x, p, heads=(1, 2, 4, 8), dual_pixel_task=False, tap=None):
+    """restormer.py:245-284.  x: (B, C_in, H, W) float32 (or float64 with a float64 state dict), H and W multiples
+    of 8.  tap: optional dict that receives the `refinement` output (before the output conv) under "refinement"."""
     e1_in = _conv3(x, p["patch_embed.proj.weight"], p.get("patch_embed.proj.bias"))
     e1 = _stage(e1_in, p, "encoder_level1", heads[0])
     e2 = _stage(F.pixel_unshuffle(_conv3(e1, p["down1_2.body.0.weight"]), 2), p, "encoder_level2", heads[1])
@@ -93,6 +94,8 @@ def restormer_forward(x, p, heads=(1, 2, 4, 8), dual_pixel_task=False):
     d1 = torch.cat([F.pixel_shuffle(_conv3(d2, p["up2_1.body.0.weight"]), 2), e1], dim=1)
     d1 = _stage(d1, p, "decoder_level1", heads[0])
     d1 = _stage(d1, p, "refinement", heads[0])
+    if tap is not None:
+        tap["refinement"] = d1
 
     if dual_pixel_task:
         d1 = d1 + F.conv2d(e1_in, p["skip_conv.weight"], p.get("skip_conv.bias"))
