@@ -567,8 +567,11 @@ static int launch_ring(const GemmArgs& a, int B, int ygroups, hipStream_t stream
     // 6 x 512^2 409 -> 381 us, M = K = 192 at 6 x 128^2 65 -> 57 us, M 192 K 510 129 -> 125 us (round 3,
     // tools/bench_apply.py; a 5-deep ring at two workgroups had bought nothing in round 2).  Long reductions (K 1021:
     // 136 -> 144 us) want the deeper ring; 8 / 9 tiles per pass need more registers: both keep two workgroups.
+    // Not the split kernel at CT 4: that 3-deep instantiation (no spills, 136 VGPRs) returns wrong values in pixel
+    // tile p = 1 of output tile 0 for every shape (tests/test_gpu_gemm_variants.py), while its 4-deep sibling, the
+    // exact-f32 CT 4 and the split CT 3 / 6 3-deep instantiations are right; no production launch uses it.
 #ifndef IRM_NO_RING3                              // (variant builds for A/B: tools/build_variant.sh NAME -DIRM_NO_RING3 gemm_pw.hip)
-    if constexpr (PT == 2 && RES && CT <= 6) {
+    if constexpr (PT == 2 && RES && CT <= 6 && !(F16 && CT == 4)) {
         if (a.K <= 512) return launch_ring_ns<PT, CT, 3, LN, RES, F16>(a, B, ygroups, stream);
     }
 #endif

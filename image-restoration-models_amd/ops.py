@@ -121,6 +121,27 @@ def ln_stats(x: torch.Tensor, stats: torch.Tensor, eps: float = 1e-5):
             _hip.ptr(stats), B, C, N, float(eps), tag=f"C{C} N{N} B{B}")
 
 
+def plan_gemm1x1(M: int, K: int, N: int, B: int, *, split: bool = False, res: bool = False, stats_out: bool = False,
+                 ct: int | None = None, ygroups: int | None = None):
+    """(ct, ygroups) of a gemm1x1 launch: output-channel tiles per pass and the workgroups sharing a pixel tile's passes.
+    Explicit values are kept; stats_out needs every output tile in one pass (one workgroup per pixel tile)."""
+    mt = (M + 15) // 16
+    if ct is None and ygroups is None and not stats_out:
+        # pixels per workgroup of the kernel that will run: 256 (emulated, no residual) or 128
+        bn = 256 if (split and not res) else 128
+        ct, ygroups = _hip.plan_gemm(mt, -(-N // bn) * B, res=res and K <= 512)
+    if ct is None:
+        ct = _hip.choose_ct(mt)
+    if ygroups is None:
+        nchunks = -(-mt // ct)
+        blocks = -(-N // 128) * B
+        ygroups = max(1, min(nchunks, -(-target_blocks() // blocks)))
+    if stats_out:
+        assert mt <= ct, "fused output statistics need all output channels in one pass"
+        ygroups = 1
+    return ct, ygroups
+
+
 def gemm1x1(wp: torch.Tensor, x: torch.Tensor, y: torch.Tensor, M: int, K: int, *, res=None, bias=None,
             stats=None, lnw=None, lnb=None, ln_mode=LN_NONE, act=ACT_NONE, w_bs: int = 0, ct: int | None = None,
             ygroups: int | None = None, stats_out=None, eps: float = 1e-5, res_scale=None, split: bool = False):
@@ -132,20 +153,8 @@ def gemm1x1(wp: torch.Tensor, x: torch.Tensor, y: torch.Tensor, M: int, K: int, 
     assert x.shape[1] >= K and y.shape[1] >= M
     if res is not None:
         _chk(res, "res")
-    mt = (M + 15) // 16
-    if ct is None and ygroups is None and stats_out is None:
-        # pixels per workgroup of the kernel that will run: 256 (emulated, no residual) or 128
-        bn = 256 if (split and res is None) else 128
-        ct, ygroups = _hip.plan_gemm(mt, -(-N // bn) * B, res=res is not None and K <= 512)
-    if ct is None:
-        ct = _hip.choose_ct(mt)
-    if ygroups is None:
-        nchunks = -(-mt // ct)
-        blocks = -(-N // 128) * B
-        ygroups = max(1, min(nchunks, -(-target_blocks() // blocks)))
-    if stats_out is not None:
-        assert mt <= ct, "fused output statistics need all output channels in one pass"
-        ygroups = 1
+    ct, ygroups = plan_gemm1x1(M, K, N, B, split=split, res=res is not None, stats_out=stats_out is not None, ct=ct,
+                               ygroups=ygroups)
     nbytes = 4.0 * B * N * (K + M + (M if res is not None else 0) + (2 if stats is not None else 0)
                             + (2 if stats_out is not None else 0))
     if split:
@@ -492,27 +501,12 @@ def mfold_numel(C: int) -> int:
     return mt * 4 * mt * 64
 
 
-def conv3x3(wp, x, y, ci: int, co: int, *, bias=None, relu1=False, res=None, res_mode=0, relu2=False,
-            store_mode=0, ct: int | None = None, ygroups: int | None = None):
-    """Dense 3x3 conv with fused epilogue; store_mode 1 = PixelUnshuffle(2), 2 = PixelShuffle(2).
-    wp: _hip.pack_conv3x3_weight(w) (exact f32 MFMA) or the pair _hip.pack_conv3x3_weight_split(w) (fp32 emulated on
-    the fp16 matrix cores, irm_conv3x3_f16x3_f32; needs W % 4 == 0 and 16-byte aligned rows)."""
-    _chk(x, "x"), _chk(y, "y")
-    B, _, H, W = x.shape
+def plan_conv3x3(co: int, H: int, W: int, B: int, *, split: bool, ct: int | None = None, ygroups: int | None = None):
+    """(ct, ygroups) of a conv3x3 launch on the exact (split=False) or the emulated (split=True) kernel; explicit values
+    are kept."""
     mt = (co + 15) // 16
     blocks = -(-W // 32) * -(-H // 8) * B
-    nbytes = 4.0 * B * H * W * (ci + co + (co if res is not None else 0))
-    if isinstance(wp, _hip.ConvWeight):
-        aligned = (W % 4 == 0 and _bs(x) % 4 == 0 and _bs(y) % 4 == 0 and _bs(res) % 4 == 0 and x.data_ptr() % 16 == 0
-                   and y.data_ptr() % 16 == 0 and (res is None or res.data_ptr() % 16 == 0))
-        if wp.raw is not None and aligned and store_mode == 0 and not os.environ.get("IRM_NO_THIN_CONV"):
-            _launch("conv3x3_thin", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_thin_f32", _hip.ptr(wp.raw), _hip.ptr(x),
-                    _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, int(relu1),
-                    int(res_mode), int(relu2), tag=f"ci{ci} co{co} {H}x{W} B{B}")
-            return
-        wp = (wp.split, wp.inv_scale) if (wp.split is not None and aligned) else wp.exact
-    if isinstance(wp, tuple):
-        wps, inv_scale = wp
+    if split:
         if ct is None:
             # output tiles per pass: 12 / 8 = 3 / 2 weight chunks of 4 per fetched + converted input tile (Co >= 128: the
             # up-sampling convs), else one chunk of <= 4
@@ -526,11 +520,7 @@ def conv3x3(wp, x, y, ci: int, co: int, *, bias=None, relu1=False, res=None, res
             ygroups = max(1, min(nchunks, -(-512 // blocks)))
             while nchunks % ygroups:                            # equal numbers of passes per workgroup
                 ygroups += 1
-        _launch("conv3x3_f16x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_f16x3_f32", _hip.ptr(wps), float(inv_scale),
-                _hip.ptr(x), _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W,
-                int(relu1), int(res_mode), int(relu2), int(store_mode), ct, ygroups,
-                tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}")
-        return
+        return ct, ygroups
     if ct is None:
         ct = _hip.choose_ct(mt, (6, 4, 3, 2, 1))
         # small images (FPN levels, level-4 tiles): fewer output tiles per workgroup so that the chip is filled
@@ -541,6 +531,35 @@ def conv3x3(wp, x, y, ci: int, co: int, *, bias=None, relu1=False, res=None, res
     if ygroups is None:
         nchunks = -(-mt // ct)
         ygroups = max(1, min(nchunks, -(-target_blocks() // blocks)))
+    return ct, ygroups
+
+
+def conv3x3(wp, x, y, ci: int, co: int, *, bias=None, relu1=False, res=None, res_mode=0, relu2=False,
+            store_mode=0, ct: int | None = None, ygroups: int | None = None):
+    """Dense 3x3 conv with fused epilogue; store_mode 1 = PixelUnshuffle(2), 2 = PixelShuffle(2).
+    wp: _hip.pack_conv3x3_weight(w) (exact f32 MFMA) or the pair _hip.pack_conv3x3_weight_split(w) (fp32 emulated on
+    the fp16 matrix cores, irm_conv3x3_f16x3_f32; needs W % 4 == 0 and 16-byte aligned rows)."""
+    _chk(x, "x"), _chk(y, "y")
+    B, _, H, W = x.shape
+    nbytes = 4.0 * B * H * W * (ci + co + (co if res is not None else 0))
+    if isinstance(wp, _hip.ConvWeight):
+        aligned = (W % 4 == 0 and _bs(x) % 4 == 0 and _bs(y) % 4 == 0 and _bs(res) % 4 == 0 and x.data_ptr() % 16 == 0
+                   and y.data_ptr() % 16 == 0 and (res is None or res.data_ptr() % 16 == 0))
+        if wp.raw is not None and aligned and store_mode == 0 and not os.environ.get("IRM_NO_THIN_CONV"):
+            _launch("conv3x3_thin", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_thin_f32", _hip.ptr(wp.raw), _hip.ptr(x),
+                    _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, int(relu1),
+                    int(res_mode), int(relu2), tag=f"ci{ci} co{co} {H}x{W} B{B}")
+            return
+        wp = (wp.split, wp.inv_scale) if (wp.split is not None and aligned) else wp.exact
+    if isinstance(wp, tuple):
+        wps, inv_scale = wp
+        ct, ygroups = plan_conv3x3(co, H, W, B, split=True, ct=ct, ygroups=ygroups)
+        _launch("conv3x3_f16x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_f16x3_f32", _hip.ptr(wps), float(inv_scale),
+                _hip.ptr(x), _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W,
+                int(relu1), int(res_mode), int(relu2), int(store_mode), ct, ygroups,
+                tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}")
+        return
+    ct, ygroups = plan_conv3x3(co, H, W, B, split=False, ct=ct, ygroups=ygroups)
     _launch("conv3x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_f32", _hip.ptr(wp), _hip.ptr(x), _bs(x),
             _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, int(relu1), int(res_mode),
             int(relu2), int(store_mode), ct, ygroups, tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}")
