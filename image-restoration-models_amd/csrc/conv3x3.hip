@@ -450,7 +450,7 @@ extern "C" int irm_conv3x3_f32(const float* wp, const float* x, long x_bs, float
     const int nchunks = (a.mtiles + ct - 1) / ct;
     if (ygroups <= 0) ygroups = 1;
     if (ygroups > nchunks) ygroups = nchunks;
-    const bool fast = a.vec && !(x_bs & 3) && irm_aligned16(x) && irm_aligned16(wp) && !irm_probe_set("IRM_CONV_GENERIC");
+    const bool fast = a.vec && !(x_bs & 3) && irm_aligned16(x) && irm_aligned16(wp);
     if (fast) {
         switch (ct) {
             case 1: return launch_conv_ring<1>(a, B, ygroups, stream);

@@ -23,7 +23,6 @@ struct DwGemmArgs {
     const float* bias;
     float* stats_out; float eps;
     int M, K, H, W, mtiles, ksteps, tiles_x, tiles;
-    int dbg;                           // IRM_DWGEMM_DBG: 1 = no DMA, 2 = no stencil/MFMA (profiling only)
 };
 
 template <int N>
@@ -221,7 +220,7 @@ void dwgemm_kernel(DwGemmArgs a) {
         for (int j = 0; j < R; ++j) {
             const float* src = (tail && s >= lim[j]) ? dg_zero_page : base[j];
             base[j] += stride[j];
-            if (!IRM_DBG(a.dbg, 1)) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(dst + j * NT * 4), 16, 0, 0);
         }
         if constexpr (F16) {
@@ -282,7 +281,6 @@ void dwgemm_kernel(DwGemmArgs a) {
         asm volatile("s_barrier" ::: "memory");
         if (s + NS - 1 < SL) issue(s + NS - 1);
 
-        if (IRM_DBG(a.dbg, 2)) continue;
         const float* xb = smem + (s % NS) * STG;
         const float* wb = xb + XC * 4;
         const v2f* dk = reinterpret_cast<const v2f*>(wb + WC * 4 + g * DWS);
@@ -402,26 +400,12 @@ static int dwgemm_entry(const float* wp, long w_bs, const float* dwp, const floa
     a.mtiles = (M + 15) / 16; a.ksteps = 4 * ((K + 15) / 16);
     a.tiles_x = (W + 31) / 32;
     a.tiles = a.tiles_x * ((H + 7) / 8);
-    a.dbg = irm_probe_int("IRM_DWGEMM_DBG", 0);
     if (split) {
-        // 64-wide tiles (IRM_DWGEMM_TW=64): fewer halo sectors, but measured 5-8 % slower than 32-wide ones
-        static const int tw_env = irm_probe_int("IRM_DWGEMM_TW", 0);
-        const bool wide = tw_env == 64;
-        if (wide) {
-            if (a.mtiles <= 3) return gate ? dg_launch<3, true, 4, true, 64>(a, B, stream) : dg_launch<3, false, 4, true, 64>(a, B, stream);
-            return gate ? dg_launch<6, true, 4, true, 64>(a, B, stream) : dg_launch<6, false, 4, true, 64>(a, B, stream);
-        }
         if (a.mtiles <= 3) return gate ? dg_launch<3, true, 4, true>(a, B, stream) : dg_launch<3, false, 4, true>(a, B, stream);
         return gate ? dg_launch<6, true, 4, true>(a, B, stream) : dg_launch<6, false, 4, true>(a, B, stream);
     }
-    static const int pt_env = irm_probe_int("IRM_DWGEMM_PT", 0);
-    const int pt = pt_env == 2 ? 2 : 4;      // 8 waves x 2 pixels: twice the occupancy, measured no faster
-    if (a.mtiles <= 3) {
-        if (pt == 4) return gate ? dg_launch<3, true, 4>(a, B, stream) : dg_launch<3, false, 4>(a, B, stream);
-        return gate ? dg_launch<3, true, 2>(a, B, stream) : dg_launch<3, false, 2>(a, B, stream);
-    }
-    if (pt == 4) return gate ? dg_launch<6, true, 4>(a, B, stream) : dg_launch<6, false, 4>(a, B, stream);
-    return gate ? dg_launch<6, true, 2>(a, B, stream) : dg_launch<6, false, 2>(a, B, stream);
+    if (a.mtiles <= 3) return gate ? dg_launch<3, true, 4>(a, B, stream) : dg_launch<3, false, 4>(a, B, stream);
+    return gate ? dg_launch<6, true, 4>(a, B, stream) : dg_launch<6, false, 4>(a, B, stream);
 }
 
 extern "C" int irm_dwgemm_f32(const float* wp, long w_bs, const float* dwp, const float* x, long x_bs, float* y,

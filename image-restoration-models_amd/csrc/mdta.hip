@@ -585,8 +585,7 @@ extern "C" int irm_mdta_gram_f32(const float* qkv, long bs, float* part, int B, 
     if (c % 16) return IRM_EINVAL;
     GramArgs a{qkv, bs, part, C, heads, N, chunk, (N + chunk - 1) / chunk, 0};
     const bool aligned = !(N & 3) && !(bs & 3) && irm_aligned16(qkv);
-    if (aligned && !(N & 63) && (c == 48 || c == 96) && (long)heads * a.nchunk <= 2147483647L &&
-        !irm_probe_set("IRM_GRAM_GENERIC"))
+    if (aligned && !(N & 63) && (c == 48 || c == 96) && (long)heads * a.nchunk <= 2147483647L)
         return c == 48 ? launch_gram_ring<3>(a, B, stream) : launch_gram_ring<6>(a, B, stream);
     const int sb = (c % 48 == 0) ? 3 : (c % 32 == 0) ? 2 : 1;
     const int nsb = c / (16 * sb);

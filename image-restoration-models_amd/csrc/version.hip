@@ -1,3 +1,3 @@
 // ABI version of libirm_hip.so (see include/irm_hip.h).
 #include "irm_common.h"
-extern "C" int irm_version(void) { return 1; }
+extern "C" int irm_version(void) { return 2; }

@@ -210,7 +210,7 @@ def ln_gemm_presplit(wps, x, y, M: int, K: int, lnw, lnb, ln_mode: int, x_scale:
     B, _, H, W = x.shape
     N = H * W
     ct, mgroups, shape = _hip.plan_presplit((M + 15) // 16, B * N // 16, K)
-    if K == 192 and mgroups == 1 and not os.environ.get("IRM_NO_LN_FUSE"):
+    if K == 192 and mgroups == 1:
         _launch("gemm_ps_f16x3", 2.0 * B * M * K * N, 4.0 * B * N * (K + M), "irm_ln_gemm_presplit_f16x3_f32", _hip.ptr(wps),
                 _hip.ptr(x), _bs(x), _hip.ptr(lnw), _hip.ptr(lnb), int(ln_mode), float(x_scale), float(eps), _hip.ptr(y), _bs(y),
                 _hip.ptr(bias), float(out_scale), B, M, K, N, 1, tag=f"M{M} K{K} N{N} B{B} ln-fused")
@@ -248,40 +248,6 @@ def gdfn_tail(pk, h_cl, x, C: int, hid: int, hid_pad: int, *, bias=None):
     _launch("gdfn_tail", B * N * (36.0 * hid + 2.0 * hid * C), 4.0 * B * N * (2 * hid_pad + 2 * C), "irm_gdfn_tail_f16x3_f32",
             _hip.ptr(h_cl), 2 * hid_pad * N, _hip.ptr(rec), _hip.ptr(w2), _hip.ptr(bias), _hip.ptr(x), _bs(x), float(inv_s2),
             B, C, hid, hid_pad, H, W, tag=f"C{C} hid{hid} {H}x{W} B{B}")
-
-
-GATE_SPLIT_SCALE = 0.0625      # 2^-4: gated activations up to ~1e6 stay inside fp16 (as irm_gemm1x1_f16x3_f32 without LN)
-
-
-def can_gate_split(M: int, hid: int, W: int, N: int) -> bool:
-    """GDFN tail on pre-split operands (gemm_ps.hip): gate -> fragments -> K-streamed GEMM; the C >= 192 levels."""
-    return 96 < M <= 384 and W % 16 == 0 and N % 16 == 0 and (-(-hid // 32)) % 4 == 0
-
-
-def dwconv3x3_gate_split(x, w9, gs, *, bias=None, scale: float = GATE_SPLIT_SCALE, ch: int = 0):
-    """gs = fp16 hi/lo fragments of gelu(dw(x[:, :hid])) * dw(x[:, hid:]) * scale (irm_dwconv3x3_gate_split_f16);
-    gs: flat float32 buffer of B * 32 ceil(hid/32) * H * W elements."""
-    _chk(x, "x")
-    B, C2, H, W = x.shape
-    hid = C2 // 2
-    kp = 32 * -(-hid // 32)
-    assert gs.numel() >= B * kp * H * W and gs.is_contiguous() and gs.dtype == torch.float32
-    _launch("dwconv3x3_gate_split", 18.0 * B * C2 * H * W, 4.0 * B * (C2 + kp) * H * W, "irm_dwconv3x3_gate_split_f16",
-            _hip.ptr(x), _bs(x), _hip.ptr(w9), _hip.ptr(bias), _hip.ptr(gs), float(scale), B, hid, H, W, int(ch),
-            tag=f"hid{hid} {H}x{W} B{B}")
-
-
-def gemm_presplit_res(wps, xs, y, M: int, KS: int, *, out_scale: float, res=None, bias=None, wg_shape: int = 0):
-    """y = res + bias + (W xs) * out_scale, K = 32 KS streamed (irm_gemm_presplit_res_f16x3_f32); y may be res."""
-    _chk(y, "y")
-    B, _, H, W = y.shape
-    N = H * W
-    assert y.shape[1] >= M and xs.numel() >= B * 32 * KS * N
-    if res is not None:
-        _chk(res, "res")
-    _launch("gemm_ps_res_f16x3", 2.0 * B * M * 32 * KS * N, 4.0 * B * N * (32 * KS + M + (M if res is not None else 0)),
-            "irm_gemm_presplit_res_f16x3_f32", _hip.ptr(wps), _hip.ptr(xs), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res),
-            _hip.ptr(bias), float(out_scale), B, M, KS, N, int(wg_shape), tag=f"M{M} K{32 * KS} N{N} B{B}")
 
 
 def dwconv3x3(x, w9, y, *, bias=None, act=ACT_NONE):
@@ -381,9 +347,8 @@ def can_qk_tile_major(C: int, heads: int, H: int, W: int) -> bool:
 def _use_qkv_cm(C: int) -> bool:
     """The channel-major qkv kernel (fused_qkv_cm.hip, bit-identical results): default where it is faster in the model - C <= 64
     (C = 48 at 512^2: 1.71 vs 1.85 ms per 24 tiles; its registers leave room to request the next input three iterations
-    early); at C = 96 it measures 3.12 vs 2.96 ms in the model (1.58 vs 1.66 ms in isolation).  IRM_QKV_CM=1 / 0 forces / forbids it."""
-    e = os.environ.get("IRM_QKV_CM")
-    return e == "1" if e in ("0", "1") else C <= 64
+    early); at C = 96 it measures 3.12 vs 2.96 ms in the model (1.58 vs 1.66 ms in isolation)."""
+    return C <= 64
 
 
 def qkv_dw_fused(pk, x, y, C: int, M: int, *, ln_mode, eps: float = 1e-5, tm: bool = False, x_tm: bool = False,
@@ -413,7 +378,7 @@ def mdta_plan(B: int, C: int, heads: int, N: int):
     c = C // heads
     sb = 3 if c % 48 == 0 else 2 if c % 32 == 0 else 1
     rec = c * c + 2 * c
-    if c in (48, 96) and N % 64 == 0 and not os.environ.get("IRM_GRAM_BLOCKS"):
+    if c in (48, 96) and N % 64 == 0:
         # the LDS-DMA ring kernels keep the whole c x c Gram in one workgroup of 72 KiB LDS: 2 per CU = 512 resident.
         # Whole rounds matter: 1026 workgroups (the old ceil(N / 1536) = 171 chunks x 6 images) are two full rounds
         # plus a third with 2 workgroups - half a round of the chip idle.  Cost model: rounds x (chunk + a fixed
@@ -426,9 +391,7 @@ def mdta_plan(B: int, C: int, heads: int, N: int):
                 best = (cost, chunk, nchunk)
         return best[1], best[2], rec
     nsub = (c // (16 * sb)) ** 2
-    tb = int(os.environ.get("IRM_GRAM_BLOCKS", 0)) or target_blocks()
-    per_wg = 1 if (c in (48, 96) and N % 64 == 0) else 4                        # units per workgroup
-    chunk = -(-(N * B * heads * (1 if per_wg == 1 else nsub)) // (per_wg * tb))
+    chunk = -(-(N * B * heads * nsub) // (4 * target_blocks()))                 # 4 units per workgroup
     chunk = min(max(-(-chunk // 64) * 64, 256), 4096)
     return chunk, -(-N // chunk), rec
 
@@ -475,7 +438,7 @@ def mdta_fold(qkv, part, gsum, temperature, wout, mfold, C: int, heads: int, att
     assert not tm or (c in (48, 96) and N % 256 == 0), "tile-major q, k: the LDS-DMA ring passes only"
     if nchunk_ready is not None:
         pass
-    elif gram_scale is not None and c in (48, 96) and N % 64 == 0 and not os.environ.get("IRM_GRAM_EXACT"):
+    elif gram_scale is not None and c in (48, 96) and N % 64 == 0:
         assert gram_scale.numel() == 2 * C and gram_scale.is_contiguous()
         _launch("mdta_gram_f16x3", 2.0 * B * heads * c * c * N, 8.0 * B * C * N,
                 "irm_mdta_gram_tm_f16x3_f32" if tm else "irm_mdta_gram_f16x3_f32", _hip.ptr(qkv),
@@ -511,8 +474,6 @@ def plan_conv3x3(co: int, H: int, W: int, B: int, *, split: bool, ct: int | None
             # output tiles per pass: 12 / 8 = 3 / 2 weight chunks of 4 per fetched + converted input tile (Co >= 128: the
             # up-sampling convs), else one chunk of <= 4
             ct = 12 if mt >= 12 else 8 if mt >= 8 else 4 if mt % 4 == 0 else 3 if mt % 3 == 0 or mt > 4 else min(mt, 4)
-            if os.environ.get("IRM_CONV_ONE_CHUNK"):
-                ct = 4 if mt % 4 == 0 or mt > 9 else 3 if mt % 3 == 0 or mt > 4 else min(mt, 4)
             while ct > 1 and blocks * -(-mt // ct) < 256:       # small images: more passes, more workgroups
                 ct = {12: 8, 8: 4}.get(ct, ct - 1)
         if ygroups is None:
@@ -545,7 +506,7 @@ def conv3x3(wp, x, y, ci: int, co: int, *, bias=None, relu1=False, res=None, res
     if isinstance(wp, _hip.ConvWeight):
         aligned = (W % 4 == 0 and _bs(x) % 4 == 0 and _bs(y) % 4 == 0 and _bs(res) % 4 == 0 and x.data_ptr() % 16 == 0
                    and y.data_ptr() % 16 == 0 and (res is None or res.data_ptr() % 16 == 0))
-        if wp.raw is not None and aligned and store_mode == 0 and not os.environ.get("IRM_NO_THIN_CONV"):
+        if wp.raw is not None and aligned and store_mode == 0:
             _launch("conv3x3_thin", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_thin_f32", _hip.ptr(wp.raw), _hip.ptr(x),
                     _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, int(relu1),
                     int(res_mode), int(relu2), tag=f"ci{ci} co{co} {H}x{W} B{B}")

@@ -194,10 +194,6 @@ class Restormer(nn.Module):
                     if _hip.split_is_safe(ff.project_out.weight):
                         pk[name]["pout_s"] = _hip.pack_gemm_weight_split(ff.project_out.weight)
                     pk[name]["mfold_split"] = _hip.split_is_safe(a.project_out.weight)
-                    if ops.can_gate_split(m.dim, ff.hidden, 16, 16):
-                        # GDFN tail on pre-split operands (gemm_ps.hip): project_out fragments, K padded to 32 ceil(hid / 32)
-                        frag, s_w = _hip.pack_gemm_weight_presplit(ff.project_out.weight, k_pad=32 * -(-ff.hidden // 32))
-                        pk[name]["pout_ps"] = (frag, 1.0 / (s_w * ops.GATE_SPLIT_SCALE))
                     if m.dim == 192:
                         # GDFN tail in one kernel (fused_tail.hip): project_in with its halves padded to a multiple of 16
                         # channels, written tile-major channel-last; taps / project_out packed for irm_gdfn_tail_f16x3_f32
@@ -267,6 +263,15 @@ class Restormer(nn.Module):
             ws[name] = t
         return t[:numel]
 
+    def _zeros(self, key, numel, device):
+        """A zero-initialised workspace tensor of the current stream, created once per key and device."""
+        ws = self._ws
+        t = ws.get(key)
+        if t is None or t.device != device:
+            t = torch.zeros(numel, dtype=torch.float32, device=device)
+            ws[key] = t
+        return t
+
     def release_workspace(self):
         self._ws_by_stream.clear()
 
@@ -293,7 +298,7 @@ class Restormer(nn.Module):
         split = self._split and N % 4 == 0            # the emulation kernel needs the 16-byte fast path
         s_qkv, s_pin, s_pout = split and "qkv_s" in w, split and "pin_s" in w, split and "pout_s" in w
         s_fold = split and w.get("mfold_split", False)
-        presplit = split and "qkv_ps" in w and ops.can_presplit(C, N) and not os.environ.get("IRM_NO_PRESPLIT")
+        presplit = split and "qkv_ps" in w and ops.can_presplit(C, N)
         if presplit:
             # LayerNorm + fp16 hi/lo split once (statistics in the kernel), then a pure matrix-core GEMM
             xs = self._buf("xsplit", B * C * N, dev)
@@ -305,7 +310,7 @@ class Restormer(nn.Module):
                 ops.ln_stats(x, stats)
             ops.gemm1x1(w["qkv_s" if s_qkv else "qkv"], x, qkv, 3 * C, C, bias=w["qkv_b"], stats=stats, lnw=w["n1w"],
                         lnb=w["n1b"], ln_mode=blk.norm1.mode, split=s_qkv)
-        fuse_dw = "v_dwp" in w and ops.can_fuse_dw(C, W) and not os.environ.get("IRM_NO_FUSE_DW")
+        fuse_dw = "v_dwp" in w and ops.can_fuse_dw(C, W)
         if fuse_dw:
             # q, k only: the depth-wise conv of v happens inside the apply GEMM below
             ops.dwconv3x3(qkv[:, :2 * C], w["qkv_dw"], qkv2[:, :2 * C],
@@ -316,11 +321,7 @@ class Restormer(nn.Module):
         part = self._buf("gram_part", B * heads * nchunk * rec, dev)
         gsum = self._buf("gram_sum", B * heads * rec, dev)
         mfold_n = ops.mfold_numel(C)
-        ws = self._ws
-        mfold = ws.get(("mfold", C, B))
-        if mfold is None or mfold.device != dev:
-            mfold = torch.zeros(B * mfold_n, dtype=torch.float32, device=dev)
-            ws[("mfold", C, B)] = mfold
+        mfold = self._zeros(("mfold", C, B), B * mfold_n, dev)
         # the folded per-image matrix in the order of the kernel that applies it (fp16 hi/lo when emulated)
         ops.mdta_fold(qkv2, part, gsum, w["temp"], w["wout"], mfold, C, heads, split=s_fold,
                       gram_scale=w.get("gram_s") if split else None)
@@ -331,7 +332,7 @@ class Restormer(nn.Module):
             ops.gemm1x1(mfold, qkv2[:, 2 * C:], x, C, C, res=x, bias=w["wout_b"], w_bs=mfold_n,
                         stats_out=stats if fuse else None, split=s_fold)
         # --- feed-forward branch: x += project_out(gelu(dw(h1)) * dw(h2))   (restormer.py:88-93, 148)
-        if (split and "tail" in w and ops.can_gdfn_tail(C, H, W) and not os.environ.get("IRM_NO_GDFN_TAIL")):
+        if split and "tail" in w and ops.can_gdfn_tail(C, H, W):
             # LayerNorm + project_in -> h tile-major channel-last; depth-wise + gate + project_out + residual in ONE kernel
             frag, out_scale, s_x, bp, hp = w["pin_cl"]
             h_cl = self._buf("h_cl", B * 2 * hp * N, dev)
@@ -350,17 +351,7 @@ class Restormer(nn.Module):
             ops.gemm1x1(w["pin_s" if s_pin else "pin"], x, h, 2 * hid, C, bias=w["pin_b"], stats=stats, lnw=w["n2w"],
                         lnb=w["n2b"], ln_mode=blk.norm2.mode, split=s_pin)
         emit = fuse and want_stats
-        if (split and "pout_ps" in w and not emit and ops.can_gate_split(C, hid, W, N) and os.environ.get("IRM_GATE_SPLIT")):
-            # gate -> fp16 hi/lo fragments (the bytes of g), then a K-streamed matrix-core GEMM in place on x.  OPT-IN
-            # (IRM_GATE_SPLIT=1): the GEMM gains (C = 384: 85 vs 126 us, C = 192: 107 vs 116 us in the model) but the
-            # fragment-writing gate kernel loses more (87 vs 65 us, 174 vs 138 us); same-box A/B of the whole step:
-            # 54.37 ms without, 54.65 ms with it at C = 384
-            frag, out_scale = w["pout_ps"]
-            ks = -(-hid // 32)
-            gs = self._buf("gsplit", B * 32 * ks * N, dev)
-            ops.dwconv3x3_gate_split(h, w["ffn_dw"], gs, bias=w["ffn_dw_b"])
-            ops.gemm_presplit_res(frag, gs, x, C, ks, out_scale=out_scale, res=x, bias=w["pout_b"])
-        elif fuse_dw:
+        if fuse_dw:
             ops.dwgemm(w["pout_s" if s_pout else "pout"], w["ffn_dwp"], h, x, C, hid, gate=True, res=x,
                        bias=w["pout_b"], stats_out=stats if emit else None, split=s_pout)
         else:
@@ -382,12 +373,11 @@ class Restormer(nn.Module):
         heads, hid = blk.attn.num_heads, blk.ffn.hidden
         qkv = self._buf("scratch_a", B * 3 * C * N, dev).view(B, 3 * C, H, W)
         # q, k tile-major for the Gram pass (its only reader) where the f16x3 ring pass runs on whole tiles
-        tm = ops.can_qk_tile_major(C, heads, H, W) and not os.environ.get("IRM_NO_QK_TM")
-        fa = "gdfn_fa" in w and not os.environ.get("IRM_NO_APPLY_FUSE")
+        tm = ops.can_qk_tile_major(C, heads, H, W)
+        fa = "gdfn_fa" in w
         assert not (x_tm or y_tm) or (tm and fa), "tile-major x / y: only between the kernels that understand them"
-        v_tm = tm and fa and not os.environ.get("IRM_NO_ACT_TM")
-        gram_in_qkv = (tm and "gram_s" in w and ops.can_qkv_gram(C, heads, H, W) and not os.environ.get("IRM_GRAM_EXACT")
-                       and not os.environ.get("IRM_NO_QKV_GRAM"))
+        v_tm = tm and fa
+        gram_in_qkv = tm and "gram_s" in w and ops.can_qkv_gram(C, heads, H, W)
         _, nchunk, rec = ops.mdta_plan(B, C, heads, N)
         nready = None
         if gram_in_qkv:
@@ -400,18 +390,11 @@ class Restormer(nn.Module):
             ops.qkv_dw_fused(w["qkv_f"], x, qkv, C, 3 * C, ln_mode=blk.norm1.mode, tm=tm, x_tm=x_tm, v_tm=v_tm)
         gsum = self._buf("gram_sum", B * heads * rec, dev)
         mfold_n = ops.mfold_numel(C)
-        ws = self._ws
-        mfold = ws.get(("mfold", C, B))
-        if mfold is None or mfold.device != dev:
-            mfold = torch.zeros(B * mfold_n, dtype=torch.float32, device=dev)
-            ws[("mfold", C, B)] = mfold
+        mfold = self._zeros(("mfold", C, B), B * mfold_n, dev)
         s_fold = w.get("mfold_split", False)
         if fa:
             # x' = x + project_out(attn @ v) is formed in the GDFN kernel's prologue and never written (:131, 147-148)
-            mfrag = ws.get(("mfold_frag", C, B))
-            if mfrag is None or mfrag.device != dev:
-                mfrag = torch.zeros(B * ops.mfold_frag_numel(C), dtype=torch.float32, device=dev)
-                ws[("mfold_frag", C, B)] = mfrag
+            mfrag = self._zeros(("mfold_frag", C, B), B * ops.mfold_frag_numel(C), dev)
             ops.mdta_fold(qkv, part, gsum, w["temp"], w["wout"], mfrag, C, heads, gram_scale=w.get("gram_s"), frag=True, tm=tm,
                           nchunk_ready=nready)
             ops.attn_gdfn_fused(w["gdfn_fa"], x, qkv[:, 2 * C:], mfrag, alt, C, hid, ln_mode=blk.norm2.mode,
@@ -430,14 +413,12 @@ class Restormer(nn.Module):
         blocks = [(f"{n}.{i}", blk) for n in names for i, blk in enumerate(getattr(self, n))]
         B, C, H, W = x.shape
         if (len(blocks) and all("gdfn_f" in pk[k] for k, _ in blocks) and ops.can_fuse_gdfn(C, W) and (H * W) % 4 == 0
-                and len({blk.attn.num_heads for _, blk in blocks}) == 1 and not os.environ.get("IRM_NO_FUSE_BLOCK")):
+                and len({blk.attn.num_heads for _, blk in blocks}) == 1):
             cur, alt = x, self._buf(f"alt_{C}", B * C * H * W, x.device).view(B, C, H, W)
             # between the blocks x travels tile-major channel-last (include/irm_hip.h): the first block reads the planar
             # input, the last one writes the planar output
             heads = blocks[0][1].attn.num_heads
-            act_tm = (all("gdfn_fa" in pk[k] for k, _ in blocks) and ops.can_qk_tile_major(C, heads, H, W)
-                      and not os.environ.get("IRM_NO_APPLY_FUSE") and not os.environ.get("IRM_NO_QK_TM")
-                      and not os.environ.get("IRM_NO_ACT_TM"))
+            act_tm = all("gdfn_fa" in pk[k] for k, _ in blocks) and ops.can_qk_tile_major(C, heads, H, W)
             for i, (k, blk) in enumerate(blocks):
                 out = self._block_fused(blk, pk[k], cur, alt, x_tm=act_tm and i > 0, y_tm=act_tm and i + 1 < len(blocks))
                 cur, alt = out, cur
@@ -495,12 +476,12 @@ class Restormer(nn.Module):
         self._run_stage("latent", pk, lat)
 
         ops.conv3x3(pk["up4_3"], lat, cat3[:, :d3], d4, d4 * 2, store_mode=2)
-        rs3 = "reduce_chan_level3_s" in pk and (H3 * W3) % 4 == 0 and not os.environ.get("IRM_NO_RC_SPLIT")
+        rs3 = "reduce_chan_level3_s" in pk and (H3 * W3) % 4 == 0
         ops.gemm1x1(pk["reduce_chan_level3" + ("_s" if rs3 else "")], cat3, dec3, d3, 2 * d3, bias=pk["reduce_chan_level3_b"],
                     split=rs3)
         self._run_stage("decoder_level3", pk, dec3)
         ops.conv3x3(pk["up3_2"], dec3, cat2[:, :d2], d3, d3 * 2, store_mode=2)
-        rs2 = "reduce_chan_level2_s" in pk and (H2 * W2) % 4 == 0 and not os.environ.get("IRM_NO_RC_SPLIT")
+        rs2 = "reduce_chan_level2_s" in pk and (H2 * W2) % 4 == 0
         ops.gemm1x1(pk["reduce_chan_level2" + ("_s" if rs2 else "")], cat2, dec2, d2, 2 * d2, bias=pk["reduce_chan_level2_b"],
                     split=rs2)
         self._run_stage("decoder_level2", pk, dec2)

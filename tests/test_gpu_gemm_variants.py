@@ -24,7 +24,7 @@ from test_gpu_precision import F, K
 
 SENTINEL = 7.0
 LN_NONE, LN_WB, LN_BF = 0, 1, 2
-CTS = (3, 4, 6, 8, 9)                   # the ct switches of gemm_entry (gemm_pw.hip:670-676, 684-690, 693-699)
+CTS = (3, 4, 6, 8, 9)                   # the ct switches of gemm_entry (gemm_pw.hip:656-662, 669-675, 678-684)
 
 
 # --------------------------------------------------------------------------- the variant table and its dispatch mirror
@@ -37,14 +37,14 @@ def generic(ct, vec):
 
 
 def xres(kt, ct):
-    # xres_launch<KT, CT, NS = 3, NPT = 16, WP = 2>, KT 12: <12, CT, 3, 8, 2> (gemm_xres.hip:230-237, 250-257);
+    # xres_launch<KT, CT, NS = 3, NPT = 16, WP = 2>, KT 12: <12, CT, 3, 8, 2> (gemm_xres.hip:229-236, 248-253);
     # the kernel's own template order is <KT, CT, NS, WP, NPT>
     return f"gemm_xres_kernel<{kt}, {ct}, 3, 2, {8 if kt == 12 else 16}>"
 
 
 def ring_ns(ct, k, f16):
     """Ring depth of a residual launch (PT 2): 3 for ct <= 6 and K <= 512 (the split kernel not at ct 4), else 4
-    (launch_ring, gemm_pw.hip:562-579)."""
+    (launch_ring, gemm_pw.hip:560-577)."""
     return 3 if ct <= 6 and k <= 512 and not (f16 and ct == 4) else 4
 
 
@@ -53,49 +53,49 @@ def _res_depths(ct, f16):
 
 
 VARIANTS = sorted(
-    # exact f32 ring, residual: PT 2, no LN (launch_ring_any, gemm_pw.hip:586-589)
+    # exact f32 ring, residual: PT 2, no LN (launch_ring_any, gemm_pw.hip:584-587)
     [ring(2, ct, ns, LN_NONE, True, False) for ct in CTS for ns in _res_depths(ct, False)]
-    # exact f32 ring, no residual: PT 4 (3-deep ring) or PT 2 (4-deep), any LN (gemm_pw.hip:590-597)
+    # exact f32 ring, no residual: PT 4 (3-deep ring) or PT 2 (4-deep), any LN (gemm_pw.hip:588-595)
     + [ring(pt, ct, 3 if pt == 4 else 4, ln, False, False) for pt in (2, 4) for ct in CTS for ln in (0, 1, 2)]
-    # split ring, residual: PT 2, no LN (launch_ring_split, gemm_pw.hip:603-606)
+    # split ring, residual: PT 2, no LN (launch_ring_split, gemm_pw.hip:601-604)
     + [ring(2, ct, ns, LN_NONE, True, True) for ct in CTS for ns in _res_depths(ct, True)]
-    # split ring, no residual: PT 4 (IRM_GEMM_SPLIT_PT default, gemm_pw.hip:607-615)
+    # split ring, no residual: PT 4 (gemm_pw.hip:605-607)
     + [ring(4, ct, 3, ln, False, True) for ct in CTS for ln in (0, 1, 2)]
-    # generic streaming kernel (gemm_pw.hip:693-700 -> launch_gemm 618-625)
+    # generic streaming kernel (gemm_pw.hip:678-685 -> launch_gemm 610-617)
     + [generic(ct, vec) for ct in CTS for vec in (False, True)]
-    # input-resident split kernel (gemm_xres.hip:248-257)
+    # input-resident split kernel (gemm_xres.hip:246-253)
     + [xres(kt, ct) for kt in (2, 4, 6, 12) for ct in (8, 9)])
 assert len(VARIANTS) == len(set(VARIANTS)) == 78
 
 
 def expected_variant(*, split, M, K, N, B, ct, ygroups, ln, res, stats_out, w_bs, vec):
-    """The instantiation gemm_entry launches (None = IRM_EINVAL), with the experiment switches at their defaults.
-    Mirrors gemm_pw.hip:643-700 and gemm_xres.hip:248-260."""
+    """The instantiation gemm_entry launches (None = IRM_EINVAL).
+    Mirrors gemm_pw.hip:626-686 and gemm_xres.hip:246-257."""
     mt = (M + 15) // 16
-    if stats_out and mt > ct:                                       # gemm_pw.hip:657
+    if stats_out and mt > ct:                                       # gemm_pw.hip:644
         return None
     nchunks = -(-mt // ct)
-    yg = min(max(ygroups, 1), nchunks)                              # gemm_pw.hip:658-660
+    yg = min(max(ygroups, 1), nchunks)                              # gemm_pw.hip:645-647
     if split:
-        if not vec or N < 4 or (res and ln):                        # gemm_pw.hip:664
+        if not vec or N < 4 or (res and ln):                        # gemm_pw.hip:651
             return None
-        if K <= 192 and ln and not stats_out and not res and not w_bs:    # gemm_pw.hip:666
-            st, kt_ct = (K + 15) // 16, 9 if mt % 9 == 0 else 8    # gemm_xres.hip:248
-            if st in (2, 4, 6) or (st == 12 and M >= 512):          # gemm_xres.hip:249-258
+        if K <= 192 and ln and not stats_out and not res and not w_bs:    # gemm_pw.hip:652
+            st, kt_ct = (K + 15) // 16, 9 if mt % 9 == 0 else 8    # gemm_xres.hip:246
+            if st in (2, 4, 6) or (st == 12 and M >= 512):          # gemm_xres.hip:247-256
                 return xres(st, kt_ct)
         if ct not in CTS:
             return None
-        if res:                                                     # gemm_pw.hip:603-606
+        if res:                                                     # gemm_pw.hip:601-604
             return ring(2, ct, ring_ns(ct, K, True), LN_NONE, True, True)
-        return ring(4, ct, 3, ln, False, True)                      # gemm_pw.hip:613-615
+        return ring(4, ct, 3, ln, False, True)                      # gemm_pw.hip:605-607
     if ct not in CTS:
         return None
-    if vec and N >= 4 and not (res and ln):                         # gemm_pw.hip:679
+    if vec and N >= 4 and not (res and ln):                         # gemm_pw.hip:665
         if res:
             return ring(2, ct, ring_ns(ct, K, False), LN_NONE, True, False)
-        pt = 4 if B * -(-N // 256) * yg >= 512 else 2               # gemm_pw.hip:682
+        pt = 4 if B * -(-N // 256) * yg >= 512 else 2               # gemm_pw.hip:668
         return ring(pt, ct, 3 if pt == 4 else 4, ln, False, False)
-    return generic(ct, vec)                                         # gemm_pw.hip:693-700
+    return generic(ct, vec)                                         # gemm_pw.hip:678-685
 
 
 # --------------------------------------------------------------------------- cases
@@ -126,7 +126,7 @@ def _ring_res_cases(ct, ns, f16):
 
 
 def _ring_plain_cases(pt, ct, ln, f16):
-    """No residual.  PT 4 on the exact path needs B * ceil(N / 256) * ygroups >= 512 (gemm_pw.hip:682)."""
+    """No residual.  PT 4 on the exact path needs B * ceil(N / 256) * ygroups >= 512 (gemm_pw.hip:668)."""
     v = ring(pt, ct, 3 if pt == 4 else 4, ln, False, f16)
     # LN on the split path: keep off the input-resident kernel (K 48 = 3 stages, K > 192, stats_out or per-batch weights)
     k_a, k_b = (48, 200) if (f16 and ln) else (37, 90)
@@ -157,7 +157,7 @@ def _ring_plain_cases(pt, ct, ln, f16):
 def _generic_cases(ct, vec):
     v = generic(ct, vec)
     if vec:
-        # the generic kernel's aligned path: a residual together with a LayerNorm prologue (gemm_pw.hip:679)
+        # the generic kernel's aligned path: a residual together with a LayerNorm prologue (gemm_pw.hip:665)
         return [
             _case(v, "m%16=1 res+ln1 yg2", 16 * ct + 1, 37, 12, 20, 2, ct=ct, yg=2, ln=1, res="sep", scale=True,
                   bias=True),

@@ -14,14 +14,14 @@ The cases take every dispatch outcome of restormer.py at least once (fused C = 4
 in the qkv kernel and the tile-major chain between them, C = 192 with presplit + GDFN tail / presplit only / neither,
 C = 384 presplit / split-only / unsplit, the two branches of ops.mdta_plan, both reduce_chan GEMMs, the dual-pixel
 skip_conv, the strictly-f32 IRM_GEMM_EXACT=1 leg), plus the conv nets, both DeblurGANv2 paths and both MaIR models.
-test_entry_point_coverage then asserts that every irm_* entry point ops.py launches was reached by them."""
+test_every_entry_point_is_reached then asserts that every irm_* entry point ops.py launches was reached by them."""
 import os
 import re
 
 import pytest
 import torch
 
-from irm_amd import _hip, deblurganv2, dncnn, mair, rednet, restormer, synth
+from irm_amd import _hip, deblurganv2, dncnn, mair, ops, rednet, restormer, synth
 from oracle import convnets_ref, deblurgan_ref, mair_ref, restormer_ref
 
 pytestmark = pytest.mark.gpu
@@ -29,12 +29,6 @@ pytestmark = pytest.mark.gpu
 #: the bar: e_gpu <= K * e_32 + F * max|y64|
 K = 4.0
 F = 2.0 ** -22
-
-#: entry points of ops.py that no model reaches unless a non-default option is set
-OPT_IN_ONLY = {
-    "irm_dwconv3x3_gate_split_f16": "IRM_GATE_SPLIT=1 only (GDFN gate written as fp16 fragments; slower, off by default)",
-    "irm_gemm_presplit_res_f16x3_f32": "IRM_GATE_SPLIT=1 only (the K-streamed project_out GEMM fed by the pair above)",
-}
 
 NET_G = dict(inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], num_refinement_blocks=4, ssm_ratio=2.0,
              flp_ratio=4.0, mlp_ratio=1.5, bias=False, dual_pixel_task=False, img_size=128, scan_len=4, batch_size=8,
@@ -86,10 +80,10 @@ CASES["restormer_dualpixel_wb_64x64_b1"] = (
 CASES["restormer_wb_128x128_b1_exact"] = (_restormer("WithBias"), (1, 3, 128, 128), (0.0, 1.0),
                                           lambda x, p, tap: restormer_ref.restormer_forward(x, p, tap=tap),
                                           {"IRM_GEMM_EXACT": "1"})
-# an A/B switch: every level on the per-op kernels (dwgemm_f16x3 at C <= 96)
+# every level on the per-op kernels (dwgemm_f16x3 at C <= 96), the path of a dim that is not a multiple of 16:
+# _build patches ops.can_fuse_gdfn to refuse the whole-branch kernels
 CASES["restormer_wb_64x64_b1_unfused"] = (_restormer("WithBias"), (1, 3, 64, 64), (0.0, 1.0),
-                                          lambda x, p, tap: restormer_ref.restormer_forward(x, p, tap=tap),
-                                          {"IRM_NO_FUSE_BLOCK": "1"})
+                                          lambda x, p, tap: restormer_ref.restormer_forward(x, p, tap=tap), {})
 # a checkpoint whose level-1 project_out weights fall under the split guard (_hip.split_is_safe: max|W| < 2^-6): the
 # fused C = 48 blocks keep the folded attention on the exact f32 MFMA and run the plain GDFN kernel (gdfn_fused)
 CASES["restormer_wb_64x64_b1_tiny_project_out"] = (_restormer("WithBias"), (1, 3, 64, 64), (0.0, 1.0),
@@ -192,6 +186,8 @@ def _run_gpu(case, dev, model, tap):
 def _build(case, dev, monkeypatch):
     for k, v in CASES[case][4].items():
         monkeypatch.setenv(k, v)
+    if case.endswith("_unfused"):
+        monkeypatch.setattr(ops, "can_fuse_gdfn", lambda C, W: False)
     model = CASES[case][0]().load_synthetic(42)
     if case.endswith("_tiny_project_out"):
         with torch.no_grad():
@@ -237,8 +233,8 @@ def test_positive_control_one_fp16_layer(dev, monkeypatch):
         assert not passes(e_gpu, e32, float(y64.abs().max())), row
 
 
-def test_entry_point_coverage(request):
-    """Every irm_* entry point ops.py launches was reached by the ledger cases (OPT_IN_ONLY excepted): a new kernel path
+def test_every_entry_point_is_reached(request):
+    """Every irm_* entry point ops.py launches was reached by the ledger cases: a new kernel path
     cannot escape the ledger.  Also prints the ledger table.  Only meaningful when the whole ledger ran."""
     ran = {it.callspec.params["case"] for it in request.session.items
            if it.module is request.module and it.originalname == "test_ledger"}
@@ -250,6 +246,5 @@ def test_entry_point_coverage(request):
         print(f"{name:48s} {e_gpu:10.3e} {e32:10.3e} {e_gpu / e32 if e32 else float('inf'):7.2f}{'' if ok else '  FAIL'}")
     with open(os.path.join(os.path.dirname(os.path.abspath(_hip.__file__)), "ops.py")) as f:
         launched = set(re.findall(r'"(irm_[a-z0-9_]+)"', f.read()))
-    assert set(OPT_IN_ONLY) <= launched, "stale OPT_IN_ONLY entry"
-    missing = sorted(launched - _REACHED - set(OPT_IN_ONLY))
+    missing = sorted(launched - _REACHED)
     assert not missing, f"entry points no ledger case reaches: {missing}"

@@ -50,7 +50,7 @@ def test_gemm_plan_explicit_ct(N, B):
 
 @pytest.mark.parametrize("res", [False, True])
 def test_stats_out_rule(res):
-    """stats_out is planned iff can_fuse_stats(M), and then as the C side needs it (gemm_pw.hip:657): every output tile
+    """stats_out is planned iff can_fuse_stats(M), and then as the C side needs it (gemm_pw.hip:644): every output tile
     in one pass, one group."""
     for M in _ms(1):
         mt = (M + 15) // 16

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Isolated timing of irm_gemm1x1_f32 on the Restormer shapes (HIP events, median of reps).
-Usage: python tools/bench_gemm.py [reps]  (env IRM_GEMM_GENERIC=1 selects the non-ring kernel)"""
+Usage: python tools/bench_gemm.py [reps]"""
 import os
 import sys
 

@@ -1,4 +1,4 @@
-"""Split (fp16x3) vs exact GEMM at the big pin / qkv shapes; IRM_GEMM_DBG bits apply to both (1 no DMA, 2 no stores)."""
+"""Split (fp16x3) vs exact GEMM at the big pin / qkv shapes."""
 import os, sys, torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import irm_amd
