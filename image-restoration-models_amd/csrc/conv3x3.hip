@@ -40,10 +40,12 @@ struct ConvArgs {
     const float* bias;            // [Co] or null
     int Ci, Co, H, W;
     int mtiles, ksteps;           // ceil(Co/16), 2*ceil(Ci/8)
-    int relu1;                    // relu right after bias
+    int relu1;                    // after the bias: 0 none, 1 ReLU, 2 LeakyReLU(slope)
+    float slope;                  // LeakyReLU negative slope (relu1 == 2)
+    int ps_r;                     // PixelShuffle factor of store_mode 2: 2, 3 or 4
     int res_mode;                 // 0 none, 1: v += R, 2: v = R - v, 3: v = clamp(tanh(v) + R, -1, 1)
     int relu2;                    // relu after the residual
-    int store_mode;               // 0 NCHW, 1 PixelUnshuffle(2), 2 PixelShuffle(2)
+    int store_mode;               // 0 NCHW, 1 PixelUnshuffle(2), 2 PixelShuffle(ps_r)
     int tiles_x;
     int vec;                      // 16-byte / 8-byte store fast paths are legal
 };
@@ -181,7 +183,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(ConvArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         v[e] = acc[p][c][e] + bv;
-                        if (a.relu1) v[e] = fmaxf(v[e], 0.0f);
+                        if (a.relu1 == 1) v[e] = fmaxf(v[e], 0.0f);
+                        else if (a.relu1 == 2) v[e] = v[e] > 0.0f ? v[e] : v[e] * a.slope;
                     }
                     if (a.store_mode == 0) {
                         const long off = (long)co * plane + (long)y * a.W + x;
@@ -222,7 +225,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(ConvArgs a) {
                             for (int e = 0; e < 4; ++e)
                                 if (x + e < a.W) Y[(long)(oc + (e & 1)) * op + o + (e >> 1)] = v[e];
                         }
-                    } else {
+                    } else if (a.ps_r == 2) {
                         // PixelShuffle(2): out[co/4][2y + ((co>>1)&1)][2x + (co&1)]
                         const int ow = a.W * 2;
                         const long op = (long)a.H * 2 * ow;
@@ -231,6 +234,15 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(ConvArgs a) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
                             if (x + e < a.W) o[2 * e] = v[e];
+                    } else {
+                        // PixelShuffle(r): out[co/r^2][r y + (co/r)%r][r x + co%r]
+                        const int pr = a.ps_r, ow = a.W * pr;
+                        const long op = (long)a.H * pr * ow;
+                        const int oc = co / (pr * pr), i = (co / pr) % pr, jx = co % pr;
+                        float* o = Y + (long)oc * op + (long)(pr * y + i) * ow + pr * x + jx;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (x + e < a.W) o[pr * e] = v[e];
                     }
                 }
             }
@@ -369,7 +381,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ring_kernel(ConvArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         v[e] = acc[p][c][e] + bv;
-                        if (a.relu1) v[e] = fmaxf(v[e], 0.0f);
+                        if (a.relu1 == 1) v[e] = fmaxf(v[e], 0.0f);
+                        else if (a.relu1 == 2) v[e] = v[e] > 0.0f ? v[e] : v[e] * a.slope;
                     }
                     acc[p][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
                     if (!row_ok || y >= a.H || x >= a.W) continue;
@@ -393,13 +406,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ring_kernel(ConvArgs a) {
                         const long o = (long)(y >> 1) * ow + (x >> 1);
                         *reinterpret_cast<float2*>(Y + (long)oc * op + o) = make_float2(v[0], v[2]);
                         *reinterpret_cast<float2*>(Y + (long)(oc + 1) * op + o) = make_float2(v[1], v[3]);
-                    } else {
+                    } else if (a.ps_r == 2) {
                         const int ow = a.W * 2;
                         const long op = (long)a.H * 2 * ow;
                         const int oc = co >> 2, i = (co >> 1) & 1, jx = co & 1;
                         float* o = Y + (long)oc * op + (long)(2 * y + i) * ow + 2 * x + jx;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[2 * e] = v[e];
+                    } else {
+                        const int pr = a.ps_r, ow = a.W * pr;
+                        const long op = (long)a.H * pr * ow;
+                        const int oc = co / (pr * pr), i = (co / pr) % pr, jx = co % pr;
+                        float* o = Y + (long)oc * op + (long)(pr * y + i) * ow + pr * x + jx;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[pr * e] = v[e];
                     }
                 }
             }
@@ -429,21 +449,23 @@ static int launch_conv(const ConvArgs& a, int B, int ygroups, hipStream_t stream
     return irm_launch_status();
 }
 
-extern "C" int irm_conv3x3_f32(const float* wp, const float* x, long x_bs, float* y, long y_bs, const float* res,
-                               long r_bs, const float* bias, int B, int Ci, int Co, int H, int W, int relu1,
-                               int res_mode, int relu2, int store_mode, int ct, int ygroups,
-                               hipStream_t stream) {
+extern "C" int irm_conv3x3_ep_f32(const float* wp, const float* x, long x_bs, float* y, long y_bs, const float* res,
+                                  long r_bs, const float* bias, int B, int Ci, int Co, int H, int W, int act1, float slope,
+                                  int res_mode, int relu2, int store_mode, int shuffle, int ct, int ygroups,
+                                  hipStream_t stream) {
     if (!wp || !x || !y || B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return IRM_EINVAL;
     if (res_mode < 0 || res_mode > 3 || (res_mode && !res) || store_mode < 0 || store_mode > 2) return IRM_EINVAL;
+    if (act1 < 0 || act1 > 2 || shuffle < 2 || shuffle > 4) return IRM_EINVAL;
     if (store_mode != 0 && res_mode != 0) return IRM_EINVAL;
     if (store_mode == 1 && ((H & 1) || (W & 1))) return IRM_EINVAL;
-    if (store_mode == 2 && (Co & 3)) return IRM_EINVAL;
+    if (store_mode == 2 && (Co % (shuffle * shuffle))) return IRM_EINVAL;
     if (B > 65535) return IRM_EINVAL;
     ConvArgs a;
     a.Wp = wp; a.X = x; a.x_bs = x_bs; a.Y = y; a.y_bs = y_bs; a.R = res; a.r_bs = r_bs; a.bias = bias;
     a.Ci = Ci; a.Co = Co; a.H = H; a.W = W;
     a.mtiles = (Co + 15) / 16; a.ksteps = 2 * ((Ci + 7) / 8);
-    a.relu1 = relu1; a.res_mode = res_mode; a.relu2 = relu2; a.store_mode = store_mode;
+    a.relu1 = act1; a.slope = slope; a.ps_r = shuffle;
+    a.res_mode = res_mode; a.relu2 = relu2; a.store_mode = store_mode;
     a.tiles_x = (W + CV_TW - 1) / CV_TW;
     a.vec = !(W & 3) && !(y_bs & 3) && !(r_bs & 3) && irm_aligned16(y) && irm_aligned16(res);
     if (ct <= 0) return IRM_EINVAL;
@@ -469,4 +491,12 @@ extern "C" int irm_conv3x3_f32(const float* wp, const float* x, long x_bs, float
         case 6: return launch_conv<6>(a, B, ygroups, stream);
         default: return IRM_EINVAL;
     }
+}
+
+extern "C" int irm_conv3x3_f32(const float* wp, const float* x, long x_bs, float* y, long y_bs, const float* res,
+                               long r_bs, const float* bias, int B, int Ci, int Co, int H, int W, int relu1,
+                               int res_mode, int relu2, int store_mode, int ct, int ygroups,
+                               hipStream_t stream) {
+    return irm_conv3x3_ep_f32(wp, x, x_bs, y, y_bs, res, r_bs, bias, B, Ci, Co, H, W, relu1 ? 1 : 0, 0.0f, res_mode,
+                              relu2, store_mode, 2, ct, ygroups, stream);
 }

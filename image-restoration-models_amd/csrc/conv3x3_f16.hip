@@ -45,6 +45,8 @@ struct ConvF16Args {
     int Ci, Co, H, W, mtiles, S;
     int relu1, res_mode, relu2, store_mode, tiles_x;
     float inv_s;                  // 16 / weight scale
+    float slope;                  // relu1: 0 none, 1 ReLU, 2 LeakyReLU(slope)
+    int ps_r;                     // PixelShuffle factor of store_mode 2: 2, 3 or 4
 };
 
 template <int N>
@@ -203,7 +205,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v[e] = fmaf(acc[p][c][e], a.inv_s, bv);
-                    if (a.relu1) v[e] = fmaxf(v[e], 0.0f);
+                    if (a.relu1 == 1) v[e] = fmaxf(v[e], 0.0f);
+                    else if (a.relu1 == 2) v[e] = v[e] > 0.0f ? v[e] : v[e] * a.slope;
                 }
                 if (!row_ok || y >= a.H || x >= a.W) continue;
                 if (a.store_mode == 0) {
@@ -226,13 +229,21 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
                     const long o = (long)(y >> 1) * ow + (x >> 1);
                     *reinterpret_cast<float2*>(Y + (long)oc * op + o) = make_float2(v[0], v[2]);
                     *reinterpret_cast<float2*>(Y + (long)(oc + 1) * op + o) = make_float2(v[1], v[3]);
-                } else {
+                } else if (a.ps_r == 2) {
                     const int ow = a.W * 2;
                     const long op = (long)a.H * 2 * ow;
                     const int oc = co >> 2, i = (co >> 1) & 1, jx = co & 1;
                     float* o = Y + (long)oc * op + (long)(2 * y + i) * ow + 2 * x + jx;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[2 * e] = v[e];
+                } else {
+                    // PixelShuffle(r): out[co/r^2][r y + (co/r)%r][r x + co%r]
+                    const int pr = a.ps_r, ow = a.W * pr;
+                    const long op = (long)a.H * pr * ow;
+                    const int oc = co / (pr * pr), i = (co / pr) % pr, jx = co % pr;
+                    float* o = Y + (long)oc * op + (long)(pr * y + i) * ow + pr * x + jx;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[pr * e] = v[e];
                 }
             }
         }
@@ -250,22 +261,23 @@ static int launch_conv_f16(const ConvF16Args& a, int B, int ygroups, hipStream_t
     return irm_launch_status();
 }
 
-extern "C" int irm_conv3x3_f16x3_f32(const float* wp_split, float inv_scale, const float* x, long x_bs, float* y, long y_bs,
-                                     const float* res, long r_bs, const float* bias, int B, int Ci, int Co, int H, int W,
-                                     int relu1, int res_mode, int relu2, int store_mode, int ct, int ygroups,
-                                     hipStream_t stream) {
+extern "C" int irm_conv3x3_f16x3_ep_f32(const float* wp_split, float inv_scale, const float* x, long x_bs, float* y,
+                                        long y_bs, const float* res, long r_bs, const float* bias, int B, int Ci, int Co,
+                                        int H, int W, int act1, float slope, int res_mode, int relu2, int store_mode,
+                                        int shuffle, int ct, int ygroups, hipStream_t stream) {
     if (!wp_split || !x || !y || B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return IRM_EINVAL;
     if (res_mode < 0 || res_mode > 3 || (res_mode && !res) || store_mode < 0 || store_mode > 2) return IRM_EINVAL;
+    if (act1 < 0 || act1 > 2 || shuffle < 2 || shuffle > 4) return IRM_EINVAL;
     if (store_mode != 0 && res_mode != 0) return IRM_EINVAL;
     if (store_mode == 1 && ((H & 1) || (W & 1))) return IRM_EINVAL;
-    if (store_mode == 2 && (Co & 3)) return IRM_EINVAL;
+    if (store_mode == 2 && (Co % (shuffle * shuffle))) return IRM_EINVAL;
     if (B > 65535 || (W & 3) || (x_bs & 3) || (y_bs & 3) || (r_bs & 3)) return IRM_EINVAL;
     if (!irm_aligned16(x) || !irm_aligned16(y) || !irm_aligned16(res) || !irm_aligned16(wp_split)) return IRM_EINVAL;
     ConvF16Args a;
     a.Wp = wp_split; a.X = x; a.x_bs = x_bs; a.Y = y; a.y_bs = y_bs; a.R = res; a.r_bs = r_bs; a.bias = bias;
     a.Ci = Ci; a.Co = Co; a.H = H; a.W = W; a.mtiles = (Co + 15) / 16; a.S = (Ci + 31) / 32;
-    a.relu1 = relu1; a.res_mode = res_mode; a.relu2 = relu2; a.store_mode = store_mode;
-    a.tiles_x = (W + CF_TW - 1) / CF_TW; a.inv_s = inv_scale;
+    a.relu1 = act1; a.res_mode = res_mode; a.relu2 = relu2; a.store_mode = store_mode;
+    a.tiles_x = (W + CF_TW - 1) / CF_TW; a.inv_s = inv_scale; a.slope = slope; a.ps_r = shuffle;
     const int nchunks = (a.mtiles + ct - 1) / (ct > 0 ? ct : 1);
     if (ygroups <= 0) ygroups = 1;
     if (ygroups > nchunks) ygroups = nchunks;
@@ -278,4 +290,12 @@ extern "C" int irm_conv3x3_f16x3_f32(const float* wp_split, float inv_scale, con
         case 12: return launch_conv_f16<4, 3>(a, B, ygroups, stream);
         default: return IRM_EINVAL;
     }
+}
+
+extern "C" int irm_conv3x3_f16x3_f32(const float* wp_split, float inv_scale, const float* x, long x_bs, float* y, long y_bs,
+                                     const float* res, long r_bs, const float* bias, int B, int Ci, int Co, int H, int W,
+                                     int relu1, int res_mode, int relu2, int store_mode, int ct, int ygroups,
+                                     hipStream_t stream) {
+    return irm_conv3x3_f16x3_ep_f32(wp_split, inv_scale, x, x_bs, y, y_bs, res, r_bs, bias, B, Ci, Co, H, W, relu1 ? 1 : 0,
+                                    0.0f, res_mode, relu2, store_mode, 2, ct, ygroups, stream);
 }

@@ -13,7 +13,8 @@
 // Parallelism over L: chunked scan.  Phase A scans every chunk from h = 0 and records its end state and
 // the chunk's total dt; phase B (tiny) carries the state across chunks, h_in[c+1] = exp(A*sum_dt[c]) h_in[c]
 // + h_end[c]; phase C rescans every chunk from its true initial state and emits y.  A work unit is one
-// wave: (batch, direction, 64-channel block, chunk); it keeps h[N], A[N] and the dt weights in registers.
+// wave: (batch, direction, 64-channel block, chunk); it keeps h[N], A[N] and the dt weights in registers.  The MaIR
+// pairs with D % 64 != 0 use scan_chunk_flat_kernel instead: lanes over (direction, channel), see there.
 #include "irm_common.h"
 
 // ---------------------------------------------------------------------------
@@ -87,14 +88,17 @@ typedef float sc_v4 __attribute__((ext_vector_type(4)));
 // directly - no v_readlane, no SGPR budget.  States go in pairs: per pair 2 exp2 + 4 packed operations
 // (v_pk_mul_f32 / v_pk_fma_f32).  Pixel ids travel as one vector load per batch (lane i = step i), three
 // batches ahead; u one load per step, two batches ahead.
+// N = 1 (lightweight-SR MaIR, d_state 1) has no pair: one exp2, h = fma(e, h, du B), y = fma(h, C, D u) per step.
+// dt_rank R is a template argument on its own: MaIRUNet has R = 3N/4, MaIR ceil(embed_dim / 16) (4 at embed 60).
 template <int N, int R, bool EMIT>
 __global__ __launch_bounds__(64, (N <= 8 ? 4 : N == 16 ? 3 : 2)) void scan_chunk_kernel(ScanArgs a) {
     IRM_KERNEL_ENTRY();   // (waves per SIMD: caps the
     constexpr int J = R + 2 * N, JV = (J + 63) / 64;                                                    // scheduler's read hoisting)
     constexpr int TU = 8;                                     // time steps per batch
     constexpr int RP = (R + 3) & ~3;                          // LDS row: [dt_raw, padded to 16 bytes | B | C]
-    constexpr int JS = RP + 2 * N;
-    static_assert(N % 4 == 0, "states are read four at a time");
+    constexpr int JS = (RP + 2 * N + 3) & ~3;                // rows stay 16-byte aligned (N = 1: [dt | B C pad])
+    constexpr int NP = N == 1 ? 1 : N / 2;                    // state registers (pairs; one scalar at N = 1)
+    static_assert(N == 1 || N % 4 == 0, "states are read four at a time");
     __shared__ __attribute__((aligned(16))) float ring[2][TU][JS];
     const int lane = threadIdx.x;
     const int c = blockIdx.x, kdb = blockIdx.y, b = blockIdx.z;
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(64, (N <= 8 ? 4 : N == 16 ? 3 : 2)) void scan_chunk
     const bool on = d < a.D;
     const int dc = on ? d : a.D - 1;                          // idle lanes shadow a valid channel
 
-    sc_v2 Ac[N / 2], h[N / 2];
+    sc_v2 Ac[NP], h[NP];
     float wdt[R];
 #pragma unroll
     for (int n = 0; n < N; ++n) Ac[n / 2][n % 2] = a.A[((long)k * a.D + dc) * N + n] * 1.44269504088896341f;   // exp(x) = exp2(x log2 e)
@@ -177,8 +181,13 @@ __global__ __launch_bounds__(64, (N <= 8 ? 4 : N == 16 ? 3 : 2)) void scan_chunk
             dt = irm_softplus(dt) * (live ? 1.0f : 0.0f);
             const float du = dt * u0[i];
             sc_v2 y2 = {dsk * u0[i], 0.f};
+            if constexpr (N == 1) {
+                const float e = __builtin_amdgcn_exp2f(dt * Ac[0].x);
+                h[0].x = fmaf(e, h[0].x, du * row[RP]);
+                if (EMIT) y2.x = fmaf(h[0].x, row[RP + 1], y2.x);
+            }
 #pragma unroll
-            for (int n = 0; n < N; n += 4) {
+            for (int n = 0; n < (N == 1 ? 0 : N); n += 4) {
                 const sc_v4 Bq = *reinterpret_cast<const sc_v4*>(row + RP + n);
                 const sc_v4 Cq = *reinterpret_cast<const sc_v4*>(row + RP + N + n);
 #pragma unroll
@@ -311,6 +320,111 @@ static int scan_launch(const ScanArgs& a, int B, hipStream_t stream) {
     return irm_launch_status();
 }
 
+// Phases A / C for d_inner not a multiple of 64 (MaIR: 66, 90): the lanes run over the flat (direction, channel) index
+// f = k D + d, so the 4 D recurrences fill ceil(4 D / 64) waves (264 / 320 lanes at D = 66, 360 / 384 at D = 90)
+// instead of 4 ceil(D / 64) half-empty ones.  A wave may straddle two directions, so the per-step row [dt_raw | B | C]
+// and the pixel id are per lane (at most two distinct addresses per wave, L1 broadcasts) instead of the wave-uniform LDS
+// ring of scan_chunk_kernel; they are prefetched one batch of TU steps ahead in registers.  State, sum-of-dt and
+// sum-of-y slots keep scan_chunk_kernel's (direction, 64-channel block, lane) layout, so the carry and combine kernels
+// are shared; the padding slots of the last channel block are not written (nothing reads them into a result).
+template <int N, int R, bool EMIT>
+__global__ __launch_bounds__(64) void scan_chunk_flat_kernel(ScanArgs a) {
+    IRM_KERNEL_ENTRY();
+    constexpr int J = R + 2 * N;
+    constexpr int TU = N == 1 ? 8 : 2;                        // steps per prefetched batch (2 J TU row registers)
+    const int lane = threadIdx.x, c = blockIdx.x, b = blockIdx.z;
+    const int f = blockIdx.y * 64 + lane;
+    const bool on = f < 4 * a.D;
+    const int fc = on ? f : 4 * a.D - 1;                      // idle lanes shadow a valid (direction, channel)
+    const int k = fc / a.D, d = fc - k * a.D;
+    const int db = d >> 6, dl = d & 63;
+    float Ac[N], h[N], wdt[R];
+#pragma unroll
+    for (int n = 0; n < N; ++n) Ac[n] = a.A[((long)k * a.D + d) * N + n] * 1.44269504088896341f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) wdt[r] = a.dtw[((long)k * a.D + d) * R + r];
+    const float bias = a.dtb[k * a.D + d];
+    const float dsk = a.Dskip[k * a.D + d];
+    const long unit = (((long)b * 4 + k) * a.DB + db) * a.nchunk + c;
+    float* st = a.state + (EMIT ? a.state_half : 0) + unit * N * 64 + dl;
+#pragma unroll
+    for (int n = 0; n < N; ++n) h[n] = EMIT ? st[n * 64] : 0.0f;
+    const int* ids = a.ids + (long)k * a.L;
+    const float* xT = a.xT + (long)b * a.L * a.D + d;
+    const float* pT = a.pT + (long)b * a.L * 4 * J + k * J;
+    float* yT = EMIT ? a.yT + ((long)b * 4 + k) * a.L * a.D + d : nullptr;
+    const int t0 = c * a.chunk, t1 = min(t0 + a.chunk, a.L);
+    float sum_dt = 0.0f, sum_y = 0.0f;
+
+    int pc[TU], pn[TU];
+    float uc[TU], un[TU], rc[TU][J], rn[TU][J];
+    auto load_ids = [&](int (&pp)[TU], int t) {
+#pragma unroll
+        for (int i = 0; i < TU; ++i) pp[i] = ids[min(t + i, a.L - 1)];
+    };
+    auto load_rows = [&](float (&u)[TU], float (&rw)[TU][J], const int (&pp)[TU]) {
+#pragma unroll
+        for (int i = 0; i < TU; ++i) {
+            u[i] = xT[(long)pp[i] * a.D];
+#pragma unroll
+            for (int j = 0; j < J; ++j) rw[i][j] = pT[(long)pp[i] * (4 * J) + j];
+        }
+    };
+    load_ids(pc, t0);
+    load_rows(uc, rc, pc);
+    load_ids(pn, t0 + TU);
+    for (int t = t0; t < t1; t += TU) {
+        load_rows(un, rn, pn);                                // batch t + TU, consumed next iteration
+        int pf[TU];
+        load_ids(pf, t + 2 * TU);
+#pragma unroll
+        for (int i = 0; i < TU; ++i) {
+            const bool live = t + i < t1;                     // past the chunk end: dt = 0, the state is untouched
+            float dt = bias;
+#pragma unroll
+            for (int r = 0; r < R; ++r) dt = fmaf(wdt[r], rc[i][r], dt);
+            dt = irm_softplus(dt) * (live ? 1.0f : 0.0f);
+            const float du = dt * uc[i];
+            float y = dsk * uc[i];
+#pragma unroll
+            for (int n = 0; n < N; ++n) {
+                const float e = __builtin_amdgcn_exp2f(dt * Ac[n]);
+                h[n] = fmaf(e, h[n], du * rc[i][R + n]);
+                if (EMIT) y = fmaf(h[n], rc[i][R + N + n], y);
+            }
+            sum_dt += dt;
+            if (EMIT) {
+                y = live ? y : 0.0f;
+                if (on && live) yT[(long)pc[i] * a.D] = y;
+                sum_y += y;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < TU; ++i) {
+            pc[i] = pn[i]; pn[i] = pf[i]; uc[i] = un[i];
+#pragma unroll
+            for (int j = 0; j < J; ++j) rc[i][j] = rn[i][j];
+        }
+    }
+    if (!on) return;
+    if (EMIT) {
+        a.ysum[unit * 64 + dl] = sum_y;
+    } else {
+#pragma unroll
+        for (int n = 0; n < N; ++n) st[n * 64] = h[n];
+        a.sdt[unit * 64 + dl] = sum_dt;
+    }
+}
+
+template <int N, int R>
+static int scan_launch_flat(const ScanArgs& a, int B, hipStream_t stream) {
+    dim3 g1(a.nchunk, (4 * a.D + 63) / 64, B), g2(4 * a.DB, B, N < 8 ? 1 : N / 8);
+    hipLaunchKernelGGL((scan_chunk_flat_kernel<N, R, false>), g1, dim3(64), 0, stream, a);
+    hipLaunchKernelGGL((scan_carry_kernel<N>), g2, dim3(1024), 0, stream, a);
+    hipLaunchKernelGGL((scan_chunk_flat_kernel<N, R, true>), g1, dim3(64), 0, stream, a);
+    return irm_launch_status();
+}
+
 extern "C" int irm_selective_scan_f32(const float* xT, const float* pT, const int* ids, const float* dtw,
                                       const float* dtb, const float* A, const float* Dskip, float* yT,
                                       float* state, float* sdt, float* ysum, int B, int L, int D, int N, int R,
@@ -325,6 +439,11 @@ extern "C" int irm_selective_scan_f32(const float* xT, const float* pT, const in
     if (N == 8 && R == 6) return scan_launch<8, 6>(a, B, stream);
     if (N == 16 && R == 12) return scan_launch<16, 12>(a, B, stream);
     if (N == 32 && R == 24) return scan_launch<32, 24>(a, B, stream);
+    // MaIR at embed 60: lightweight SR (d_state 1) and the class default (d_state 16); lanes over (direction, channel)
+    // unless D fills whole 64-channel blocks
+    const bool flat = (D & 63) != 0;
+    if (N == 1 && R == 4) return flat ? scan_launch_flat<1, 4>(a, B, stream) : scan_launch<1, 4>(a, B, stream);
+    if (N == 16 && R == 4) return flat ? scan_launch_flat<16, 4>(a, B, stream) : scan_launch<16, 4>(a, B, stream);
     return IRM_EINVAL;                                  // (d_state, dt_rank) pairs of MaIRUNet / MaIR
 }
 

@@ -73,6 +73,7 @@ struct BlendArgs {
     int H, W, Co, Cp, th, tw, ph, pw, ps, T;
     int is_u16;
     float post_scale, post_shift;   // postprocess v*scale+shift (DeblurGANv2 (x+1)/2); 1,0 = off
+    int scale;                      // SCALED: super-resolution factor s, origins are in input pixels (x s)
 };
 
 // One workgroup blends BLEND_PER_WG consecutive output elements (256 threads x 8 rounds) and adds its squared error
@@ -80,6 +81,8 @@ struct BlendArgs {
 // per wave (43 200 same-address atomics serialised at the L2: 0.5 ms of a 57 ms frame).  Integer sums: order independent.
 #define BLEND_PER_WG 2048
 
+// SCALED (irm_window_blend_scaled): every extent above is already at output scale; only the origins are scaled here.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void blend_kernel(BlendArgs a) {
     IRM_KERNEL_ENTRY();
     const long total = (long)a.H * a.W * a.Co;
@@ -95,7 +98,9 @@ __global__ __launch_bounds__(256) void blend_kernel(BlendArgs a) {
         const int x = (int)(t % a.W), y = (int)(t / a.W);
         float acc = 0.0f, wsum = 0.0f;
         for (int i = 0; i < a.T; ++i) {            // same order as the h_idx / w_idx loops
-            const int ly = y - a.origins[2 * i], lx = x - a.origins[2 * i + 1];
+            const int oy = SCALED ? a.origins[2 * i] * a.scale : a.origins[2 * i];
+            const int ox = SCALED ? a.origins[2 * i + 1] * a.scale : a.origins[2 * i + 1];
+            const int ly = y - oy, lx = x - ox;
             if (ly < 0 || ly >= a.th || lx < 0 || lx >= a.tw) continue;
             float p = a.pred[(((long)i * a.Cp + c) * a.ph + ly) * a.pw + lx];
             if (albu) p = __fmul_rn(__fadd_rn(p, a.post_shift), a.post_scale);
@@ -136,8 +141,26 @@ extern "C" int irm_window_blend(const float* pred, const int* origins, const flo
     if (!pred || !origins || !window || !out || H <= 0 || W <= 0 || Co <= 0 || Cp < Co || T <= 0) return IRM_EINVAL;
     if (th <= 0 || tw <= 0 || ph < th || pw < tw || th > ps || tw > ps) return IRM_EINVAL;
     BlendArgs a{pred, origins, window, out, target, sse, H, W, Co, Cp, th, tw, ph, pw, ps, T, is_u16,
-                post_scale, post_shift};
+                post_scale, post_shift, 1};
     const long total = (long)H * W * Co;
-    hipLaunchKernelGGL(blend_kernel, dim3((unsigned)((total + BLEND_PER_WG - 1) / BLEND_PER_WG)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(blend_kernel<false>, dim3((unsigned)((total + BLEND_PER_WG - 1) / BLEND_PER_WG)), dim3(256), 0, stream, a);
+    return irm_launch_status();
+}
+
+// Super-resolution blend: geometry in input pixels, predictions / window / output at scale s (see irm_hip.h).
+extern "C" int irm_window_blend_scaled(const float* pred, const int* origins, const float* window, void* out,
+                                       int is_u16, const void* target, unsigned long long* sse, int H, int W, int Co,
+                                       int Cp, int th, int tw, int ph, int pw, int ps, int T, int scale,
+                                       float post_scale, float post_shift, hipStream_t stream) {
+    if (!pred || !origins || !window || !out || H <= 0 || W <= 0 || Co <= 0 || Cp < Co || T <= 0) return IRM_EINVAL;
+    if (th <= 0 || tw <= 0 || ph < th || pw < tw || th > ps || tw > ps || scale < 1 || scale > 8) return IRM_EINVAL;
+    // int indices inside the kernel: output rows / columns and the window index (s ps)^2 stay below 2^31
+    if ((long)H * scale > (1L << 20) || (long)W * scale > (1L << 20) || (long)ps * scale * ps * scale >= (1L << 31))
+        return IRM_EINVAL;
+    const int s = scale;
+    BlendArgs a{pred, origins, window, out, target, sse, s * H, s * W, Co, Cp, s * th, s * tw, s * ph, s * pw, s * ps, T,
+                is_u16, post_scale, post_shift, s};
+    const long total = (long)a.H * a.W * Co;
+    hipLaunchKernelGGL(blend_kernel<true>, dim3((unsigned)((total + BLEND_PER_WG - 1) / BLEND_PER_WG)), dim3(256), 0, stream, a);
     return irm_launch_status();
 }

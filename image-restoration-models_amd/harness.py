@@ -1,7 +1,8 @@
 """Benchmark-harness aggregate of the reference (scripts/tests.py:389-424): per image PSNR, SSIM and
 inference time, per (dataset, model) their mean and standard deviation, one CSV row per combination with
 the reference's column names.  Dataset file IO is out of scope - `loader` is any iterable yielding
-(input_uint8_hwc, target_uint8_hwc, name), e.g. `synthetic_loader`."""
+(input_uint8_hwc, target_uint8_hwc, name), e.g. `synthetic_loader`.  For a super-resolving model (`model.upscale`
+s > 1) the pairs are (low-resolution input, s x larger target)."""
 from __future__ import annotations
 
 import csv

@@ -192,7 +192,7 @@ class MambaHost(nn.Module):
         xT = self._buf("xT", B * L * D, dev).view(B, L, D)
         pT = self._buf("pT", B * L * 4 * J, dev).view(B, L, 4 * J)
         yT = self._buf("yT", B * 4 * L * D, dev)
-        chunk, nchunk, DB = ops.scan_plan(B, L, D)
+        chunk, nchunk, DB = ops.scan_plan(B, L, D, flat=ops.scan_is_flat(D, N, R))
         state = self._buf("scan_state", 2 * B * 4 * DB * nchunk * N * 64, dev)
         sdt = self._buf("scan_sdt", B * 4 * DB * nchunk * 64, dev)
         ysum = self._buf("scan_ysum", B * 4 * DB * nchunk * 64, dev)

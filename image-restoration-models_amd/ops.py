@@ -496,17 +496,22 @@ def plan_conv3x3(co: int, H: int, W: int, B: int, *, split: bool, ct: int | None
 
 
 def conv3x3(wp, x, y, ci: int, co: int, *, bias=None, relu1=False, res=None, res_mode=0, relu2=False,
-            store_mode=0, ct: int | None = None, ygroups: int | None = None):
-    """Dense 3x3 conv with fused epilogue; store_mode 1 = PixelUnshuffle(2), 2 = PixelShuffle(2).
-    wp: _hip.pack_conv3x3_weight(w) (exact f32 MFMA) or the pair _hip.pack_conv3x3_weight_split(w) (fp32 emulated on
-    the fp16 matrix cores, irm_conv3x3_f16x3_f32; needs W % 4 == 0 and 16-byte aligned rows)."""
+            store_mode=0, ct: int | None = None, ygroups: int | None = None, leaky: float | None = None, shuffle: int = 2):
+    """Dense 3x3 conv with fused epilogue; store_mode 1 = PixelUnshuffle(2), 2 = PixelShuffle(shuffle), shuffle in
+    {2, 3, 4}; leaky: LeakyReLU slope right after the bias, instead of relu1 (the SR reconstruction heads).
+    wp: _hip.pack_conv3x3_weight(w) (exact f32 MFMA, irm_conv3x3_ep_f32) or the pair _hip.pack_conv3x3_weight_split(w)
+    (fp32 emulated on the fp16 matrix cores, irm_conv3x3_f16x3_ep_f32; needs W % 4 == 0 and 16-byte aligned rows)."""
     _chk(x, "x"), _chk(y, "y")
     B, _, H, W = x.shape
     nbytes = 4.0 * B * H * W * (ci + co + (co if res is not None else 0))
+    if leaky is not None and relu1:
+        raise ValueError("conv3x3: relu1 and leaky are exclusive")
+    act1, slope = (2, float(leaky)) if leaky is not None else (int(bool(relu1)), 0.0)
+    extra = (f" ps{shuffle}" if shuffle != 2 else "") + (f" leaky{slope:g}" if leaky is not None else "")
     if isinstance(wp, _hip.ConvWeight):
         aligned = (W % 4 == 0 and _bs(x) % 4 == 0 and _bs(y) % 4 == 0 and _bs(res) % 4 == 0 and x.data_ptr() % 16 == 0
                    and y.data_ptr() % 16 == 0 and (res is None or res.data_ptr() % 16 == 0))
-        if wp.raw is not None and aligned and store_mode == 0:
+        if wp.raw is not None and aligned and store_mode == 0 and act1 < 2:
             _launch("conv3x3_thin", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_thin_f32", _hip.ptr(wp.raw), _hip.ptr(x),
                     _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, int(relu1),
                     int(res_mode), int(relu2), tag=f"ci{ci} co{co} {H}x{W} B{B}")
@@ -515,15 +520,16 @@ def conv3x3(wp, x, y, ci: int, co: int, *, bias=None, relu1=False, res=None, res
     if isinstance(wp, tuple):
         wps, inv_scale = wp
         ct, ygroups = plan_conv3x3(co, H, W, B, split=True, ct=ct, ygroups=ygroups)
-        _launch("conv3x3_f16x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_f16x3_f32", _hip.ptr(wps), float(inv_scale),
-                _hip.ptr(x), _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W,
-                int(relu1), int(res_mode), int(relu2), int(store_mode), ct, ygroups,
-                tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}")
+        _launch("conv3x3_f16x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_f16x3_ep_f32", _hip.ptr(wps),
+                float(inv_scale), _hip.ptr(x), _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci,
+                co, H, W, act1, slope, int(res_mode), int(relu2), int(store_mode), int(shuffle), ct, ygroups,
+                tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}{extra}")
         return
     ct, ygroups = plan_conv3x3(co, H, W, B, split=False, ct=ct, ygroups=ygroups)
-    _launch("conv3x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_f32", _hip.ptr(wp), _hip.ptr(x), _bs(x),
-            _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, int(relu1), int(res_mode),
-            int(relu2), int(store_mode), ct, ygroups, tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}")
+    _launch("conv3x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_ep_f32", _hip.ptr(wp), _hip.ptr(x), _bs(x),
+            _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, act1, slope, int(res_mode),
+            int(relu2), int(store_mode), int(shuffle), ct, ygroups,
+            tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}{extra}")
 
 
 # --------------------------------------------------------------------------- MaIR / LoSh2D
@@ -534,12 +540,20 @@ def transpose(src: torch.Tensor, dst: torch.Tensor, R: int, C: int):
             dst.stride(0), B, R, C, tag=f"R{R} C{C} B{B}")
 
 
-def scan_plan(B: int, L: int, D: int):
+def scan_is_flat(D: int, N: int, R: int) -> bool:
+    """irm_selective_scan_f32 runs its lanes over (direction, channel) - ceil(4 D / 64) waves per chunk instead of
+    4 ceil(D / 64) - for the MaIR pairs (N, R) = (1, 4), (16, 4) when D is not a multiple of 64 (include/irm_hip.h)."""
+    return (N, R) in ((1, 4), (16, 4)) and D % 64 != 0
+
+
+def scan_plan(B: int, L: int, D: int, flat: bool = False):
     """(chunk, nchunk, DB): time steps per wave.  A wave is one sequential recurrence; measured on the five MaIRUNet
     shapes of a 256x256 image (tools/bench_scan.py) the scan is fastest with ~3 waves per SIMD (3k waves: all
-    resident at once, none queued behind a full SIMD) and chunks of at least 32 steps (whole batches of 8)."""
+    resident at once, none queued behind a full SIMD) and chunks of at least 32 steps (whole batches of 8).
+    flat (scan_is_flat): a chunk takes ceil(4 D / 64) waves, so the same wave budget buys shorter chunks."""
     DB = (D + 63) // 64
-    nchunk = max(1, min(-(-L // 32), -(-3072 // (B * 4 * DB))))
+    waves = -(-4 * D // 64) if flat else 4 * DB
+    nchunk = max(1, min(-(-L // 32), -(-3072 // (B * waves))))
     chunk = max(32, -(-(-(-L // nchunk)) // 8) * 8)
     return chunk, -(-L // chunk), DB
 

@@ -386,6 +386,9 @@ def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_
         norm_mean = float(np.float32(0.5) * np.float32(255.0))
         norm_inv_std = float(np.float32(1.0) / (np.float32(0.5) * np.float32(255.0)))
         post_scale, post_shift, pad_mode = 0.5, 1.0, "zero32"
+    s = int(getattr(model, "upscale", 1) or 1)             # super-resolving model: outputs s x the tile
+    if s > 1 and noise_sigma is not None:
+        raise ValueError("need_degradation with a super-resolution model: the reference defines no SR degradation")
     img0 = imgs_dev[0]
     h, w, c = img0.shape
     if any(tuple(im.shape) != (h, w, c) or im.dtype != img0.dtype for im in imgs_dev):
@@ -459,17 +462,26 @@ def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_
                 pred = o if o.shape[0] == NT else torch.empty(NT, *o.shape[1:], dtype=torch.float32, device=dev)
             if pred is not o:
                 pred[i:i + o.shape[0]] = o
+    if s > 1 and tuple(pred.shape[2:]) != (s * ph, s * pw):
+        raise ValueError(f"model.upscale = {s}: expected {s * ph}x{s * pw} predictions for {ph}x{pw} tiles, "
+                         f"got {tuple(pred.shape[2:])}")
     if keep_tiles is not None:
-        keep_tiles.append(pred[:, :c_out, :th, :tw].clone())
+        keep_tiles.append(pred[:, :c_out, :s * th, :s * tw].clone())
     results = []
     for k in range(K):
-        out = torch.empty(h, w, c_out, dtype=img0.dtype, device=dev)
+        out = torch.empty(s * h, s * w, c_out, dtype=img0.dtype, device=dev)
         sse, tgt = None, None
         if targets_dev is not None and targets_dev[k] is not None:
             sse, tgt = torch.zeros(1, dtype=torch.int64, device=dev), targets_dev[k]
-        _hip.call("irm_window_blend", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, ps)), _hip.ptr(out),
-                  int(is_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw,
-                  pred.shape[2], pred.shape[3], ps, T, post_scale, post_shift)
+        if s > 1:
+            # tiles cut at input scale, blended at output scale: origins x s, window of s * ps (irm_hip.h)
+            _hip.call("irm_window_blend_scaled", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, s * ps)),
+                      _hip.ptr(out), int(is_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw, ph, pw,
+                      ps, T, s, post_scale, post_shift)
+        else:
+            _hip.call("irm_window_blend", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, ps)), _hip.ptr(out),
+                      int(is_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw,
+                      pred.shape[2], pred.shape[3], ps, T, post_scale, post_shift)
         results.append((out, sse))
     return results
 
@@ -496,6 +508,8 @@ def _run_model_inference(model, input_img, device, normalize=normalize, patch_si
     run_model_inference's, input upload through output download."""
     start_time = time.time()
     out = None
+    if need_degradation and int(getattr(model, "upscale", 1) or 1) > 1:
+        raise ValueError("need_degradation with a super-resolution model: the reference defines no SR degradation")
     dg = (normalize is deblurganv2.normalize and pad is deblurganv2.pad and postprocess is deblurganv2.postprocess
           and input_img.dtype == np.uint8)
     stock = dg or (normalize is globals()['normalize'] and (pad is None or pad is globals()['pad'])
@@ -529,9 +543,10 @@ def _run_tiles_on_host(model, input_img, device, normalize_fn, patch_size, patch
     else:
         ps, ys, xs = max(h, w), [0], [0]
     c_out = min(3, img.shape[2])
-    acc = np.zeros((h, w, c_out), np.float32)
-    wsum = np.zeros((h, w, c_out), np.float32)
-    win = get_gaussian_weights(ps, ps, c_out)
+    s = int(getattr(model, "upscale", 1) or 1)        # super resolution: blend at output scale
+    acc = np.zeros((s * h, s * w, c_out), np.float32)
+    wsum = np.zeros((s * h, s * w, c_out), np.float32)
+    win = get_gaussian_weights(s * ps, s * ps, c_out)
     for y0 in ys:
         for x0 in xs:
             tile = img[y0:y0 + ps, x0:x0 + ps, :].copy()
@@ -540,15 +555,15 @@ def _run_tiles_on_host(model, input_img, device, normalize_fn, patch_size, patch
             t = torch.from_numpy(tile.transpose(2, 0, 1)).unsqueeze(0).to(device)
             if pad_fn is not None:
                 hp, wp = t.shape[-2:]
-                o = model(pad_fn(t))[:, :, :hp, :wp]
+                o = model(pad_fn(t))[:, :, :s * hp, :s * wp]
             else:
                 o = model(t)
             if postprocess is not None:
                 o = postprocess(o)
             p = o.squeeze(0).cpu().numpy().transpose(1, 2, 0)
             ch, cw = p.shape[:2]
-            acc[y0:y0 + ch, x0:x0 + cw, :] += p * win[:ch, :cw]
-            wsum[y0:y0 + ch, x0:x0 + cw, :] += win[:ch, :cw]
+            acc[s * y0:s * y0 + ch, s * x0:s * x0 + cw, :] += p * win[:ch, :cw]
+            wsum[s * y0:s * y0 + ch, s * x0:s * x0 + cw, :] += win[:ch, :cw]
     acc /= np.maximum(wsum, 1e-8)
     if input_img.dtype == np.uint16:
         return np.clip(acc * 65535.0, 0, 65535).round().astype(np.uint16)

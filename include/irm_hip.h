@@ -329,6 +329,19 @@ int irm_conv3x3_f16x3_f32(const float* wp_split, float inv_scale, const float* x
                           const float* res, long r_bs, const float* bias, int B, int Ci, int Co, int H, int W, int relu1,
                           int res_mode, int relu2, int store_mode, int ct, int ygroups, irm_stream_t stream);
 
+/* irm_conv3x3_f32 / irm_conv3x3_f16x3_f32 with the epilogue of an SR reconstruction head (mair_arch.py:620-629,
+ * 940-969): act1 after the bias is 0 none, 1 ReLU, 2 LeakyReLU(slope) (`x > 0 ? x : x * slope`); store_mode 2 is
+ * PixelShuffle(shuffle), shuffle in {2, 3, 4}, Co % shuffle^2 == 0: out[co / r^2][r y + (co / r) % r][r x + co % r]
+ * (y: [B][Co / r^2][r H][r W], batch stride y_bs).  Everything else as the two kernels above; irm_conv3x3_f32 is
+ * irm_conv3x3_ep_f32 with act1 = relu1 ? 1 : 0 and shuffle = 2. */
+int irm_conv3x3_ep_f32(const float* wp, const float* x, long x_bs, float* y, long y_bs, const float* res, long r_bs,
+                       const float* bias, int B, int Ci, int Co, int H, int W, int act1, float slope, int res_mode,
+                       int relu2, int store_mode, int shuffle, int ct, int ygroups, irm_stream_t stream);
+int irm_conv3x3_f16x3_ep_f32(const float* wp_split, float inv_scale, const float* x, long x_bs, float* y, long y_bs,
+                             const float* res, long r_bs, const float* bias, int B, int Ci, int Co, int H, int W,
+                             int act1, float slope, int res_mode, int relu2, int store_mode, int shuffle, int ct,
+                             int ygroups, irm_stream_t stream);
+
 /* Tile extraction for the tiled-patch loop (src/utils.py:379-417):
  * img [H][W][C] uint8 (is_u16=0) or uint16 -> tiles [T][C][ph][pw] float32 =
  * img/255 (or /65535), + optional float64 noise field [th][tw][C] then clip
@@ -351,6 +364,15 @@ int irm_tile_extract(const void* img, int is_u16, const int* origins, const doub
 int irm_window_blend(const float* pred, const int* origins, const float* window, void* out, int is_u16,
                      const void* target, unsigned long long* sse, int H, int W, int Co, int Cp, int th, int tw,
                      int ph, int pw, int ps, int T, float post_scale, float post_shift, irm_stream_t stream);
+
+/* irm_window_blend for a super-resolving model (factor scale in 1..8): H, W, th, tw, ph, pw, ps and the origins are in
+ * INPUT pixels; pred is [T][Cp][scale ph][scale pw] (only [:Co][:scale th][:scale tw] is read), window
+ * [scale ps][scale ps] (get_gaussian_weights(scale ps, scale ps)), out / target [scale H][scale W][Co]; tile i covers
+ * output rows scale * origins[i][0] .. + scale th.  Same float32 operation order and requantisation. */
+int irm_window_blend_scaled(const float* pred, const int* origins, const float* window, void* out, int is_u16,
+                            const void* target, unsigned long long* sse, int H, int W, int Co, int Cp, int th, int tw,
+                            int ph, int pw, int ps, int T, int scale, float post_scale, float post_shift,
+                            irm_stream_t stream);
 
 /* Per-frame PSNR / SSIM inputs of the benchmark loop (src/utils.py:134-156, calculate_metrics: PSNR and
  * skimage structural_similarity with its defaults) for K frames of one shape: pred and target
@@ -405,7 +427,10 @@ int irm_transpose_f32(const float* in, long in_bs, float* out, long out_bs, int 
  * xT [B][L][D], pT [B][L][4J] channel-last; ids [4][L] int32 (device); A = -exp(A_logs).
  * Chunked over L (chunk steps per wave): workspaces state [2][B][4][DB][nchunk][N][64], sdt and ysum
  * [B][4][DB][nchunk][64] with DB = ceil(D/64), nchunk = ceil(L/chunk); ysum receives per-chunk sums of y
- * (for the ShuffleAttn mean).  (N, R) in {(4,3), (8,6), (16,12), (32,24)}. */
+ * (for the ShuffleAttn mean).  (N, R) in {(4,3), (8,6), (16,12), (32,24)} (MaIRUNet levels) and {(1,4), (16,4)}
+ * (MaIR at embed_dim 60: dt_rank = ceil(60 / 16); d_state 1 is the lightweight-SR configuration).  For the MaIR pairs
+ * with D % 64 != 0 the lanes run over (direction, channel) (ceil(4D/64) waves per chunk; choose chunk with
+ * ops.scan_plan(flat=True)); the workspace layout is the same, its slots of channels d >= D are left unwritten. */
 int irm_selective_scan_f32(const float* xT, const float* pT, const int* ids, const float* dtw, const float* dtb,
                            const float* A, const float* Dskip, float* yT, float* state, float* sdt, float* ysum,
                            int B, int L, int D, int N, int R, int chunk, irm_stream_t stream);
