@@ -18,14 +18,24 @@ import yaml as _yaml
 
 from .mairunet_arch import MaIRUNet  # noqa: E402
 from .mair_arch import MaIR  # noqa: E402
+from ..ensemble import SelfEnsemble  # noqa: E402
 
-__all__ = ["MaIRUNet", "MaIR", "get_model", "SYNTH_RULES"]
+__all__ = ["MaIRUNet", "MaIR", "MaIRPlus", "get_model", "SYNTH_RULES"]
 
 
-def get_model(opt_path: str):
+class MaIRPlus(SelfEnsemble):
+    """MaIR+ (the option files' `model_type: MaIRPlusModel`, mairplus_model.py): the network under the x8 self-ensemble
+    with the partitioned forward.  For the flat MaIR, which takes any H x W."""
+
+    def __init__(self, net):
+        super().__init__(net, chop=True)
+
+
+def get_model(opt_path: str, plus: bool = False):
     """yml -> network_g -> MaIRUNet, weights from path.pretrain_network_g under key 'params' with an
     optional 'module.' prefix (BasicSR load_network, base_model.py:277-304), eval mode, on the GPU iff
-    num_gpu != 0 and one is present (base_model.py:18).  No device argument, like the reference."""
+    num_gpu != 0 and one is present (base_model.py:18).  No device argument, like the reference.
+    plus=True: the network wrapped in MaIRPlus (the reference selects it with model_type in the same option file)."""
     with open(opt_path, mode="r") as f:
         opt = _yaml.safe_load(f)
     net_opt = dict(opt["network_g"])
@@ -42,4 +52,4 @@ def get_model(opt_path: str):
         model.to("cuda")
     model.eval()
     print(f"Successfully loaded {_np.sum([p.numel() for p in model.parameters()]):,} parameters from {weights_path}")
-    return model
+    return MaIRPlus(model).eval() if plus else model

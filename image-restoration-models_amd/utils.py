@@ -23,13 +23,13 @@ from .configs import PATCH_CONFIG, ROOT_RESULTS_DIR, ROOT_WEIGHTS_DIR
 from .dncnn import DnCNN
 from .rednet import REDNet
 from .restormer import Restormer
-from .mair import MaIR, MaIRUNet
+from .mair import MaIR, MaIRPlus, MaIRUNet
 from .deblurganv2 import FPNMobileNet
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
 #: model classes whose forward is the HIP path (isinstance dispatch as in utils.py:280/292)
-_PAD8_MODELS = (Restormer, MaIR, MaIRUNet)
+_PAD8_MODELS = (Restormer, MaIR, MaIRUNet, MaIRPlus)
 
 
 def get_model_total_parameters(model: Module) -> int:
@@ -76,6 +76,8 @@ def get_gaussian_weights(height: int, width: int, n_channels=3, sigma_scale=0.12
 def get_patch_config(task, subtask, model_name) -> dict | None:
     """src/utils.py:184-213."""
     model_key = model_name.split(' ')[0]
+    if model_key == 'MaIR+':                      # the same network under the x8 self-ensemble: the same tiles
+        model_key = 'MaIR'
     config = PATCH_CONFIG.get(model_key, None)
     if isinstance(config, list):
         if model_key == 'DeblurGANv2':
@@ -123,15 +125,16 @@ def get_model_instance(task, subtask, model_name, device: torch.device, gray=Fal
                 return restormer.get_model(_restormer_opt('DefocusDeblur_Single_8bit_Restormer'), device)
             if subtask == 'motion':
                 return restormer.get_model(_restormer_opt('Deblurring_Restormer'), device)
-    elif model_key == 'MaIR':
+    elif model_key in ('MaIR', 'MaIR+'):
         opt_dir = os.path.join(_PKG_DIR, 'mair', 'options')
+        plus = model_key == 'MaIR+'               # the same option files (model_type: MaIRPlusModel), wrapped
         if task == 'denoising':
             if subtask == 'gaussian' and not gray and sigma is not None:
-                return mair.get_model(os.path.join(opt_dir, f'test_MaIR_CDN_s{sigma}.yml'))
+                return mair.get_model(os.path.join(opt_dir, f'test_MaIR_CDN_s{sigma}.yml'), plus=plus)
             if subtask == 'real':
-                return mair.get_model(os.path.join(opt_dir, 'test_MaIR_RealDN.yml'))
+                return mair.get_model(os.path.join(opt_dir, 'test_MaIR_RealDN.yml'), plus=plus)
         if task == 'deblurring' and subtask == 'motion':
-            return mair.get_model(os.path.join(opt_dir, 'test_MaIR_MotionDeblur.yml'))
+            return mair.get_model(os.path.join(opt_dir, 'test_MaIR_MotionDeblur.yml'), plus=plus)
     elif model_key == 'DeblurGANv2':
         if task == 'deblurring' and subtask == 'motion':
             if 'Inception' in model_name:

@@ -413,6 +413,32 @@ int irm_dwconv3x3_s2_f32(const float* x, long x_bs, const float* w, float* y, lo
 int irm_upsample_add_f32(const float* src, long s_bs, const float* add, long a_bs, float* out, long o_bs, int B, int C,
                          int Hs, int Ws, int scale, irm_stream_t stream);
 
+/* --- x8 self-ensemble with partitioned forward (MaIR+: mairplus_model.py; sr_model.py:132-178 without partitions) ---
+ * Geometry table, int32 on the device, (8 + P) rows of 8 (irm_amd/ensemble.py builds it):
+ *   rows 0..7      variant e = vf + 2 hf + 4 tr (aug = transpose^tr(hflip^hf(vflip^vf(img)))):
+ *                  {nh, nw, split_h, split_w, shave_h, shave_w, p0, 0} - the grid of the AUGMENTED image (a transposed
+ *                  variant has its own: the reference pads and chops after augmenting), partition (i, j) is row
+ *                  8 + p0 + i nw + j;
+ *   rows 8..8+P-1  partition: {e, y0, x0, ph, pw, pix_off, 0, 0} - origin in the right/bottom reflect-padded augmented
+ *                  image, extent, and the pixel offset of image 0's block in the packed buffer.
+ * Packed buffer: partition p of image b is a dense [C][ph][pw] block at float offset (pix_off + b ph pw) C, so the
+ * partitions of one shape, placed back to back, are a [n][C][ph][pw] network input.
+ *
+ * irm_dihedral_chop_f32: src [B][C][H][W] -> every partition of the table (any subset of the variants), one pass;
+ * pure data movement.  dst_pixels = capacity of dst in pixels (floats / C); max_ph, max_pw = the largest partition
+ * extents (launch grid).  Rows that would leave dst are skipped, source coordinates are clamped into the plane. */
+int irm_dihedral_chop_f32(const float* src, const int* table, float* dst, long dst_pixels, int B, int C, int H, int W,
+                          int P, int max_ph, int max_pw, irm_stream_t stream);
+/* irm_ensemble_merge_f32: pred = the packed buffer at output scale (partition p, image b: [Co][scale ph][scale pw] at
+ * float offset (pix_off + b ph pw) scale^2 Co), table with all 8 variants in rows 0..7.  For every output pixel: per
+ * variant the partition whose interior owns it and the shaved offset inside its prediction (mairplus_model.py:65-77,
+ * x scale), the inverse transform, the sum ((m0 + m1) + (m2 + m3)) + ((m4 + m5) + (m6 + m7)) x 0.125 (a fixed order in
+ * which 8 equal members give their own value exactly; no atomics), the crop of the padded rows / columns (:103).
+ * out [B][Co][scale H][scale W], scale in 1..4; H, W in input pixels; pred_pixels = capacity of pred in input pixels
+ * (floats / (Co scale^2)). */
+int irm_ensemble_merge_f32(const float* pred, const int* table, float* out, long pred_pixels, int B, int Co, int H,
+                           int W, int P, int scale, irm_stream_t stream);
+
 /* [B][R][C] -> [B][C][R] (planar NCHW <-> channel-last tokens around the selective scan). */
 int irm_transpose_f32(const float* in, long in_bs, float* out, long out_bs, int B, int R, int C,
                       irm_stream_t stream);
