@@ -65,6 +65,8 @@ SIGNATURES = {
     "irm_window_blend": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P],
     "irm_window_blend_scaled": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P],
     "irm_frame_metrics": [_P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _L, _P],
+    "irm_imresize_bicubic": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "irm_frame_metrics_basicsr": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "irm_dihedral_chop_f32": [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P],
     "irm_ensemble_merge_f32": [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],
 }

@@ -2,18 +2,21 @@
 inference time, per (dataset, model) their mean and standard deviation, one CSV row per combination with
 the reference's column names.  Dataset file IO is out of scope - `loader` is any iterable yielding
 (input_uint8_hwc, target_uint8_hwc, name), e.g. `synthetic_loader`.  For a super-resolving model (`model.upscale`
-s > 1) the pairs are (low-resolution input, s x larger target)."""
+s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `evaluate_sr` make them from HR frames
+by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics)."""
 from __future__ import annotations
 
 import csv
 import os
+import time
 
 import numpy as np
 import torch
 
 from . import synth
-from .utils import (_get_model_prediction, calculate_metrics, calculate_metrics_device, get_model_prediction,
-                    get_model_total_parameters)
+from .utils import (_get_model_prediction, calculate_metrics, calculate_metrics_basicsr,
+                    calculate_metrics_basicsr_device, calculate_metrics_device, get_model_prediction,
+                    get_model_total_parameters, imresize_device, mod_crop)
 
 COLUMNS = ['Task', 'Type', 'Dataset', 'Sigma', 'Model', 'Model_Params', 'PSNR', 'SSIM', 'Std_PSNR', 'Std_SSIM',
            'Avg_Time_ms', 'Std_Time_ms']
@@ -86,6 +89,92 @@ def _device_metrics(pred, pred_dev, target_img, device):
     tgt = target_img.view(np.int16) if target_img.dtype == np.uint16 else target_img
     tgt_dev = torch.from_numpy(np.ascontiguousarray(tgt)).to(pred_dev.device)
     return calculate_metrics_device(pred_dev, tgt_dev)
+
+
+def _to_device(img: np.ndarray, device) -> torch.Tensor:
+    """A uint8 / uint16 host frame on the GPU (uint16 as its int16 bit pattern, as the tiler takes it)."""
+    src = img.view(np.int16) if img.dtype == np.uint16 else img
+    return torch.from_numpy(np.ascontiguousarray(src)).to(device)
+
+
+def _to_host(t: torch.Tensor, dtype) -> np.ndarray:
+    a = t.view(torch.int16).cpu().numpy() if t.dtype == torch.uint16 else t.cpu().numpy()
+    return a.view(np.uint16) if dtype == np.uint16 else a
+
+
+def sr_pairs(hr_loader, scale: int, device):
+    """Super-resolution pairs from HR frames: yields (lr, hr_mod_cropped, name) host arrays.  `hr_loader` yields
+    (hr, name) or, like `synthetic_loader`, (input, target, name) - the target is the HR frame.  The HR frame is
+    mod-cropped to a multiple of `scale`; the LR frame is MATLAB's antialiased bicubic imresize of it by 1 / scale, made
+    on the GPU (imresize_device) and quantised to the HR dtype, as LR files are made."""
+    if scale not in (2, 3, 4):
+        raise ValueError(f"sr_pairs: scale must be 2, 3 or 4, not {scale!r}")
+    for item in hr_loader:
+        hr, name = (item[-2], item[-1])
+        if not isinstance(hr, np.ndarray) or hr.dtype not in (np.uint8, np.uint16):
+            raise ValueError("sr_pairs needs uint8 or uint16 HR frames")
+        hr = np.ascontiguousarray(mod_crop(hr, scale))
+        lr = imresize_device(_to_device(hr, device), 1.0 / scale, out="same")
+        yield _to_host(lr, hr.dtype), hr, name
+
+
+def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, task: str = "super-resolution",
+                subtask: str | None = None, dataset: str = "synthetic", model_name: str | None = None, sigma='N/A',
+                crop_border: int | None = None, test_y_channel: bool = True, channel_order: str = "rgb",
+                skip_failed=True, metrics="device") -> dict:
+    """One results_table row by the super-resolution protocol: per HR frame, mod-crop, LR by MATLAB bicubic on the
+    GPU (`sr_pairs`), the model's x`scale` prediction, then basicsr's PSNR / SSIM with `crop_border` pixels (default:
+    `scale`) cropped from every side, on the Y channel unless test_y_channel=False.  The timed region is what
+    `evaluate` times (input upload through output download of the prediction); LR synthesis and scoring are outside
+    it.  metrics="device" scores the prediction while it is on the GPU (calculate_metrics_basicsr_device),
+    metrics="host" the downloaded one (calculate_metrics_basicsr); they differ by rounding only.
+    model=None gives the bicubic baseline row: the prediction is imresize_device(lr, scale), the time that of the
+    upload, the resize and the download.  Failed frames are handled as in `evaluate`."""
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
+    if scale not in (2, 3, 4):
+        raise ValueError(f"evaluate_sr: scale must be 2, 3 or 4, not {scale!r}")
+    if model is not None and int(getattr(model, "upscale", 1) or 1) != scale:
+        raise ValueError(f"evaluate_sr: scale {scale} but model.upscale = {getattr(model, 'upscale', 1)}")
+    crop = scale if crop_border is None else crop_border
+    if int(crop) != crop or crop < 0:
+        raise ValueError(f"crop_border must be a non-negative integer, not {crop_border!r}")
+    if channel_order not in ("rgb", "bgr"):
+        raise ValueError(f"channel_order must be 'rgb' or 'bgr', not {channel_order!r}")
+    if model_name is None:
+        model_name = "Bicubic" if model is None else type(model).__name__
+    psnr_list, ssim_list, time_list, failed = [], [], [], []
+    for lr, hr, name in sr_pairs(hr_loader, scale, device):
+        try:
+            if model is None:
+                start = time.time()
+                pred_dev = imresize_device(_to_device(lr, device), scale, out="same")
+                pred = _to_host(pred_dev, lr.dtype)
+                ms = (time.time() - start) * 1000
+            else:
+                pred, ms, pred_dev = _get_model_prediction(model, lr, device, **patch_config)
+            if pred.shape != hr.shape:
+                raise ValueError(f"prediction {pred.shape} for an HR frame {hr.shape}")
+            if metrics == "device":
+                if pred_dev is None:
+                    pred_dev = _to_device(pred, device)
+                p, s = calculate_metrics_basicsr_device(pred_dev, _to_device(hr, pred_dev.device), crop, test_y_channel,
+                                                        channel_order)
+            else:
+                p, s = calculate_metrics_basicsr(pred, hr, crop, test_y_channel, channel_order)
+        except Exception as e:                                  # noqa: BLE001 (reported, not swallowed)
+            if not skip_failed or "out of memory" in str(e).lower():
+                raise
+            failed.append((name, f"{type(e).__name__}: {e}"))
+            print(f"[harness] {model_name} on {dataset}: frame {name} failed ({type(e).__name__}: {e}); skipped")
+            continue
+        psnr_list.append(p)
+        ssim_list.append(s)
+        time_list.append(ms)
+    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask or f"x{scale}", dataset=dataset, sigma=sigma,
+                    model_name=model_name, params=0 if model is None else get_model_total_parameters(model))
+    row['Failed'] = failed
+    return row
 
 
 def aggregate(psnr_list, ssim_list, time_list, *, task, subtask, dataset, sigma, model_name, params) -> dict:

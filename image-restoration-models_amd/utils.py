@@ -269,6 +269,285 @@ def calculate_metrics_device(pred_dev: torch.Tensor, target_dev: torch.Tensor, d
 
 
 # ---------------------------------------------------------------------------
+# super-resolution protocol: MATLAB bicubic resize, Y-channel / cropped metrics (basicsr)
+# ---------------------------------------------------------------------------
+
+_RESIZE_SCALES = (2, 3, 4)
+
+
+def mod_crop(img, scale: int):
+    """Drop the bottom rows / right columns beyond a multiple of `scale` (HW or HWC array or tensor; a view)."""
+    scale = int(scale)
+    if scale < 1:
+        raise ValueError(f"mod_crop: scale must be a positive integer, not {scale}")
+    if len(img.shape) not in (2, 3):
+        raise ValueError(f"mod_crop takes HW or HWC frames, not shape {tuple(img.shape)}")
+    h, w = img.shape[:2]
+    return img[:h - h % scale, :w - w % scale]
+
+
+def _resize_factor(scale) -> tuple:
+    """scale -> (s, shrink) for s or 1 / s with s in {2, 3, 4}; ValueError otherwise."""
+    for s in _RESIZE_SCALES:
+        if scale == s:
+            return s, False
+        if isinstance(scale, float) and abs(scale * s - 1.0) < 1e-12:
+            return s, True
+    raise ValueError(f"resize factor must be s or 1/s with s in {_RESIZE_SCALES}, not {scale!r}")
+
+
+def _cubic(x: np.ndarray) -> np.ndarray:
+    a = np.abs(x)
+    return np.where(a <= 1, (1.5 * a - 2.5) * a * a + 1, np.where(a <= 2, ((-0.5 * a + 2.5) * a - 4) * a + 2, 0.0))
+
+
+def resize_table(in_length: int, scale) -> tuple:
+    """Taps of MATLAB's bicubic imresize along one axis, in float64: (weights [out][P], indices [out][P] int64,
+    0-based and reflected into [0, in_length)), out = ceil(in_length * scale).  u = x / scale + 0.5 (1 - 1 / scale) for
+    the 1-based output coordinate x; kernel width 4, or 4 / scale when shrinking (antialiasing); P = ceil(width) + 2 taps
+    from floor(u - width / 2); the cubic kernel at scale * distance times scale when shrinking; rows normalised to sum 1.
+    Zero-weight edge taps stay in the table."""
+    s, shrink = _resize_factor(scale)
+    scale = 1.0 / s if shrink else float(s)
+    width = 4 * s if shrink else 4
+    p = width + 2
+    if in_length < p:
+        raise ValueError(f"resize by {scale:g}: a side of {in_length} is shorter than the {p} taps")
+    out_length = -(-in_length // s) if shrink else in_length * s
+    x = np.arange(1, out_length + 1, dtype=np.float64)
+    u = x / scale + 0.5 * (1 - 1 / scale)
+    left = np.floor(u - width / 2)
+    idx = left[:, None] + np.arange(p, dtype=np.float64)[None, :]           # 1-based
+    dist = u[:, None] - idx
+    w = scale * _cubic(dist * scale) if shrink else _cubic(dist)
+    w = w / w.sum(1, keepdims=True)
+    i0 = idx.astype(np.int64) - 1
+    i0 = np.where(i0 < 0, -i0 - 1, np.where(i0 >= in_length, 2 * in_length - 1 - i0, i0))
+    assert i0.min() >= 0 and i0.max() < in_length
+    return w, i0
+
+
+def _check_resize_frame(shape, what="imresize") -> tuple:
+    if len(shape) == 2:
+        return shape[0], shape[1], 1
+    if len(shape) == 3 and shape[2] in (1, 3):
+        return tuple(shape)
+    raise ValueError(f"{what} takes HW or HWC frames with 1 or 3 channels, not shape {tuple(shape)}")
+
+
+def imresize_host(img: np.ndarray, scale, out: str = "float") -> np.ndarray:
+    """MATLAB bicubic imresize (antialiased when shrinking) of a uint8 / uint16 HW or HWC frame, restated in float64:
+    the frame / 255 (65535), the H pass, then the W pass.  out="float": float64 in [0, 1] nominal, unrounded;
+    out="same": clipped to [0, 1], x 255 (65535), rounded half to even, in the frame's dtype (tensor2img)."""
+    if out not in ("float", "same"):
+        raise ValueError(f"out must be 'float' or 'same', not {out!r}")
+    if not isinstance(img, np.ndarray) or img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("imresize_host takes uint8 or uint16 numpy frames")
+    h, w, _ = _check_resize_frame(img.shape, "imresize_host")
+    wh, ih = resize_table(h, scale)
+    ww, iw = resize_table(w, scale)
+    peak = 255.0 if img.dtype == np.uint8 else 65535.0
+    x = img.astype(np.float64) / peak
+    mid = np.zeros((wh.shape[0],) + x.shape[1:], np.float64)
+    for p in range(wh.shape[1]):                                              # ascending tap order
+        mid += wh[:, p].reshape((-1,) + (1,) * (x.ndim - 1)) * x[ih[:, p]]
+    res = np.zeros((mid.shape[0], ww.shape[0]) + mid.shape[2:], np.float64)
+    for p in range(ww.shape[1]):
+        res += ww[:, p].reshape((1, -1) + (1,) * (x.ndim - 2)) * mid[:, iw[:, p]]
+    if out == "float":
+        return res
+    return np.round(np.clip(res, 0.0, 1.0) * peak).astype(img.dtype)
+
+
+_RESIZE_TABLES: dict = {}
+
+
+def _resize_table_on(device, in_length: int, s: int, shrink: bool) -> tuple:
+    """The axis table on the device (fp32 weights, int32 indices), cached per (device, length, factor) like
+    mairunet_arch.scan_ids: a repeated or captured call enqueues kernels only."""
+    key = (str(device), in_length, s, shrink)
+    if key not in _RESIZE_TABLES:
+        w, i = resize_table(in_length, 1.0 / s if shrink else s)
+        _RESIZE_TABLES[key] = (torch.from_numpy(w.astype(np.float32)).contiguous().to(device),
+                               torch.from_numpy(i.astype(np.int32)).contiguous().to(device))
+    return _RESIZE_TABLES[key]
+
+
+def imresize_device(frames, scale, out: str = "same"):
+    """MATLAB bicubic imresize on the GPU (irm_imresize_bicubic): `frames` is one uint8 / uint16 (or int16 = uint16 bit
+    pattern) HW / HWC GPU tensor, a [K][H][W][C] stack, or a list of frames of one shape; scale is s or 1/s, s in
+    {2, 3, 4}.  out="same": quantised to the input's dtype (how LR files are made); out="float": float32 in [0, 1]
+    nominal, unrounded.  Returns the same arrangement (tensor -> tensor, list -> list) without synchronising."""
+    if out not in ("float", "same"):
+        raise ValueError(f"out must be 'float' or 'same', not {out!r}")
+    s, shrink = _resize_factor(scale)
+    as_list = isinstance(frames, (list, tuple))
+    items = list(frames) if as_list else [frames]
+    if not items:
+        raise ValueError("imresize_device: no frames")
+    for f in items:
+        if not isinstance(f, torch.Tensor):
+            raise ValueError("imresize_device takes torch tensors (imresize_host takes numpy arrays)")
+        if f.dtype not in _METRICS_DTYPES:
+            raise ValueError(f"imresize_device takes uint8 or uint16 frames, not {f.dtype}")
+        if f.shape != items[0].shape or f.dtype != items[0].dtype or f.device != items[0].device:
+            raise ValueError("the frames of one call must share shape, dtype and device")
+        if not f.is_cuda:
+            raise ValueError("imresize_device needs GPU tensors; there is no CPU fallback (imresize_host takes host arrays)")
+    f0 = items[0]
+    stacked = not as_list and f0.dim() == 4
+    if stacked:
+        k, (h, w, c) = f0.shape[0], _check_resize_frame(f0.shape[1:], "imresize_device")
+        if k < 1:
+            raise ValueError("imresize_device: empty stack")
+    else:
+        k, (h, w, c) = len(items), _check_resize_frame(f0.shape, "imresize_device")
+    p = 4 * s + 2 if shrink else 6
+    if min(h, w) < p:
+        raise ValueError(f"resize by {scale:g}: a {h}x{w} frame has a side shorter than the {p} taps")
+    oh, ow = (-(-h // s), -(-w // s)) if shrink else (h * s, w * s)
+    as_bits = (lambda x: x.view(torch.int16)) if f0.dtype == torch.uint16 else (lambda x: x)
+    dev = f0.device
+    with torch.cuda.device(dev):
+        src = as_bits(f0).contiguous() if (stacked or k == 1) else torch.stack([as_bits(x) for x in items])
+        wh, ih = _resize_table_on(dev, h, s, shrink)
+        ww, iw = _resize_table_on(dev, w, s, shrink)
+        res = torch.empty((k, oh, ow, c), dtype=torch.float32 if out == "float" else src.dtype, device=dev)
+        _hip.call("irm_imresize_bicubic", _hip.ptr(src), int(f0.dtype != torch.uint8), _hip.ptr(res), int(out == "float"),
+                  _hip.ptr(wh), _hip.ptr(ih), _hip.ptr(ww), _hip.ptr(iw), k, h, w, c, s, int(shrink))
+    if out == "same" and f0.dtype == torch.uint16:
+        res = res.view(torch.uint16)
+    tail = (oh, ow) if (f0.dim() - int(stacked)) == 2 else (oh, ow, c)
+    if stacked:
+        return res.view((k,) + tail)
+    return [r.view(tail) for r in res] if as_list else res[0].view(tail)
+
+
+_Y_COEF = {"rgb": (65.481, 128.553, 24.966), "bgr": (24.966, 128.553, 65.481)}
+
+
+def _gauss11() -> np.ndarray:
+    g = np.exp(-((np.arange(11) - 5.0) ** 2) / (2 * 1.5 ** 2))
+    return g / g.sum()
+
+
+def _basicsr_values(img: np.ndarray, crop_border: int, test_y_channel: bool, channel_order: str) -> np.ndarray:
+    """The HxWxCe float64 values the reference's metrics see (psnr_ssim.py:32-41, metric_util.to_y_channel)."""
+    peak = np.float32(255.0 if img.dtype == np.uint8 else 65535.0)
+    if img.ndim == 2:
+        img = img[..., None]
+    if crop_border:
+        img = img[crop_border:-crop_border, crop_border:-crop_border]
+    if not test_y_channel:
+        return img.astype(np.float64)
+    v = img.astype(np.float32) / peak                                         # fp32
+    if img.shape[2] == 3:
+        k = _Y_COEF[channel_order]
+        v64 = v.astype(np.float64)
+        y = ((v64[..., 0] * k[0] + v64[..., 1] * k[1]) + v64[..., 2] * k[2]) + 16.0      # fp64
+        v = (y / 255.0).astype(np.float32)[..., None]
+    return (v * peak).astype(np.float64)                                      # the product is fp32
+
+
+def _check_basicsr_args(shape, crop_border, channel_order):
+    if channel_order not in _Y_COEF:
+        raise ValueError(f"channel_order must be 'rgb' or 'bgr', not {channel_order!r}")
+    if int(crop_border) != crop_border or crop_border < 0:
+        raise ValueError(f"crop_border must be a non-negative integer, not {crop_border!r}")
+    h, w, c = _check_resize_frame(shape, "the basicsr metrics")
+    if min(h, w) - 2 * crop_border < 11:
+        raise ValueError(f"frame {h}x{w} cropped by {crop_border}: both sides must keep at least 11 pixels, the SSIM window")
+    return h, w, c
+
+
+def calculate_metrics_basicsr(pred: np.ndarray, target: np.ndarray, crop_border: int, test_y_channel: bool,
+                              channel_order: str = "rgb"):
+    """(psnr, ssim) of the super-resolution protocol for uint8 / uint16 HW or HWC frames: basicsr's calculate_psnr /
+    calculate_ssim restated (crop, optional BT.601 Y channel with the reference's fp32 / fp64 steps, 11x11 Gaussian
+    window of sigma 1.5 applied separably over the valid region, channel mean).  The Y-channel squared error is
+    summed in float64 (the reference takes that mean in fp32)."""
+    if not isinstance(pred, np.ndarray) or not isinstance(target, np.ndarray):
+        raise ValueError("calculate_metrics_basicsr takes numpy arrays (calculate_metrics_basicsr_device takes GPU tensors)")
+    if pred.shape != target.shape or pred.dtype != target.dtype:
+        raise ValueError(f"prediction {pred.shape} {pred.dtype} and target {target.shape} {target.dtype} differ")
+    if pred.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"the basicsr metrics take uint8 or uint16 frames, not {pred.dtype}")
+    _check_basicsr_args(pred.shape, crop_border, channel_order)
+    peak = 255.0 if pred.dtype == np.uint8 else 65535.0
+    x = _basicsr_values(pred, int(crop_border), bool(test_y_channel), channel_order)
+    y = _basicsr_values(target, int(crop_border), bool(test_y_channel), channel_order)
+    mse = np.mean((x - y) ** 2)
+    psnr_value = float('inf') if mse == 0 else float(10 * np.log10(peak ** 2 / mse))
+    c1, c2 = (0.01 * peak) ** 2, (0.03 * peak) ** 2
+    g = _gauss11()
+
+    def blur(a):                                                              # valid region, rows then columns
+        n0, n1 = a.shape[0] - 10, a.shape[1] - 10
+        v = sum(g[d] * a[d:d + n0] for d in range(11))
+        return sum(g[d] * v[:, d:d + n1] for d in range(11))
+    vals = []
+    for ch in range(x.shape[2]):
+        a, b = x[..., ch], y[..., ch]
+        m1, m2 = blur(a), blur(b)
+        v1, v2, v12 = blur(a * a) - m1 * m1, blur(b * b) - m2 * m2, blur(a * b) - m1 * m2
+        vals.append((((2 * (m1 * m2) + c1) * (2 * v12 + c2)) / ((m1 * m1 + m2 * m2 + c1) * (v1 + v2 + c2))).mean())
+    return psnr_value, float(np.mean(vals))
+
+
+def frame_metrics_basicsr_device(preds, targets, crop_border: int, test_y_channel: bool, channel_order: str = "rgb"):
+    """Device squared-error sums and SSIMs of K prediction / target frames of one shape (irm_frame_metrics_basicsr):
+    returns (sse [K] - int64, exact, with test_y_channel off; float64 with it on - and ssim [K] float64) as device
+    tensors, without synchronising.  A frame's values are bitwise the same whatever K and on every call."""
+    preds, targets = list(preds), list(targets)
+    if not preds or len(preds) != len(targets):
+        raise ValueError(f"{len(preds)} predictions and {len(targets)} targets: need the same number, at least one")
+    for p_, t_ in zip(preds, targets):
+        if not isinstance(p_, torch.Tensor) or not isinstance(t_, torch.Tensor):
+            raise ValueError("device metrics take torch tensors (use calculate_metrics_basicsr for numpy arrays)")
+        if p_.shape != t_.shape or p_.dtype != t_.dtype or p_.shape != preds[0].shape or p_.dtype != preds[0].dtype:
+            raise ValueError("the frames of one call must share shape and dtype")
+        if p_.dtype not in _METRICS_DTYPES:
+            raise ValueError(f"device metrics take uint8 or uint16 frames, not {p_.dtype}")
+    h, w, c = _check_basicsr_args(preds[0].shape, crop_border, channel_order)
+    for p_, t_ in zip(preds, targets):
+        if not p_.is_cuda or not t_.is_cuda:
+            raise ValueError("device metrics need GPU tensors; there is no CPU fallback")
+        if p_.device != preds[0].device or t_.device != preds[0].device:
+            raise ValueError("the frames of one call must share a device")
+    crop_border, test_y = int(crop_border), bool(test_y_channel)
+    as_bits = (lambda x: x.view(torch.int16)) if preds[0].dtype == torch.uint16 else (lambda x: x)
+    k, dev = len(preds), preds[0].device
+    ce = 1 if test_y else c
+    with torch.cuda.device(dev):
+        if k == 1:
+            p, t = as_bits(preds[0]).contiguous(), as_bits(targets[0]).contiguous()
+        else:
+            p, t = torch.stack([as_bits(x) for x in preds]), torch.stack([as_bits(x) for x in targets])
+        tiles = (-(-(h - 2 * crop_border - 10) // _METRICS_TILE_ROWS)
+                 * -(-(w - 2 * crop_border - 10) // (_METRICS_TILE_VALUES // ce)))
+        ws = torch.empty(2 * k * tiles, dtype=torch.float64, device=dev)
+        sse = torch.empty(k, dtype=torch.float64 if test_y else torch.int64, device=dev)
+        ssim_dev = torch.empty(k, dtype=torch.float64, device=dev)
+        _hip.call("irm_frame_metrics_basicsr", _hip.ptr(p), _hip.ptr(t), int(preds[0].dtype != torch.uint8), k, h, w, c,
+                  crop_border, int(test_y), int(channel_order == "bgr"), _hip.ptr(sse), _hip.ptr(ssim_dev), _hip.ptr(ws),
+                  ws.numel())
+    return sse, ssim_dev
+
+
+def calculate_metrics_basicsr_device(pred_dev: torch.Tensor, target_dev: torch.Tensor, crop_border: int,
+                                     test_y_channel: bool, channel_order: str = "rgb"):
+    """Device twin of calculate_metrics_basicsr: (psnr, ssim) as Python floats after one synchronising copy."""
+    sse, ssim_dev = frame_metrics_basicsr_device([pred_dev], [target_dev], crop_border, test_y_channel, channel_order)
+    h, w, c = _check_resize_frame(pred_dev.shape)
+    host = torch.stack([sse.view(torch.int64), ssim_dev.view(torch.int64)]).cpu()     # the one host synchronisation
+    sse_v = float(host[0].view(torch.float64)[0]) if test_y_channel else int(host[0, 0])
+    ssim_v = float(host[1].view(torch.float64)[0])
+    peak = 255.0 if pred_dev.dtype == torch.uint8 else 65535.0
+    n = (h - 2 * int(crop_border)) * (w - 2 * int(crop_border)) * (1 if test_y_channel else c)
+    return (float('inf') if sse_v == 0 else float(10 * np.log10(peak ** 2 / (sse_v / n)))), ssim_v
+
+
+# ---------------------------------------------------------------------------
 # tiled-patch inference
 # ---------------------------------------------------------------------------
 

@@ -388,6 +388,42 @@ int irm_window_blend_scaled(const float* pred, const int* origins, const float* 
 int irm_frame_metrics(const void* pred, const void* target, int is_u16, int K, int H, int W, int C, double data_range,
                       unsigned long long* sse, double* ssim, void* ws, long ws_words, irm_stream_t stream);
 
+/* MATLAB-compatible bicubic resize (imresize, antialiasing on; basicsr/utils/matlab_functions.py) of K frames
+ * in [K][H][W][C] interleaved, uint8 (is_u16 = 0) or uint16 (is_u16 = 1), C = 1 or 3, by the integer factor s
+ * (shrink = 0) or 1 / s (shrink = 1), s = 2, 3, 4.  out is [K][OH][OW][C] with OH = s H or ceil(H / s) (OW alike).
+ * Tables (device, built by the host in float64): per axis and output coordinate x (1-based) the P taps that start
+ * at floor(u - width / 2), u = x / scale + 0.5 (1 - 1 / scale), width = 4 (enlarging) or 4 s (shrinking),
+ * P = width + 2 (6, or 10 / 14 / 18): wh [OH][P] / ww [OW][P] float32 weights - the cubic kernel at the tap's distance
+ * (at distance / s, divided by s, when shrinking), each row normalised to sum 1 - and ih / iw int32 source indices,
+ * 0-based, reflected symmetrically into the frame (i < 0 -> -i - 1, i >= n -> 2 n - 1 - i).  Zero-weight edge taps
+ * stay in the table.  H, W >= P (a shorter side returns IRM_EINVAL: one reflection must reach every tap).
+ * Arithmetic: inputs v / 255 (or / 65535) in fp32; the H pass first, then the W pass, each tap sum an fp32 FMA
+ * chain in ascending tap order; the fp32 intermediate stays on chip.  out_float = 1: out is float32 in [0, 1]
+ * nominal, unrounded (what imresize returns).  out_float = 0: out has the input's type: clamp to [0, 1], x 255
+ * (65535) in fp32, round half to even (tensor2img).  A value does not depend on K, the tiling or the run. */
+int irm_imresize_bicubic(const void* in, int is_u16, void* out, int out_float, const float* wh, const int* ih,
+                         const float* ww, const int* iw, int K, int H, int W, int C, int s, int shrink,
+                         irm_stream_t stream);
+
+/* Per-frame squared-error sum and SSIM of the super-resolution protocol (basicsr/metrics/psnr_ssim.py,
+ * calculate_psnr / calculate_ssim) for K frame pairs [K][H][W][C] interleaved, uint8 or uint16, C = 1 or 3.
+ * Both frames are cropped by crop_border >= 0 pixels on every side; a cropped side below 11 returns IRM_EINVAL.
+ * R = 255 (uint8) or 65535 (uint16).
+ *   test_y_channel = 0: the raw values of all C channels.  sse[k] is a uint64, the exact integer sum.
+ *   test_y_channel = 1: one channel.  C = 3: BT.601 luma with the reference's rounding steps: v / R in fp32; the
+ *     three-term dot in fp64 in ascending channel order, every product and sum rounded (coefficients 65.481,
+ *     128.553, 24.966 for bgr = 0, reversed for bgr = 1), plus 16 in fp64; / 255 in fp64; rounded to fp32; x R in
+ *     fp32.  C = 1: v / R x R in fp32.  sse[k] is an fp64: the sum of the fp64 squares of the fp64 differences.
+ *   ssim[k]: per channel over the valid region (Hc - 10) x (Wc - 10), separable 11-tap Gaussian window
+ *     exp(-(i - 5)^2 / (2 * 1.5^2)) normalised, fp64 moments, c1 = (0.01 R)^2, c2 = (0.03 R)^2; channel mean.
+ *     Identical frames give exactly 1.
+ * Bitwise reproducible as irm_frame_metrics is (workspace partials, fixed-order second launch, no atomics).
+ * Workspace of 8-byte words, Ce = test_y_channel ? 1 : C:
+ *   ws_words >= 2 * K * ceil((Hc - 10) / 16) * ceil((Wc - 10) / (192 / Ce)). */
+int irm_frame_metrics_basicsr(const void* pred, const void* target, int is_u16, int K, int H, int W, int C,
+                              int crop_border, int test_y_channel, int bgr, void* sse, double* ssim, void* ws,
+                              long ws_words, irm_stream_t stream);
+
 /* --- DeblurGANv2 FPN-MobileNet (train-mode norms = per-(sample, channel) statistics) ---
  * stats[b][c] = {mean, 1/sqrt(biased var + eps)} over the H*W plane: BatchNorm2d in train mode on one
  * tile (mobilenet_v2.py:5-57 with deblurganv2/__init__.py:38) and InstanceNorm2d (fpn_mobilenet.py:96-104). */
