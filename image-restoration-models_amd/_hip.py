@@ -67,6 +67,7 @@ SIGNATURES = {
     "irm_frame_metrics": [_P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _L, _P],
     "irm_imresize_bicubic": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "irm_frame_metrics_basicsr": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    "irm_niqe_features": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "irm_dihedral_chop_f32": [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P],
     "irm_ensemble_merge_f32": [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],
 }

@@ -3,7 +3,8 @@ inference time, per (dataset, model) their mean and standard deviation, one CSV 
 the reference's column names.  Dataset file IO is out of scope - `loader` is any iterable yielding
 (input_uint8_hwc, target_uint8_hwc, name), e.g. `synthetic_loader`.  For a super-resolving model (`model.upscale`
 s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `evaluate_sr` make them from HR frames
-by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics)."""
+by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics).  Where no target exists
+(real captures), `evaluate_blind` scores the frames by NIQE instead."""
 from __future__ import annotations
 
 import csv
@@ -15,11 +16,13 @@ import torch
 
 from . import synth
 from .utils import (_get_model_prediction, calculate_metrics, calculate_metrics_basicsr,
-                    calculate_metrics_basicsr_device, calculate_metrics_device, get_model_prediction,
-                    get_model_total_parameters, imresize_device, mod_crop)
+                    calculate_metrics_basicsr_device, calculate_metrics_device, calculate_niqe, calculate_niqe_device,
+                    get_model_prediction, get_model_total_parameters, imresize_device, mod_crop)
 
 COLUMNS = ['Task', 'Type', 'Dataset', 'Sigma', 'Model', 'Model_Params', 'PSNR', 'SSIM', 'Std_PSNR', 'Std_SSIM',
            'Avg_Time_ms', 'Std_Time_ms']
+#: the columns of an `evaluate_blind` row: the reference's plus the no-reference score
+COLUMNS_BLIND = COLUMNS + ['NIQE', 'Std_NIQE']
 
 
 def synthetic_loader(n_images: int, h: int = 720, w: int = 1280, c: int = 3, seed_base: int = 1000, blur: int = 15):
@@ -177,6 +180,57 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
     return row
 
 
+def evaluate_blind(model, loader, device, patch_config: dict, *, niqe_params, crop_border: int = 0, metrics="device",
+                   task: str = "blind", subtask: str = "N/A", dataset: str = "captures", model_name: str | None = None,
+                   sigma='N/A', channel_order: str = "rgb", need_degradation=False, noise_level=None,
+                   skip_failed=True) -> dict:
+    """One results_table row for frames without a target: per frame the model's prediction and its NIQE
+    (`niqe_params` from utils.load_niqe_params; `crop_border` pixels cropped from every side; the Y channel of colour
+    frames read in `channel_order`).  `loader` yields (input, name) or (input, target, name); a target is ignored.
+    The timed region is what `evaluate` times (input upload through output download); scoring is outside it.
+    metrics="device" scores the prediction while it is on the GPU (calculate_niqe_device), metrics="host" the
+    downloaded one (calculate_niqe); they differ by rounding only.  model=None scores the inputs themselves (the
+    "before" row; its times are 0).  The row has the reference's columns - PSNR and SSIM are NaN - plus 'NIQE' and
+    'Std_NIQE' (COLUMNS_BLIND).  Failed frames are handled as in `evaluate`."""
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
+    if model_name is None:
+        model_name = "Input" if model is None else type(model).__name__
+    niqe_list, time_list, failed = [], [], []
+    for item in loader:
+        input_img, name = item[0], item[-1]
+        try:
+            if model is None:
+                pred, ms, pred_dev = input_img, 0.0, None
+            else:
+                pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
+                                                           need_degradation=need_degradation, noise_level=noise_level)
+            if metrics == "device":
+                if not isinstance(pred, np.ndarray) or pred.dtype not in (np.uint8, np.uint16):
+                    raise ValueError("metrics='device' needs uint8 or uint16 frames")
+                if pred_dev is None:
+                    pred_dev = _to_device(pred, device)
+                q = calculate_niqe_device(pred_dev, crop_border, niqe_params, channel_order=channel_order)
+            else:
+                q = calculate_niqe(pred, crop_border, niqe_params, channel_order=channel_order)
+        except Exception as e:                                  # noqa: BLE001 (reported, not swallowed)
+            if not skip_failed or "out of memory" in str(e).lower():
+                raise
+            failed.append((name, f"{type(e).__name__}: {e}"))
+            print(f"[harness] {model_name} on {dataset}: frame {name} failed ({type(e).__name__}: {e}); skipped")
+            continue
+        niqe_list.append(q)
+        time_list.append(ms)
+    nan = [float('nan')] * len(niqe_list)
+    row = aggregate(nan, nan, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
+                    model_name=model_name, params=0 if model is None else get_model_total_parameters(model))
+    if not niqe_list:
+        niqe_list = [float('nan')]
+    row['NIQE'], row['Std_NIQE'] = np.mean(niqe_list), np.std(niqe_list)
+    row['Failed'] = failed
+    return row
+
+
 def aggregate(psnr_list, ssim_list, time_list, *, task, subtask, dataset, sigma, model_name, params) -> dict:
     if not psnr_list:                      # every frame failed: an empty row, not a numpy warning
         psnr_list = ssim_list = time_list = [float('nan')]
@@ -186,12 +240,14 @@ def aggregate(psnr_list, ssim_list, time_list, *, task, subtask, dataset, sigma,
             'Std_Time_ms': np.std(time_list)}
 
 
-def save_results(rows: list, out_dir: str = 'results', file_name: str = 'results_summary.csv') -> str:
-    """CSV with the reference's columns (scripts/tests.py:415-424; written with the csv module, not pandas)."""
+def save_results(rows: list, out_dir: str = 'results', file_name: str = 'results_summary.csv', columns=None) -> str:
+    """CSV with the reference's columns (scripts/tests.py:415-424; written with the csv module, not pandas), or with
+    `columns` (COLUMNS_BLIND for `evaluate_blind` rows); a column a row lacks stays empty."""
+    columns = COLUMNS if columns is None else list(columns)
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, file_name)
     with open(path, 'w', newline='') as f:
-        wr = csv.DictWriter(f, fieldnames=COLUMNS, extrasaction='ignore')
+        wr = csv.DictWriter(f, fieldnames=columns, extrasaction='ignore')
         wr.writeheader()
         for r in rows:
             wr.writerow(r)

@@ -424,6 +424,27 @@ int irm_frame_metrics_basicsr(const void* pred, const void* target, int is_u16, 
                               int crop_border, int test_y_channel, int bgr, void* sse, double* ssim, void* ws,
                               long ws_words, irm_stream_t stream);
 
+/* NIQE block features without a target frame (basicsr/metrics/niqe.py: niqe, compute_feature, estimate_aggd_param)
+ * for K frames [K][H][W][C] interleaved, uint8 or uint16, C = 1 or 3.  The plane: C = 3: the BT.601 luma
+ * ((b / 255 x 24.966 + g / 255 x 128.553) + r / 255 x 65.481) + 16, unrounded (bgr = 1: channel 0 is blue; bgr = 0:
+ * channel 0 is red; the sum runs in this order either way); C = 1: the values; uint16 values are divided by 257 first
+ * (the metric is defined on 0..255).  It is cropped by crop_border >= 0 pixels on every side, then to nbh x nbw whole
+ * 96 x 96 blocks (nbh = floor((H - 2 crop_border) / 96), nbw alike); fewer than two blocks return IRM_EINVAL (the
+ * score needs a covariance).  The scale-2 plane is the 2 x 2 mean of the cropped plane.
+ * Per scale s = 1, 2 and block (side 96 / s): local mean and sqrt|E[x^2] - mu^2| by the 7 x 7 `window` (device,
+ * 49 doubles, applied as a correlation: mu[y][x] = sum window[i][j] plane[y + i - 3][x + j - 3]) with the plane's
+ * border repeated; MSCN = (x - mu) / (sigma + 1); the AGGD fit of the block and of block x np.roll(block, shift) for
+ * the shifts (0, 1), (1, 0), (1, 1), (1, -1), circular inside the block.  A fit: left / right standard deviation over
+ * the strictly negative / positive values, rhat = mean|x|^2 / mean(x^2), the index of the first minimum of
+ * (r_gam - rhatnorm)^2 over `table` (device, [2][9801] doubles: r_gam, then the alpha grid gam; the host builds both).
+ * feat [K][nbw nbh][36] doubles, block (i_h, i_w) at index i_w nbh + i_h (the reference's order), the 18 features
+ * of scale 1 then those of scale 2; feat_words >= 36 K nbh nbw.  A block without negative or without positive values
+ * gives NaN features (alpha = gam[0]), as the reference does.
+ * All arithmetic is fp64.  One launch, no workspace, no atomics, every reduction in a fixed order: a frame's features
+ * are bitwise the same on every run and for any K. */
+int irm_niqe_features(const void* frames, int is_u16, int K, int H, int W, int C, int crop_border, int bgr,
+                      const double* window, const double* table, double* feat, long feat_words, irm_stream_t stream);
+
 /* --- DeblurGANv2 FPN-MobileNet (train-mode norms = per-(sample, channel) statistics) ---
  * stats[b][c] = {mean, 1/sqrt(biased var + eps)} over the H*W plane: BatchNorm2d in train mode on one
  * tile (mobilenet_v2.py:5-57 with deblurganv2/__init__.py:38) and InstanceNorm2d (fpn_mobilenet.py:96-104). */
