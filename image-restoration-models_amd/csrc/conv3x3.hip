@@ -52,7 +52,6 @@ struct ConvArgs {
 
 template <int CT>
 __global__ __launch_bounds__(256) void conv3x3_kernel(ConvArgs a) {
-    IRM_KERNEL_ENTRY();
     __shared__ float xs[2][CV_CK * CV_PLANE];
     // packed weights of one stage (9 taps x CT tiles x 2 k-steps x 64 lanes), double buffered like xs: read
     // from global once per stage with coalesced loads instead of one dependent load per tap inside the MFMA loop
@@ -257,16 +256,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(ConvArgs a) {
 // 400-float plane stride), out-of-image chunks read a 16-byte zero page, and the 9 taps' packed weights
 // of the pass (9*CT*256 B) arrive by DMA as well.  NS-1 stages stay in flight behind a counted vmcnt;
 // the pipeline runs across output-channel passes.
-__device__ __attribute__((aligned(16))) float irm_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
-
-template <int N>
-__device__ __forceinline__ void cv_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int CT, int NS>
 __global__ __launch_bounds__(256, 2) void conv3x3_ring_kernel(ConvArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int XU = 8;                          // 1 KiB units of the input image per stage (400 chunks + pad:
                                                    // every wave issues the same number of DMA instructions)
     constexpr int WCH = 9 * CT * 16;               // 16-byte chunks of weights per stage
@@ -304,6 +295,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ring_kernel(ConvArgs a) {
     const int my_chunks = (nchunks - (int)blockIdx.y + (int)gridDim.y - 1) / (int)gridDim.y;
     const int TOT = my_chunks * S;
 
+    const float* const zero_page = irm_zero_page;      // (named here, not inside the lambda: irm_common.h)
     auto issue = [&](int it) {
         const int ci = it / S, s = it - ci * S;
         const int mt0 = ((int)blockIdx.y + ci * (int)gridDim.y) * CT;
@@ -311,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ring_kernel(ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const bool ok = xok[j] && s * 4 + xch[j] < a.Ci;
-            const float* src = ok ? X + (long)s * 4 * plane + xoff[j] : irm_zero_page;
+            const float* src = ok ? X + (long)s * 4 * plane + xoff[j] : zero_page;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)(xb + (wave * 2 + j) * 256),
                                                  16, 0, 0);
@@ -323,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ring_kernel(ConvArgs a) {
             const int pair = qq >> 4, tap = pair / CT, ct = pair - tap * CT;
             const int mt = min(mt0 + ct, a.mtiles - 1);
             const float* src = qq < WCH
-                ? a.Wp + (((long)tap * a.mtiles + mt) * a.ksteps + s) * 64 + (qq & 15) * 4 : irm_zero_page;
+                ? a.Wp + (((long)tap * a.mtiles + mt) * a.ksteps + s) * 64 + (qq & 15) * 4 : zero_page;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(xb + (XU + u) * 256), 16, 0, 0);
         }
@@ -342,8 +334,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ring_kernel(ConvArgs a) {
     int s = 0, ci = 0;
     for (int it = 0; it < TOT; ++it) {
         const int rem = min(NS - 2, TOT - 1 - it);
-        if (rem >= 1 && NS >= 3) cv_wait_vmcnt<LPS>();
-        else cv_wait_vmcnt<0>();
+        if (rem >= 1 && NS >= 3) irm_wait_vmcnt<LPS>();
+        else irm_wait_vmcnt<0>();
         asm volatile("s_barrier" ::: "memory");
         if (it + NS - 1 < TOT) issue(it + NS - 1);
 

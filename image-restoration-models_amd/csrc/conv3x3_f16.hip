@@ -16,7 +16,6 @@
 // ReLU, residual modes, PixelUnshuffle / PixelShuffle folded into the store) is the one of conv3x3.hip.
 #include "irm_common.h"
 
-typedef _Float16 cf_h8 __attribute__((ext_vector_type(8)));
 
 #define CF_TH 8
 #define CF_TW 32
@@ -28,7 +27,6 @@ typedef _Float16 cf_h8 __attribute__((ext_vector_type(8)));
 #define CF_IMGB (CF_NP * CF_PXB)        // 54400
 #define CF_NRAW 7                       // raw DMA instructions per lane and stage (3200 chunks / 512 lanes)
 
-__device__ __attribute__((aligned(16))) float cf_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
 
 __device__ __forceinline__ float cf_res(float v, float r, int mode) {
     if (mode == 1) return v + r;
@@ -49,8 +47,6 @@ struct ConvF16Args {
     int ps_r;                     // PixelShuffle factor of store_mode 2: 2, 3 or 4
 };
 
-template <int N>
-__device__ __forceinline__ void cf_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // NCH (round 3): a pass covers NCH chunks of CT output tiles (accumulators for all of them in registers: 8 CT NCH), so the
 // input tile of a stage is fetched and converted ONCE per NCH x CT output tiles instead of once per CT - the up-sampling
@@ -58,7 +54,6 @@ __device__ __forceinline__ void cf_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(
 // tap group still cover CT tiles (the LDS bound): NCH x 3 groups per stage instead of 3.
 template <int CT, int NCH = 1>
 __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
-    IRM_KERNEL_ENTRY();
     constexpr int TT = CT * NCH;                   // output tiles per pass
     constexpr int NG = 3 * NCH;                    // weight groups per stage
     constexpr int WGB = 3 * CT * 2048;             // bytes of the weights of one tap group (3 taps)
@@ -92,11 +87,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
         xok[j] = q < 3200 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
         xoff[j] = (long)ch * plane + (long)gy * a.W + gx;
     }
+    const float* const zero_page = irm_zero_page;      // (named here, not inside the lambda: irm_common.h)
     auto issue_raw = [&](int s) {
 #pragma unroll
         for (int j = 0; j < CF_NRAW; ++j) {
             const bool ok = xok[j] && s * 32 + xch[j] < a.Ci;
-            const float* src = ok ? X + (long)s * 32 * plane + xoff[j] : cf_zero_page;
+            const float* src = ok ? X + (long)s * 32 * plane + xoff[j] : zero_page;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(raw + (j * 512 + wave * 64) * 16), 16, 0, 0);
         }
@@ -130,7 +126,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
         issue_raw(0);
         issue_w(mt0, 0);
         for (int s = 0; s < S; ++s) {
-            cf_wait_vmcnt<0>();
+            irm_wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();                                    // raw(s), W(3 s) landed; image free
             // ---- fp32 planes -> channel-minor fp16 hi / lo image
 #pragma unroll
@@ -140,13 +136,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
                     const int cg = item / CF_NP, px = item - cg * CF_NP;
                     const int row = px / CF_HC, col = px - row * CF_HC;
                     const float* rp = reinterpret_cast<const float*>(raw) + (8 * cg) * CF_PLANE + row * 40 + col + 3;
-                    cf_h8 hi, lo;
+                    irm_h8 hi, lo;
                     float xs[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) xs[e] = irm_sat_h(__fmul_rn(rp[e * CF_PLANE], 0.0625f));
                     irm_split8(xs, hi, lo);                                  // one rounded value for hi and lo (irm_common.h)
-                    *reinterpret_cast<cf_h8*>(img + px * CF_PXB + cg * 16) = hi;
-                    *reinterpret_cast<cf_h8*>(img + px * CF_PXB + 64 + cg * 16) = lo;
+                    *reinterpret_cast<irm_h8*>(img + px * CF_PXB + cg * 16) = hi;
+                    *reinterpret_cast<irm_h8*>(img + px * CF_PXB + 64 + cg * 16) = lo;
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -158,11 +154,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
             for (int gi = 0; gi < NG; ++gi) {
                 const int n = NG * s + gi, tg = gi % 3, chn = gi / 3;
                 if (gi == 1) {
-                    if (s + 1 < S) cf_wait_vmcnt<CF_NRAW>(); else cf_wait_vmcnt<0>();      // group n landed (raw may be in flight)
+                    if (s + 1 < S) irm_wait_vmcnt<CF_NRAW>(); else irm_wait_vmcnt<0>();      // group n landed (raw may be in flight)
                     __builtin_amdgcn_s_barrier();                                          // everybody is done with group n - 1
                     issue_w(mt0, n + 1);
                 } else if (gi > 1) {
-                    cf_wait_vmcnt<0>();
+                    irm_wait_vmcnt<0>();
                     __builtin_amdgcn_s_barrier();
                     if (gi + 1 < NG || s + 1 < S) issue_w(mt0, n + 1);
                 }
@@ -170,23 +166,21 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
 #pragma unroll
                 for (int tl = 0; tl < 3; ++tl) {
                     const int dy = tg, dx = tl;
-                    cf_h8 ah[2], al[2];
+                    irm_h8 ah[2], al[2];
 #pragma unroll
                     for (int p = 0; p < 2; ++p) {
                         const int pi = (wave + dy) * CF_HC + 16 * p + r + dx;
-                        ah[p] = *reinterpret_cast<const cf_h8*>(img + pi * CF_PXB + 16 * g);
-                        al[p] = *reinterpret_cast<const cf_h8*>(img + pi * CF_PXB + 64 + 16 * g);
+                        ah[p] = *reinterpret_cast<const irm_h8*>(img + pi * CF_PXB + 16 * g);
+                        al[p] = *reinterpret_cast<const irm_h8*>(img + pi * CF_PXB + 64 + 16 * g);
                     }
 #pragma unroll
                     for (int c = 0; c < CT; ++c) {
-                        const cf_h8 wh = *reinterpret_cast<const cf_h8*>(wb + ((c * 3 + tl) * 2) * 1024 + lane * 16);
-                        const cf_h8 wl = *reinterpret_cast<const cf_h8*>(wb + ((c * 3 + tl) * 2 + 1) * 1024 + lane * 16);
+                        const irm_h8 wh = *reinterpret_cast<const irm_h8*>(wb + ((c * 3 + tl) * 2) * 1024 + lane * 16);
+                        const irm_h8 wl = *reinterpret_cast<const irm_h8*>(wb + ((c * 3 + tl) * 2 + 1) * 1024 + lane * 16);
 #pragma unroll
                         for (int p = 0; p < 2; ++p) {
                             f32x4& t = acc[p][chn * CT + c];
-                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[p], wh, t, 0, 0, 0);
-                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[p], wl, t, 0, 0, 0);
-                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[p], wh, t, 0, 0, 0);
+                            t = irm_mfma3_f16(ah[p], al[p], wh, wl, t);
                         }
                     }
                 }

@@ -12,8 +12,6 @@
 // activations live only in registers.
 #include "irm_common.h"
 
-__device__ __attribute__((aligned(16))) float dg_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
-
 struct DwGemmArgs {
     const float* Wp; long w_bs;        // packed [mtiles][ksteps][64] (per sample when w_bs != 0)
     const float* dwp;                  // [4*S][DWS] depth-wise coefficients, see irm_hip.h
@@ -24,11 +22,6 @@ struct DwGemmArgs {
     float* stats_out; float eps;
     int M, K, H, W, mtiles, ksteps, tiles_x, tiles;
 };
-
-template <int N>
-__device__ __forceinline__ void dg_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // LayerNorm statistics of the finished output pixels (same contract as irm_stats_from_acc in gemm_pw.hip):
 // lane (g, j) holds channel 16c + j of PT pixel quads; pix[q] < 0 marks a quad outside the image.
@@ -87,46 +80,26 @@ __device__ __forceinline__ void dg_stats(const float4 (&t)[PT][CT], int M, long 
     }
 }
 
-typedef float v2f __attribute__((ext_vector_type(2)));
-
 // Packed-fp32 (v_pk_fma_f32) stencil: PT+2 rows x 3 columns around PT vertically neighbouring pixels, the
 // outputs as register pairs (o0,o1)[, (o2,o3)].  kk[t] holds tap t twice (k,k); bias first, then the taps row
 // by row, as dw_apply in elementwise.hip.  Lanes of a wave read consecutive columns of the halo image: no LDS
 // bank conflicts.
 template <int PT, int RF>
-__device__ __forceinline__ void dg_stencil(const float* img, const v2f (&kk)[9], v2f bias, v2f (&o)[PT / 2]) {
-    v2f rp[PT + 1][3];                             // rp[d][dx] = rows d and d+1 at column dx
+__device__ __forceinline__ void dg_stencil(const float* img, const irm_v2 (&kk)[9], irm_v2 bias, irm_v2 (&o)[PT / 2]) {
+    irm_v2 rp[PT + 1][3];                             // rp[d][dx] = rows d and d+1 at column dx
 #pragma unroll
     for (int d = 0; d < PT + 1; ++d)
 #pragma unroll
-        for (int dx = 0; dx < 3; ++dx) rp[d][dx] = (v2f){img[d * RF + dx], img[(d + 1) * RF + dx]};
+        for (int dx = 0; dx < 3; ++dx) rp[d][dx] = (irm_v2){img[d * RF + dx], img[(d + 1) * RF + dx]};
 #pragma unroll
     for (int h = 0; h < PT / 2; ++h) {
-        v2f s = bias;
+        irm_v2 s = bias;
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
             for (int dx = 0; dx < 3; ++dx) s = kk[dy * 3 + dx] * rp[2 * h + dy][dx] + s;
         o[h] = s;
     }
-}
-
-// GELU with erf from Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 rounding level): branch free,
-// packed fp32 except the two transcendentals per element; the kernel is VALU bound on this function.
-__device__ __forceinline__ v2f dg_gelu2(v2f x) {
-    const v2f z = __builtin_elementwise_abs(x) * 0.70710678118654752440f;
-    const v2f d = z * 0.3275911f + 1.0f;
-    const v2f t = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-    v2f p = t * 1.061405429f + -1.453152027f;
-    p = p * t + 1.421413741f;
-    p = p * t + -0.284496736f;
-    p = p * t + 0.254829592f;
-    const v2f q = z * z * -1.4426950408889634f;
-    const v2f e = p * t * (v2f){__builtin_amdgcn_exp2f(q.x), __builtin_amdgcn_exp2f(q.y)};   // 1 - erf(|z|)
-    const v2f w = 1.0f - e;
-    const v2f sg = {copysignf(w.x, x.x), copysignf(w.y, x.y)};
-    const v2f h = x * 0.5f;
-    return sg * h + h;
 }
 
 // PT = pixels per lane: 4 -> 4 waves, each a 4 x 16 patch; 2 -> 8 waves, each a 2 x 16 patch (half the
@@ -137,14 +110,12 @@ __device__ __forceinline__ v2f dg_gelu2(v2f x) {
 // every 4th stage three MFMAs per tile (lo*hi, hi*lo, hi*hi) accumulate in fp32.  The split weights of a
 // 16-channel group (host packed: irm_gemm1x1_f16x3_f32's order) arrive in quarters with the 4 stages through one
 // extra, partly masked DMA instruction per wave and stage, into a double-buffered area next to the ring.
-typedef _Float16 dg_h4 __attribute__((ext_vector_type(4)));
 
 // TW = tile width (32 or 64 pixels; 8 rows): the halo columns cost a 64-byte sector per row and side for one
 // pixel each, so a 64-wide tile (8 waves) moves 1.5x instead of 2x the bytes of its rows
 template <int CT, bool GATE, int NS, int PT, bool F16 = false, int TW = 32>
 __global__ __launch_bounds__((PT == 4 ? 256 : 512) * (TW / 32), TW == 64 ? 1 : (PT == 4 ? (CT <= 3 ? 3 : 2) : 2))
 void dwgemm_kernel(DwGemmArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int CH = TW / 4 + 2;                 // 16-byte chunks per halo row
     constexpr int RF = CH * 4, PL = 10 * RF;       // floats per halo row / plane
     constexpr int NWX = TW / 16;                   // wave columns
@@ -179,6 +150,7 @@ void dwgemm_kernel(DwGemmArgs a) {
     const int SL = F16 ? ((S + 3) & ~3) : S;       // F16: whole 16-channel groups (stages beyond S carry zeros)
     const int groups = a.ksteps >> 2;              // 16-channel groups of the packed weights
 
+    const float* const zero_page = irm_zero_page;      // (named here, not inside the lambda: irm_common.h)
     // per-lane DMA sources: src(s) = s < lim ? base + s * stride : zero page
     const float* base[R];
     long stride[R];
@@ -186,7 +158,7 @@ void dwgemm_kernel(DwGemmArgs a) {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const int q = j * NT + tid;
-        base[j] = dg_zero_page; stride[j] = 0; lim[j] = 0;
+        base[j] = zero_page; stride[j] = 0; lim[j] = 0;
         if (q < XC) {
             const int pl = q / (10 * CH), rem = q - pl * (10 * CH), row = rem / CH, chunk = rem - row * CH;
             const int gy = ty0 - 1 + row, gx = tx0 - 4 + chunk * 4;
@@ -218,7 +190,7 @@ void dwgemm_kernel(DwGemmArgs a) {
         const bool tail = ragged && s >= S - 1;
 #pragma unroll
         for (int j = 0; j < R; ++j) {
-            const float* src = (tail && s >= lim[j]) ? dg_zero_page : base[j];
+            const float* src = (tail && s >= lim[j]) ? zero_page : base[j];
             base[j] += stride[j];
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(dst + j * NT * 4), 16, 0, 0);
@@ -228,7 +200,7 @@ void dwgemm_kernel(DwGemmArgs a) {
             if (lane < LW) {
                 const int cq = wave * LW + lane, ct = cq >> 4;
                 const float* src = ct < a.mtiles
-                    ? Wp + ((long)ct * groups + (s >> 2)) * 256 + (s & 3) * 64 + (cq & 15) * 4 : dg_zero_page;
+                    ? Wp + ((long)ct * groups + (s >> 2)) * 256 + (s & 3) * 64 + (cq & 15) * 4 : zero_page;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                     (__attribute__((address_space(3))) void*)(warea + ((s >> 2) & 1) * (CT * 256) + (s & 3) * (CT * 64) +
                                                               wave * (LW * 4)), 16, 0, 0);
@@ -276,27 +248,27 @@ void dwgemm_kernel(DwGemmArgs a) {
     float ag[4][PT];                               // F16: stencil outputs of the 4 stages of a group
     for (int s = 0; s < SL; ++s) {
         const int rem = min(NS - 2, SL - 1 - s);
-        if (rem >= NS - 2 && NS >= 3) dg_wait_vmcnt<(NS - 2) * RW>();
-        else dg_wait_vmcnt<0>();
+        if (rem >= NS - 2 && NS >= 3) irm_wait_vmcnt<(NS - 2) * RW>();
+        else irm_wait_vmcnt<0>();
         asm volatile("s_barrier" ::: "memory");
         if (s + NS - 1 < SL) issue(s + NS - 1);
 
         const float* xb = smem + (s % NS) * STG;
         const float* wb = xb + XC * 4;
-        const v2f* dk = reinterpret_cast<const v2f*>(wb + WC * 4 + g * DWS);
+        const irm_v2* dk = reinterpret_cast<const irm_v2*>(wb + WC * 4 + g * DWS);
         float af[PT];
         {
-            v2f ka[9], oa[PT / 2];
+            irm_v2 ka[9], oa[PT / 2];
 #pragma unroll
             for (int t = 0; t < 9; ++t) ka[t] = dk[t];
             dg_stencil<PT, RF>(xb + img_off, ka, dk[9], oa);
             if (GATE) {
-                v2f kb[9], ob[PT / 2];
+                irm_v2 kb[9], ob[PT / 2];
 #pragma unroll
                 for (int t = 0; t < 9; ++t) kb[t] = dk[10 + t];
                 dg_stencil<PT, RF>(xb + img_off + 4 * PL, kb, dk[19], ob);
 #pragma unroll
-                for (int h = 0; h < PT / 2; ++h) oa[h] = dg_gelu2(oa[h]) * ob[h];
+                for (int h = 0; h < PT / 2; ++h) oa[h] = irm_gelu2(oa[h]) * ob[h];
             }
             #pragma unroll
             for (int h = 0; h < PT / 2; ++h) { af[2 * h] = oa[h].x; af[2 * h + 1] = oa[h].y; }
@@ -309,7 +281,7 @@ void dwgemm_kernel(DwGemmArgs a) {
 #pragma unroll
                 for (int p = 0; p < PT; ++p) ag[j][p] = j4 == j ? af[p] : (j4 < j ? 0.0f : ag[j][p]);
             if (j4 == 3) {
-                dg_h4 ah[PT], al[PT];
+                irm_h4 ah[PT], al[PT];
 #pragma unroll
                 for (int p = 0; p < PT; ++p)
 #pragma unroll
@@ -319,11 +291,11 @@ void dwgemm_kernel(DwGemmArgs a) {
                         al[p][j] = (_Float16)(x - (float)ah[p][j]);
                     }
                 const float* wa = warea + ((s >> 2) & 1) * (CT * 256) + (lane >> 5) * (CT * 64) + (lane & 31) * 2;
-                dg_h4 bh[CT], bl[CT];
+                irm_h4 bh[CT], bl[CT];
 #pragma unroll
                 for (int c = 0; c < CT; ++c) {
-                    bh[c] = *reinterpret_cast<const dg_h4*>(wa + c * 64);
-                    bl[c] = *reinterpret_cast<const dg_h4*>(wa + 2 * (CT * 64) + c * 64);
+                    bh[c] = *reinterpret_cast<const irm_h4*>(wa + c * 64);
+                    bl[c] = *reinterpret_cast<const irm_h4*>(wa + 2 * (CT * 64) + c * 64);
                 }
 #pragma unroll
                 for (int c = 0; c < CT; ++c)

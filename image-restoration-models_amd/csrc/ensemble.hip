@@ -28,7 +28,6 @@ struct ChopArgs {
 };
 
 __global__ __launch_bounds__(256) void dihedral_chop_kernel(ChopArgs a) {
-    IRM_KERNEL_ENTRY();
     __shared__ float tile[ENS_TILE * ENS_LDS_STRIDE];
     const int* t = a.tab + (8 + (int)blockIdx.y) * ENS_TAB;
     const int e = t[0], y0 = t[1], x0 = t[2], ph = t[3], pw = t[4], off = t[5];
@@ -123,7 +122,6 @@ struct EnsAxis {
 // ((m0 + m1) + (m2 + m3)) + ((m4 + m5) + (m6 + m7)) - a fixed order, and every partial sum of 8 EQUAL values is exact
 // (2x, 4x, 8x), so an equivariant network gives back its single forward bit for bit - then x 0.125.
 __global__ __launch_bounds__(256) void ensemble_merge_kernel(MergeArgs a) {
-    IRM_KERNEL_ENTRY();
     __shared__ float tile[ENS_TILE * ENS_LDS_STRIDE];
     const int s = a.s, sH = s * a.H, sW = s * a.W;
     const int tiles_x = (sW + ENS_TILE - 1) / ENS_TILE;

@@ -21,10 +21,6 @@
 // {4-11} at g + 1 - then touch 16 different bank quads.
 // Whole tiles only (H % 8 == 0, W % 32 == 0), C % 16 == 0, M = 3 C; q, k tile-major, v channel-last or planar.
 #include "irm_common.h"
-#include <utility>
-
-typedef _Float16 qc_h8 __attribute__((ext_vector_type(8)));
-typedef float qc_v2 __attribute__((ext_vector_type(2)));
 
 #define QC_TH 8
 #define QC_TW 32
@@ -49,30 +45,6 @@ struct QcArgs {
 };
 #define QC_NCH 4
 
-typedef __attribute__((address_space(3))) char qc_lc;
-__device__ __forceinline__ unsigned qc_opaque(unsigned v) { asm volatile("" : "+v"(v)); return v; }
-template <typename T>
-__device__ __forceinline__ T qc_ld(const qc_lc* base, unsigned voff, int imm) {
-    return *reinterpret_cast<const __attribute__((address_space(3))) T*>(base + voff + imm);
-}
-template <typename T>
-__device__ __forceinline__ void qc_st(qc_lc* base, unsigned voff, int imm, T v) {
-    *reinterpret_cast<__attribute__((address_space(3))) T*>(base + voff + imm) = v;
-}
-template <int NP>
-__device__ __forceinline__ void qc_dma(const float* src, float* dst, int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < (NP + 7) / 8; ++i) {
-        const int pc = wave + 8 * i;
-        if (pc < NP)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + pc * 256 + lane * 4),
-                                             (__attribute__((address_space(3))) void*)(dst + pc * 256), 16, 0, 0);
-    }
-}
-template <class F, int... Is>
-__device__ __forceinline__ void qc_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void qc_for(F&& f) { qc_for_impl(f, std::make_integer_sequence<int, N>{}); }
 // byte offset of channel row c (0 .. 31) inside an image
 __device__ __forceinline__ unsigned qc_row(int c) {
     const int i = c & 15;
@@ -93,7 +65,6 @@ __device__ __forceinline__ unsigned qc_row(int c) {
 // 36 accumulator + 24 operand registers here; c = 96 needs 144 + 48 (two heads of 48: 72 + 48) beside 72 of resident input.
 template <int KS, bool GRAM = false>
 __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
-    IRM_KERNEL_ENTRY();
     static_assert(!GRAM || KS == 2, "GRAM: C = 48");
     constexpr int W1F = KS * 1024, RECF = W1F + 512, RECP = KS * 4 + 2;
     constexpr int SLOT_B = RECF * 4, CF_OFF = W1F * 4;
@@ -101,7 +72,7 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
     static_assert(PL_OFF % 16 == 0 && PL_OFF + 2 * QC_IMG <= 160 * 1024, "LDS");
     static_assert(15 * 16 + 368 * 4 <= QC_CS, "row + phase shift inside the row stride");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    qc_lc* lds = (qc_lc*)smem;
+    irm_lc* lds = (irm_lc*)smem;
     float* slots = smem;
 
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -138,7 +109,7 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
         const int ty0 = (tile / a.tiles_x) * QC_TH, tx0 = (tile % a.tiles_x) * QC_TW;
         float* Y = a.Y + (long)b * a.y_bs;
         const int nitem = item_of(round + 1);
-        const unsigned vw = qc_opaque((unsigned)(lane * 16));
+        const unsigned vw = irm_opaque((unsigned)(lane * 16));
 
         // ------------------------------------------------------------ input: lane (r, g) -> pixel slot 16 (wave + 8 j) + r
         bool inside[3];
@@ -189,12 +160,12 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
         constexpr bool PREFETCH = KS <= 2 && !GRAM;
         if (round == 0) load_x(item);
         // the previous item's last barrier has passed: every LDS region is free.  Record k lives in slot k % 3.
-        qc_dma<RECP>(a.rec, slots, wave, lane);
-        qc_dma<RECP>(a.rec + RECF, slots + RECF, wave, lane);
-        if (S >= 2) qc_dma<RECP>(a.rec + 2 * RECF, slots + 2 * RECF, wave, lane);
+        irm_dma<RECP>(a.rec, slots, wave, lane);
+        irm_dma<RECP>(a.rec + RECF, slots + RECF, wave, lane);
+        if (S >= 2) irm_dma<RECP>(a.rec + 2 * RECF, slots + 2 * RECF, wave, lane);
 
         // ------------------------------------------------------------ LayerNorm + fp16 split (as fused_block.hip)
-        qc_h8 xh[3][KS], xl[3][KS];
+        irm_h8 xh[3][KS], xl[3][KS];
         // (FULL: C == 32 KS, no channel masks - the same expressions as lnpw_dw_fused_kernel's specialised copies, so that the
         // compiler contracts the same multiply-adds and the two kernels stay bit-identical)
         auto ln_phase = [&](auto FULL_, auto WBK_) {
@@ -244,8 +215,8 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
                 // zero-pads h) for the lanes that will hold this pixel's h values: through LDS
                 if (g == 0 && wave + 8 * j < QC_PT) {
                     const int p = 16 * (wave + 8 * j) + r;
-                    qc_st<float>(lds, (unsigned)(OSC_OFF + p * 4), 0, inside[j] ? oscj : 0.f);
-                    qc_st<float>(lds, (unsigned)(MSK_OFF + p * 4), 0, inside[j] ? 1.f : 0.f);
+                    irm_st<float>(lds, (unsigned)(OSC_OFF + p * 4), 0, inside[j] ? oscj : 0.f);
+                    irm_st<float>(lds, (unsigned)(MSK_OFF + p * 4), 0, inside[j] ? 1.f : 0.f);
                 }
             }
         };
@@ -264,12 +235,12 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const unsigned po = (unsigned)((16 * min(wave + 8 * j, QC_PT - 1) + 4 * g) * 4);
-            osc4[j] = qc_ld<f32x4>(lds, po, OSC_OFF);
-            msk4[j] = qc_ld<f32x4>(lds, po, MSK_OFF);
+            osc4[j] = irm_ld<f32x4>(lds, po, OSC_OFF);
+            msk4[j] = irm_ld<f32x4>(lds, po, MSK_OFF);
         }
 
         // one stage of the 1x1 conv: 32 channels (2 tiles) for this wave's 3 pixel tiles -> image img
-        const unsigned vrow0 = qc_opaque(qc_row(r)), vrow1 = qc_opaque(qc_row(16 + r));
+        const unsigned vrow0 = irm_opaque(qc_row(r)), vrow1 = irm_opaque(qc_row(16 + r));
         auto gemm1h = [&](int slot, int img, int hct) {
             {
                 f32x4 acc[3];
@@ -277,8 +248,8 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
                 for (int j = 0; j < 3; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
-                    const qc_h8 bh = qc_ld<qc_h8>(lds, vw, slot * SLOT_B + ((hct * KS + ks) * 2) * 1024);
-                    const qc_h8 bl = qc_ld<qc_h8>(lds, vw, slot * SLOT_B + ((hct * KS + ks) * 2 + 1) * 1024);
+                    const irm_h8 bh = irm_ld<irm_h8>(lds, vw, slot * SLOT_B + ((hct * KS + ks) * 2) * 1024);
+                    const irm_h8 bl = irm_ld<irm_h8>(lds, vw, slot * SLOT_B + ((hct * KS + ks) * 2 + 1) * 1024);
 #pragma unroll
                     for (int j = 0; j < 3; ++j) {
                         // (the product order of lnpw_dw_fused_kernel: W_lo x_hi, W_hi x_lo, W_hi x_hi - bit-identical sums)
@@ -287,7 +258,7 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
                         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh[j][ks], bh, acc[j], 0, 0, 0);
                     }
                 }
-                const float b1 = qc_ld<float>(lds, (unsigned)(r * 4), slot * SLOT_B + CF_OFF + 320 * 4 + hct * 64);
+                const float b1 = irm_ld<float>(lds, (unsigned)(r * 4), slot * SLOT_B + CF_OFF + 320 * 4 + hct * 64);
                 const unsigned vr = hct ? vrow1 : vrow0;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
@@ -295,7 +266,7 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
                         f32x4 h;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) h[e] = fmaf(acc[j][e], osc4[j][e], b1 * msk4[j][e]);
-                        qc_st<f32x4>(lds, vr + (unsigned)((16 * (wave + 8 * j) + 4 * g) * 4), PL_OFF + img * QC_IMG, h);
+                        irm_st<f32x4>(lds, vr + (unsigned)((16 * (wave + 8 * j) + 4 * g) * 4), PL_OFF + img * QC_IMG, h);
                     }
                 }
             }
@@ -305,21 +276,21 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
         // the reads of one (16-channel tile, row) unit: issued BEFORE the 1x1 conv of the same channel tile of the next stage, so
         // that their LDS latency passes under its MFMAs; used by the FMAs behind it
         f32x4 sp0[3], sp1[3];
-        qc_v2 sp2[3];
+        irm_v2 sp2[3];
         float stap[10];
         auto st_read = [&](int slot, int img, int hct) {
             const unsigned vr = (hct ? vrow1 : vrow0) + (unsigned)((wave * QC_PITCH + 8 * g) * 4);
             const unsigned vt = (unsigned)((16 * hct + r) * 4);
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
-                sp0[dy] = qc_ld<f32x4>(lds, vr, PL_OFF + img * QC_IMG + dy * QC_PITCH * 4);
-                sp1[dy] = qc_ld<f32x4>(lds, vr, PL_OFF + img * QC_IMG + dy * QC_PITCH * 4 + 16);
-                sp2[dy] = qc_ld<qc_v2>(lds, vr, PL_OFF + img * QC_IMG + dy * QC_PITCH * 4 + 32);
+                sp0[dy] = irm_ld<f32x4>(lds, vr, PL_OFF + img * QC_IMG + dy * QC_PITCH * 4);
+                sp1[dy] = irm_ld<f32x4>(lds, vr, PL_OFF + img * QC_IMG + dy * QC_PITCH * 4 + 16);
+                sp2[dy] = irm_ld<irm_v2>(lds, vr, PL_OFF + img * QC_IMG + dy * QC_PITCH * 4 + 32);
             }
 #pragma unroll
-            for (int t = 0; t < 10; ++t) stap[t] = qc_ld<float>(lds, vt, slot * SLOT_B + CF_OFF + t * 128);
+            for (int t = 0; t < 10; ++t) stap[t] = irm_ld<float>(lds, vt, slot * SLOT_B + CF_OFF + t * 128);
         };
-        qc_h8 gqh[GRAM ? 3 : 1], gql[GRAM ? 3 : 1];      // GRAM: the wave's q tiles as MFMA operands (this tile's 32 pixels of row w)
+        irm_h8 gqh[GRAM ? 3 : 1], gql[GRAM ? 3 : 1];      // GRAM: the wave's q tiles as MFMA operands (this tile's 32 pixels of row w)
         auto st_comp = [&](int st, int hct, auto UC) {
             {
                 constexpr int U = decltype(UC)::value;             // GRAM: 16-channel tile index 2 st + hct at compile time
@@ -346,7 +317,7 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
                     float nn = 0.f, xs[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { nn = fmaf(o[e], o[e], nn); xs[e] = o[e] * sc; }
-                    qc_h8 hi, lo;
+                    irm_h8 hi, lo;
                     irm_split8(xs, hi, lo);
                     if constexpr (U < 3) {
                         gnq[U] += nn; gqh[U] = hi; gql[U] = lo;
@@ -355,9 +326,7 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
 #pragma unroll
                         for (int x = 0; x < 3; ++x) {
                             f32x4& t = gacc[x][U - 3];
-                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(gql[x], hi, t, 0, 0, 0);
-                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(gqh[x], lo, t, 0, 0, 0);
-                            t = __builtin_amdgcn_mfma_f32_16x16x32_f16(gqh[x], hi, t, 0, 0, 0);
+                            t = irm_mfma3_f16(gqh[x], gql[x], hi, lo, t);
                         }
                     }
                     return;
@@ -392,11 +361,11 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
             // C = 48: S = 5 stages, unrolled (the role of a unit - q, k or v tile - is a compile-time property here); the next
             // item's input is requested in the last iteration (the Gram operands and accumulators take the registers the early
             // request would need)
-            qc_for<5>([&](auto ITC) {
+            irm_for<5>([&](auto ITC) {
                 constexpr int it = decltype(ITC)::value;
                 constexpr int s1c = (it + 1) % 3, s3c = it % 3;
                 if constexpr (it + 1 < 5) {
-                    if constexpr (it + 3 <= 5) qc_dma<RECP>(a.rec + (long)(it + 3) * RECF, slots + s3c * RECF, wave, lane);
+                    if constexpr (it + 3 <= 5) irm_dma<RECP>(a.rec + (long)(it + 3) * RECF, slots + s3c * RECF, wave, lane);
                     st_read(s1c, it & 1, 0); gemm1h(s1c, (it + 1) & 1, 0); st_comp(it, 0, std::integral_constant<int, 2 * it>{});
                     st_read(s1c, it & 1, 1); gemm1h(s1c, (it + 1) & 1, 1); st_comp(it, 1, std::integral_constant<int, 2 * it + 1>{});
                     if constexpr (it + 3 <= 5) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -414,15 +383,9 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
         int s1 = 1, s3 = 0;                                              // slots of record it + 1 / it + 3
         for (int it = 0; it + 1 < S; ++it) {
             const bool dma = it + 3 <= S;
-            if (dma) qc_dma<RECP>(a.rec + (long)(it + 3) * RECF, slots + s3 * RECF, wave, lane);
-#ifdef QC_NO_PIPE
-            gemm1h(s1, (it + 1) & 1, 0); gemm1h(s1, (it + 1) & 1, 1);
-            st_read(s1, it & 1, 0); st_comp(it, 0, NOU);
-            st_read(s1, it & 1, 1); st_comp(it, 1, NOU);
-#else
+            if (dma) irm_dma<RECP>(a.rec + (long)(it + 3) * RECF, slots + s3 * RECF, wave, lane);
             st_read(s1, it & 1, 0); gemm1h(s1, (it + 1) & 1, 0); st_comp(it, 0, NOU);
             st_read(s1, it & 1, 1); gemm1h(s1, (it + 1) & 1, 1); st_comp(it, 1, NOU);
-#endif
             if (it <= it_pf) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // (the stage's stores included)
             else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (PREFETCH && it == it_pf) { load_x(min(nitem, a.items - 1)); __builtin_amdgcn_sched_barrier(0); }

@@ -18,19 +18,6 @@
 // v_mfma_f32_16x16x32_f16 per product, CT = C / 16 = 12 accumulator tiles x 2 rows per wave) are that kernel's.  The block's
 // residual is read and written in place in the epilogue (a tile reads h with its halo, x only inside the tile).
 #include "irm_common.h"
-#include <utility>
-
-typedef _Float16 ft_h8 __attribute__((ext_vector_type(8)));
-typedef unsigned ft_u4 __attribute__((ext_vector_type(4)));
-
-#define FT_TH 8
-#define FT_TW 32
-#define FT_HC (FT_TW + 2)
-#define FT_NP ((FT_TH + 2) * FT_HC)       // 340 halo pixels
-#define FT_PS 40                          // floats per pixel of the LDS image
-#define FT_PLF ((FT_NP + 16) * FT_PS)     // + 16 junk pixels (lanes without a pixel park there)
-
-__device__ __attribute__((aligned(16))) float ft_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
 
 struct TailArgs {
     const float* Hh; long h_bs;           // [B][tiles][CB / 64][256][64]
@@ -43,72 +30,16 @@ struct TailArgs {
     int tiles_x, tiles, items, gpx;
 };
 
-// gelu(x) = max(x, 0) - 0.5 |x| erfc(|x| / sqrt 2), Abramowitz-Stegun 7.1.26 with folded constants (fused_block.hip)
-__device__ __forceinline__ float ft_gelu1(float x) {
-    constexpr double CU = 0.84932180028801904272;
-    constexpr double F = 0.5 / CU;
-    constexpr float k = (float)(0.3275911 / 1.2011224087864498);
-    constexpr float a1 = (float)(0.254829592 * F), a2 = (float)(-0.284496736 * F), a3 = (float)(1.421413741 * F),
-                    a4 = (float)(-1.453152027 * F), a5 = (float)(1.061405429 * F);
-    const float u = fabsf(x) * (float)CU;
-    const float t = __builtin_amdgcn_rcpf(fmaf(u, k, 1.0f));
-    float p = fmaf(t, a5, a4);
-    p = fmaf(p, t, a3);
-    p = fmaf(p, t, a2);
-    p = fmaf(p, t, a1);
-    const float w = (p * t) * __builtin_amdgcn_exp2f(-u * u);
-    return fmaf(-u, w, __builtin_amdgcn_fmed3f(x, 0.0f, 3.0e38f));
-}
-
-typedef __attribute__((address_space(3))) char ft_lc;
-__device__ __forceinline__ unsigned ft_opaque(unsigned v) { asm volatile("" : "+v"(v)); return v; }
-template <typename T>
-__device__ __forceinline__ T ft_ld(const ft_lc* base, unsigned voff, int imm) {
-    return *reinterpret_cast<const __attribute__((address_space(3))) T*>(base + voff + imm);
-}
-template <typename T>
-__device__ __forceinline__ void ft_st(ft_lc* base, unsigned voff, int imm, T v) {
-    *reinterpret_cast<__attribute__((address_space(3))) T*>(base + voff + imm) = v;
-}
-template <int IMM, typename T>
-__device__ __forceinline__ void ft_dsr(T& d, unsigned voff) {
-    static_assert(sizeof(T) == 16 && IMM >= 0 && IMM < 65536, "ds_read_b128");
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(voff), "n"(IMM) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ft_waitcnt() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-template <typename T>
-__device__ __forceinline__ void ft_tie1(T& r) { asm volatile("" : "+v"(r)); }
-template <typename... T>
-__device__ __forceinline__ void ft_tie(T&... r) { (ft_tie1(r), ...); }
-template <int I> using ft_ic = std::integral_constant<int, I>;
-template <class F, int... Is>
-__device__ __forceinline__ void ft_for_impl(F&& f, std::integer_sequence<int, Is...>) { (f(ft_ic<Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void ft_for(F&& f) { ft_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
-template <int NP>
-__device__ __forceinline__ void ft_dma(const float* src, float* dst, int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < (NP + 7) / 8; ++i) {
-        const int pc = wave + 8 * i;
-        if (pc < NP)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + pc * 256 + lane * 4),
-                                             (__attribute__((address_space(3))) void*)(dst + pc * 256), 16, 0, 0);
-    }
-}
-
 template <int CT>
 __global__ __launch_bounds__(512, 2) void gdfn_tail_kernel(TailArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int RECF = 512;                      // floats per tap record
     constexpr int W2F = CT * 512, W2P = CT * 2;
-    constexpr int SLOT_B = RECF * 4, W2_OFF = 2 * SLOT_B, PL_OFF = W2_OFF + W2F * 4, PL_B = FT_PLF * 4;
+    constexpr int SLOT_B = RECF * 4, W2_OFF = 2 * SLOT_B, PL_OFF = W2_OFF + W2F * 4, PL_B = IRM_PLF * 4;
     constexpr int PARK_OFF = PL_OFF + 2 * PL_B;
-    constexpr int NK = (FT_NP * 8 + 511) / 512;    // 16-byte pieces per lane and stage (6; the last one partly)
+    constexpr int NK = (IRM_NP * 8 + 511) / 512;    // 16-byte pieces per lane and stage (6; the last one partly)
     static_assert(PARK_OFF + 8192 <= 160 * 1024, "LDS");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    ft_lc* lds = (ft_lc*)smem;
+    irm_lc* lds = (irm_lc*)smem;
     float* slots = smem;
     float* w2a = smem + W2_OFF / 4;
 
@@ -128,13 +59,13 @@ __global__ __launch_bounds__(512, 2) void gdfn_tail_kernel(TailArgs a) {
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, g = lane >> 4, r = lane & 15;
         const int b = item / a.tiles, tile = item - b * a.tiles;
-        const int ty0 = (tile / a.tiles_x) * FT_TH, tx0 = (tile % a.tiles_x) * FT_TW;
+        const int ty0 = (tile / a.tiles_x) * IRM_TH, tx0 = (tile % a.tiles_x) * IRM_TW;
         const float* Hh = a.Hh + (long)b * a.h_bs;
-        const unsigned vw = ft_opaque((unsigned)(lane * 16));
-        const unsigned vc = ft_opaque((unsigned)(16 * g));
-        const int sp0 = (2 * (wave >> 1)) * FT_HC + 16 * (wave & 1) + r;
-        const unsigned vp0 = ft_opaque((unsigned)(PL_OFF + (sp0 * FT_PS + 4 * g) * 4));
-        const unsigned vp1 = ft_opaque(vp0 + PL_B);
+        const unsigned vw = irm_opaque((unsigned)(lane * 16));
+        const unsigned vc = irm_opaque((unsigned)(16 * g));
+        const int sp0 = (2 * (wave >> 1)) * IRM_HC + 16 * (wave & 1) + r;
+        const unsigned vp0 = irm_opaque((unsigned)(PL_OFF + (sp0 * IRM_PS + 4 * g) * 4));
+        const unsigned vp1 = irm_opaque(vp0 + PL_B);
 
         // this lane's pieces of a stage: piece idx = k 512 + tid -> (halo pixel idx >> 3, 16-byte piece idx & 7: channels
         // 4 (piece & 3) .. + 3 of half piece >> 2).  goff: float offset of the piece in h for stage 0, or -1 (pixel outside the
@@ -144,77 +75,50 @@ __global__ __launch_bounds__(512, 2) void gdfn_tail_kernel(TailArgs a) {
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             const int idx = k * 512 + tid, px = idx >> 3, pc = idx & 7;
-            const int hr = px / FT_HC, hc = px - hr * FT_HC;
+            const int hr = px / IRM_HC, hc = px - hr * IRM_HC;
             const int gy = ty0 - 1 + hr, gx = tx0 - 1 + hc;
-            const bool valid = px < FT_NP, inside = valid && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+            const bool valid = px < IRM_NP, inside = valid && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
             // h: [tile][CB / 64 chunks][256 pixels][64 channels]; the multiplier half starts HP / 64 chunks further on
-            goff[k] = inside ? ((gy >> 3) * a.tiles_x + (gx >> 5)) * 256 * a.CB + ((gy & 7) * FT_TW + (gx & 31)) * 64 + (pc & 3) * 4 +
+            goff[k] = inside ? ((gy >> 3) * a.tiles_x + (gx >> 5)) * 256 * a.CB + ((gy & 7) * IRM_TW + (gx & 31)) * 64 + (pc & 3) * 4 +
                                (pc >> 2) * (a.HP / 64) * (256 * 64)
                              : -1;
-            loff[k] = (unsigned)(PL_OFF + ((valid ? px : FT_NP + (tid & 15)) * FT_PS) * 4 + (pc & 3) * 16 + (pc >> 2) * 64);
+            loff[k] = (unsigned)(PL_OFF + ((valid ? px : IRM_NP + (tid & 15)) * IRM_PS) * 4 + (pc & 3) * 16 + (pc >> 2) * 64);
         }
         f32x4 hreg[NK];
+        const float* const zero_page = irm_zero_page;      // (named here, not inside the lambda: irm_common.h)
         auto load_h = [&](int s) {
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
-#ifdef FT_NO_LOAD                                  // (diagnostic: the kernel without its HBM reads of h)
-                const float* src = ft_zero_page;
-#else
-                const float* src = goff[k] >= 0 ? Hh + goff[k] + (s >> 2) * (256 * 64) + (s & 3) * 16 : ft_zero_page;
-#endif
+                const float* src = goff[k] >= 0 ? Hh + goff[k] + (s >> 2) * (256 * 64) + (s & 3) * 16 : zero_page;
                 hreg[k] = *reinterpret_cast<const f32x4*>(src);
             }
         };
         auto park_h = [&](int img) {
 #pragma unroll
-            for (int k = 0; k < NK; ++k) ft_st<f32x4>(lds, loff[k], img * PL_B, hreg[k]);
+            for (int k = 0; k < NK; ++k) irm_st<f32x4>(lds, loff[k], img * PL_B, hreg[k]);
         };
 
         const int nitem = item_of(round + 1);
 
         // the previous item's last barrier has passed: every LDS region is free
-        ft_dma<2>(a.rec, slots, wave, lane);                                // taps of stage 0 -> slot 0
-        ft_dma<W2P>(a.w2, w2a, wave, lane);
+        irm_dma<2>(a.rec, slots, wave, lane);                                // taps of stage 0 -> slot 0
+        irm_dma<W2P>(a.w2, w2a, wave, lane);
         load_h(0);
         f32x4 acc2[2][CT];
-        const unsigned vpark = ft_opaque((unsigned)(PARK_OFF + threadIdx.x * 16));
+        const unsigned vpark = irm_opaque((unsigned)(PARK_OFF + threadIdx.x * 16));
 #pragma unroll
         for (int c = 0; c < CT; ++c) { acc2[0][c] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc2[1][c] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        ft_st<f32x4>(lds, vpark, 0, acc2[1][CT - 1]);
+        irm_st<f32x4>(lds, vpark, 0, acc2[1][CT - 1]);
         park_h(0);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
 
         float o[2][2][4];
         f32x4 kprev[3];
-        auto st_comp = [&](int hf, int dy, const f32x4 (&P)[3], const f32x4 (&kc)[3], const f32x4& kb) {
-            if (dy == 0) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[hf][q][e] = kb[e];
-            }
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (dy < 3) o[hf][0][e] = fmaf(kc[dx][e], P[dx][e], o[hf][0][e]);
-                    if (dy > 0) o[hf][1][e] = fmaf(kprev[dx][e], P[dx][e], o[hf][1][e]);
-                }
-            }
-            if (dy < 3) {
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) kprev[dx] = kc[dx];
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(o[hf][q][e]));
-        };
 
-        ft_u4 Gh[2], Gl[2];
+        irm_u4 Gh[2], Gl[2];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) { Gh[q] = (ft_u4){0u, 0u, 0u, 0u}; Gl[q] = (ft_u4){0u, 0u, 0u, 0u}; }
+        for (int q = 0; q < 2; ++q) { Gh[q] = (irm_u4){0u, 0u, 0u, 0u}; Gl[q] = (irm_u4){0u, 0u, 0u, 0u}; }
 
         // iteration it: stencil + gate of stage it (image it & 1, taps in slot it & 1); the pieces of stage it + 1 are requested
         // at its start and parked in the other image at its end; project_out every second stage
@@ -223,9 +127,9 @@ __global__ __launch_bounds__(512, 2) void gdfn_tail_kernel(TailArgs a) {
             constexpr bool more = decltype(MORE)::value;
             if constexpr (more) {
                 load_h(it + 1);
-                ft_dma<2>(a.rec + (long)(it + 1) * RECF, slots + (par ^ 1) * RECF, wave, lane);
+                irm_dma<2>(a.rec + (long)(it + 1) * RECF, slots + (par ^ 1) * RECF, wave, lane);
             }
-            if (par == 0 && it > 0) ft_dma<W2P>(a.w2 + (long)(it >> 1) * W2F, w2a, wave, lane);
+            if (par == 0 && it > 0) irm_dma<W2P>(a.w2 + (long)(it >> 1) * W2F, w2a, wave, lane);
             {
                 const unsigned vp = par ? vp1 : vp0;
                 f32x4 P[2][3], K[2][3], KB[1];
@@ -233,28 +137,28 @@ __global__ __launch_bounds__(512, 2) void gdfn_tail_kernel(TailArgs a) {
                     constexpr int I = decltype(IC)::value, n = decltype(NC)::value;
                     constexpr int hf = I >> 2, dy = I & 3;
                     constexpr int cf = par * SLOT_B + hf * 64;
-                    if constexpr (dy == 0) ft_dsr<cf + 9 * 128>(KB[0], vc);
+                    if constexpr (dy == 0) irm_dsr<cf + 9 * 128>(KB[0], vc);
                     if constexpr (dy < 3) {
-                        ft_dsr<cf + (dy * 3 + 0) * 128>(K[n][0], vc);
-                        ft_dsr<cf + (dy * 3 + 1) * 128>(K[n][1], vc);
-                        ft_dsr<cf + (dy * 3 + 2) * 128>(K[n][2], vc);
+                        irm_dsr<cf + (dy * 3 + 0) * 128>(K[n][0], vc);
+                        irm_dsr<cf + (dy * 3 + 1) * 128>(K[n][1], vc);
+                        irm_dsr<cf + (dy * 3 + 2) * 128>(K[n][2], vc);
                     }
-                    ft_dsr<(dy * FT_HC + 0) * (FT_PS * 4) + hf * 64>(P[n][0], vp);
-                    ft_dsr<(dy * FT_HC + 1) * (FT_PS * 4) + hf * 64>(P[n][1], vp);
-                    ft_dsr<(dy * FT_HC + 2) * (FT_PS * 4) + hf * 64>(P[n][2], vp);
+                    irm_dsr<(dy * IRM_HC + 0) * (IRM_PS * 4) + hf * 64>(P[n][0], vp);
+                    irm_dsr<(dy * IRM_HC + 1) * (IRM_PS * 4) + hf * 64>(P[n][1], vp);
+                    irm_dsr<(dy * IRM_HC + 2) * (IRM_PS * 4) + hf * 64>(P[n][2], vp);
                 };
-                loads(ft_ic<0>{}, ft_ic<0>{});
-                ft_for<8>([&](auto IC) {
+                loads(irm_ic<0>{}, irm_ic<0>{});
+                irm_for<8>([&](auto IC) {
                     constexpr int I = decltype(IC)::value, c = I & 1, n = c ^ 1;
                     constexpr int hf = I >> 2, dy = I & 3;
-                    if constexpr (I + 1 < 8) loads(ft_ic<I + 1>{}, ft_ic<n>{});
+                    if constexpr (I + 1 < 8) loads(irm_ic<I + 1>{}, irm_ic<n>{});
                     constexpr int J = I + 1, jdy = J & 3;
                     constexpr int nnext = J < 8 ? 3 + (jdy < 3 ? 3 : 0) + (jdy == 0 ? 1 : 0) : 0;
-                    ft_waitcnt<nnext>();
-                    ft_tie(P[c][0], P[c][1], P[c][2]);
-                    if constexpr (dy < 3) ft_tie(K[c][0], K[c][1], K[c][2]);
-                    if constexpr (dy == 0) ft_tie(KB[0]);
-                    st_comp(hf, dy, P[c], K[c], KB[0]);
+                    irm_wait_lgkmcnt<nnext>();
+                    irm_tie(P[c][0], P[c][1], P[c][2]);
+                    if constexpr (dy < 3) irm_tie(K[c][0], K[c][1], K[c][2]);
+                    if constexpr (dy == 0) irm_tie(KB[0]);
+                    irm_stencil_step(dy, o[hf], kprev, P[c], K[c], KB[0]);
                     __builtin_amdgcn_sched_barrier(0);
                 });
             }
@@ -263,10 +167,8 @@ __global__ __launch_bounds__(512, 2) void gdfn_tail_kernel(TailArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; e += 2) {
                     // (taps and bias of the second half are pre-scaled by 2^-4 on the host: o[1] = dw(h2) / 16, exact)
-                    const float g0 = irm_sat_h(__fmul_rn(ft_gelu1(o[0][q][e]), o[1][q][e]));
-                    const float g1 = irm_sat_h(__fmul_rn(ft_gelu1(o[0][q][e + 1]), o[1][q][e + 1]));
                     unsigned hh, ll;
-                    irm_split2(g0, g1, hh, ll);
+                    irm_gate_split2(o[0][q][e], o[0][q][e + 1], o[1][q][e], o[1][q][e + 1], hh, ll);
                     Gh[q][2 * par + e / 2] = hh;
                     Gl[q][2 * par + e / 2] = ll;
                 }
@@ -278,22 +180,20 @@ __global__ __launch_bounds__(512, 2) void gdfn_tail_kernel(TailArgs a) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();
                 }
-                f32x4 accp = ft_ld<f32x4>(lds, vpark, 0);
+                f32x4 accp = irm_ld<f32x4>(lds, vpark, 0);
 #pragma unroll
                 for (int c = 0; c < CT; ++c) {
-                    const ft_h8 bh = ft_ld<ft_h8>(lds, vw, W2_OFF + (c * 2) * 1024);
-                    const ft_h8 bl = ft_ld<ft_h8>(lds, vw, W2_OFF + (c * 2 + 1) * 1024);
+                    const irm_h8 bh = irm_ld<irm_h8>(lds, vw, W2_OFF + (c * 2) * 1024);
+                    const irm_h8 bl = irm_ld<irm_h8>(lds, vw, W2_OFF + (c * 2 + 1) * 1024);
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
                         f32x4& t = (q == 1 && c == CT - 1) ? accp : acc2[q][c];
-                        t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ft_h8, Gl[q]), bh, t, 0, 0, 0);
-                        t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ft_h8, Gh[q]), bl, t, 0, 0, 0);
-                        t = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(ft_h8, Gh[q]), bh, t, 0, 0, 0);
+                        t = irm_mfma3_f16(__builtin_bit_cast(irm_h8, Gh[q]), __builtin_bit_cast(irm_h8, Gl[q]), bh, bl, t);
                     }
                 }
-                ft_st<f32x4>(lds, vpark, 0, accp);
+                irm_st<f32x4>(lds, vpark, 0, accp);
 #pragma unroll
-                for (int q = 0; q < 2; ++q) { Gh[q] = (ft_u4){0u, 0u, 0u, 0u}; Gl[q] = (ft_u4){0u, 0u, 0u, 0u}; }
+                for (int q = 0; q < 2; ++q) { Gh[q] = (irm_u4){0u, 0u, 0u, 0u}; Gl[q] = (irm_u4){0u, 0u, 0u, 0u}; }
             }
             if constexpr (more) park_h(par ^ 1);            // (the other image: its stencil finished before the last barrier)
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -314,7 +214,7 @@ __global__ __launch_bounds__(512, 2) void gdfn_tail_kernel(TailArgs a) {
             asm volatile("" : "+v"(t3));
             const int r3 = t3 & 15, ox = tx0 + 16 * (wave & 1) + 4 * ((t3 & 63) >> 4), oy0 = ty0 + 2 * (wave >> 1);
             float* X = a.X + (long)b * a.x_bs;
-            acc2[1][CT - 1] = ft_ld<f32x4>(lds, vpark, 0);
+            acc2[1][CT - 1] = irm_ld<f32x4>(lds, vpark, 0);
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
                 const int co = 16 * c + r3;
@@ -347,9 +247,9 @@ extern "C" int irm_gdfn_tail_f16x3_f32(const float* h_cl, long h_bs, const float
     TailArgs a;
     a.Hh = h_cl; a.h_bs = h_bs; a.X = x; a.x_bs = x_bs; a.rec = rec; a.w2 = w2; a.bias2 = bias2;
     a.C = C; a.H = H; a.W = W; a.S = (hid + 15) / 16; a.HP = hid_pad; a.CB = 2 * hid_pad; a.inv_s2 = inv_s2;
-    a.tiles_x = W / FT_TW; a.tiles = a.tiles_x * (H / FT_TH); a.items = B * a.tiles;
+    a.tiles_x = W / IRM_TW; a.tiles = a.tiles_x * (H / IRM_TH); a.items = B * a.tiles;
     constexpr int CT = 12;
-    const size_t lds = (size_t)(2 * 512 + CT * 512 + 2 * FT_PLF + 2048) * sizeof(float);
+    const size_t lds = (size_t)(2 * 512 + CT * 512 + 2 * IRM_PLF + 2048) * sizeof(float);
     IRM_ALLOW_BIG_LDS((&gdfn_tail_kernel<CT>));
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess ||

@@ -20,16 +20,14 @@
 //   C >= 192 levels (gemm_xres.hip / gemm_pw.hip remain the entry points for every other shape).
 #include "irm_common.h"
 #include <type_traits>
-#include <utility>
 
-typedef _Float16 ps_h8 __attribute__((ext_vector_type(8)));
 
 // LayerNorm + power-of-two scale + fp16 hi/lo split of ONE pixel's channels as lane (i, g) of a wave holds them (channels
 // 32 ks + 8 g + e; the other three lanes of the pixel are 16, 32, 48 lanes away).  Every operation is an explicitly rounded
 // intrinsic (no fma contraction left to the compiler): ln_split_kernel and the LN-fused GEMM run this same function.  lw / lb: LDS, LayerNorm weight / bias x operand scale.
 template <int KS>
 __device__ __forceinline__ void ps_ln_pixel(const float (&v)[KS][8], int K, int g, const float* lw, const float* lb, int ln_mode,
-                                            float eps, ps_h8 (&hi)[KS], ps_h8 (&lo)[KS]) {
+                                            float eps, irm_h8 (&hi)[KS], irm_h8 (&lo)[KS]) {
     float s = 0.0f;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
@@ -83,7 +81,6 @@ struct LnSplitArgs {
 
 template <int KS>
 __global__ __launch_bounds__(256) void ln_split_kernel(LnSplitArgs a) {
-    IRM_KERNEL_ENTRY();
     __shared__ __attribute__((aligned(16))) float lw[KS * 32], lb[KS * 32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int k = tid; k < KS * 32; k += blockDim.x) {
@@ -107,13 +104,13 @@ __global__ __launch_bounds__(256) void ln_split_kernel(LnSplitArgs a) {
             const int k = ks * 32 + 8 * g + e;
             v[ks][e] = xp[(long)min(k, a.K - 1) * a.N];
         }
-    ps_h8 hi[KS], lo[KS];
+    irm_h8 hi[KS], lo[KS];
     ps_ln_pixel<KS>(v, a.K, g, lw, lb, a.ln_mode, a.eps, hi, lo);
     _Float16* out = a.xs + (long)pt * KS * 1024 + lane * 8;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        *reinterpret_cast<ps_h8*>(out + ks * 1024) = hi[ks];
-        *reinterpret_cast<ps_h8*>(out + ks * 1024 + 512) = lo[ks];
+        *reinterpret_cast<irm_h8*>(out + ks * 1024) = hi[ks];
+        *reinterpret_cast<irm_h8*>(out + ks * 1024 + 512) = lo[ks];
     }
 }
 
@@ -155,21 +152,6 @@ struct PsArgs {
 
 __device__ float4 ps_dump[256 * 64];
 
-template <int... I, class F>
-__device__ __forceinline__ void ps_static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression
-template <int N, class F>
-__device__ __forceinline__ void ps_static_for(F&& f) {
-    ps_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
-
-template <int N>
-__device__ __forceinline__ void ps_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // KS = k-steps of 32 input channels, WP = pixel tiles per wave, CT = output tiles per chunk (one ring stage = the weight
 // fragments of CT tiles for one k-step), CG = tiles per register group (two groups in flight: CT / CG must be even).
 // NW = waves per workgroup: 8 (one workgroup per CU) or 4 (two per CU: while one loads its resident operands or stores a
@@ -182,7 +164,6 @@ __device__ __forceinline__ void ps_wait_vmcnt() {
 // an output tile - one 16-byte store per tile and pixel; the store count per wave and chunk (the vmcnt arithmetic) is unchanged.
 template <int KS, int WP, int CT, int CG, int NW, bool LNF = false, bool YCL = false>
 __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int NS = 4;                          // ring depth
     constexpr int FR = 2 * CT;                     // 1 KiB fragments per stage
     constexpr int DPW = (FR + NW - 1) / NW;        // DMA instructions per wave and stage (duplicates fill the last round)
@@ -207,11 +188,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
         const int id = blockIdx.x, mg = a.mgroups;
         if ((a.nblk & 7) == 0) {
             const int q = id / (8 * mg), rem = id - q * 8 * mg;
-#ifdef PS_OLD_MAP
-            pb = q * 8 + (rem & 7);
-#else
             pb = (rem & 7) * (a.nblk >> 3) + q;
-#endif
             mgi = rem >> 3;
         } else {
             pb = id / mg;
@@ -242,7 +219,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
     const int nc = min(c0 + a.cpg, nchunks) - c0;  // chunks of this workgroup (>= 1: the host sends no empty group)
 
     // ---- resident A operands: the wave's WP pixel tiles, all KS k-steps, hi and lo
-    ps_h8 xh[KS][WP], xl[KS][WP];
+    irm_h8 xh[KS][WP], xl[KS][WP];
     if constexpr (LNF) {
         float* lw = lbias + a.cpg * CT * 16;       // [2][32 KS] LayerNorm weight, bias x operand scale
         for (int k = tid; k < KS * 32; k += NW * 64) {
@@ -259,7 +236,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
             for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[ks][e] = xp[(long)(ks * 32 + 8 * g + e) * a.N];
-            ps_h8 hi[KS], lo[KS];
+            irm_h8 hi[KS], lo[KS];
             ps_ln_pixel<KS>(v, KS * 32, g, lw, lw + KS * 32, a.ln_mode, a.eps, hi, lo);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) { xh[ks][p] = hi[ks]; xl[ks][p] = lo[ks]; }
@@ -270,8 +247,8 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
             const _Float16* xp = a.xs + (long)pt_idx[p] * KS * 1024 + lane * 8;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                xh[ks][p] = *reinterpret_cast<const ps_h8*>(xp + ks * 1024);
-                xl[ks][p] = *reinterpret_cast<const ps_h8*>(xp + ks * 1024 + 512);
+                xh[ks][p] = *reinterpret_cast<const irm_h8*>(xp + ks * 1024);
+                xl[ks][p] = *reinterpret_cast<const irm_h8*>(xp + ks * 1024 + 512);
             }
         }
     }
@@ -279,16 +256,10 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
     // The workgroups sweep their output-tile chunks in ROTATED order (workgroup i starts at chunk i mod nc): started
     // together on the same order, all 256 CUs would request the same few KiB of the weight fragments at every moment -
     // one or two L2 channels per XCD serving everybody - instead of spreading their reads over the whole matrix.
-#ifdef PS_NO_ROTATE
-    const int rot = 0;
-#elif defined(PS_ROTATE_PER_WG)
-    const int rot = pb % nc;
-#else
     // per XCD, not per workgroup: the workgroups of an XCD (neighbouring pixel blocks) keep one chunk order, so that
     // together they write long contiguous runs of every output row and share each weight line through their L2; the
     // eight XCDs start an eighth of the matrix apart
     const int rot = (a.nblk & 7) == 0 ? (int)(((long)(pb / (a.nblk >> 3)) * nc) >> 3) : pb % nc;
-#endif
     auto cm = [&](int c) { const int cc = c + rot; return c0 + (cc >= nc ? cc - nc : cc); };
 
     // stage (c, ks) -> ring slot (c KS + ks) % NS
@@ -310,13 +281,13 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
 #pragma unroll
         for (int c = 0; c < CT; ++c) acc[p][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    ps_h8 wh[2][CG], wl[2][CG];
+    irm_h8 wh[2][CG], wl[2][CG];
     auto read_group = [&](int slot, int jg, int set) {
         const char* base = smem + slot * STG + jg * CG * 2048 + lane * 16;
 #pragma unroll
         for (int c = 0; c < CG; ++c) {
-            wh[set][c] = *reinterpret_cast<const ps_h8*>(base + c * 2048);
-            wl[set][c] = *reinterpret_cast<const ps_h8*>(base + c * 2048 + 1024);
+            wh[set][c] = *reinterpret_cast<const irm_h8*>(base + c * 2048);
+            wl[set][c] = *reinterpret_cast<const irm_h8*>(base + c * 2048 + 1024);
         }
     };
 
@@ -327,7 +298,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
         const int co = c0 * CT * 16 + k;
         lbias[k] = (a.bias && co < a.M) ? a.bias[co] : 0.0f;
     }
-    ps_wait_vmcnt<0>();
+    irm_wait_vmcnt<0>();
     {
         float4* d = ps_dump + ((blockIdx.x & 255) * 64 + lane);
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
@@ -343,7 +314,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
     auto chunk = [&](auto last_tag, int c) {
         constexpr bool LAST = decltype(last_tag)::value;
         const int it0 = c * KS;
-        ps_static_for<KS>([&](auto ks_c) {
+        irm_for<KS>([&](auto ks_c) {
             constexpr int ks = decltype(ks_c)::value;
             const int it = it0 + ks;
 #pragma unroll
@@ -356,7 +327,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
                     // the prologue's dump stores)
                     constexpr bool dma2 = !LAST || ks + 2 < KS;
                     constexpr int younger = (dma2 ? DPW : 0) + ((ks == 0 || ks == 1) ? ST : 0);
-                    ps_wait_vmcnt<younger>();
+                    irm_wait_vmcnt<younger>();
                     asm volatile("s_barrier" ::: "memory");   // stage it + 1 is complete; nobody reads stage it - 1 any more
                     if (!LAST || ks + 3 < KS) issue(c + (ks + 3) / KS, (ks + 3) % KS);
                     read_group((it + 1) & (NS - 1), 0, 0);     // (after the last stage: a stale slot, never used)
@@ -417,7 +388,7 @@ __global__ __launch_bounds__(NW * 64, 2) void gemm_ps_kernel(PsArgs a) {
 
     for (int c = 0; c < nc - 1; ++c) chunk(std::false_type{}, c);
     chunk(std::true_type{}, nc - 1);
-    ps_wait_vmcnt<0>();                            // no LDS-DMA may be in flight when the workgroup's LDS is released
+    irm_wait_vmcnt<0>();                            // no LDS-DMA may be in flight when the workgroup's LDS is released
 }
 
 template <int KS, int WP, int CT, int CG, int NW, bool LNF = false, bool YCL = false>

@@ -100,7 +100,6 @@ __device__ __forceinline__ void irm_stats_from_acc(const f32x4 (&acc)[PT][CT], i
 
 template <int PT, int CT, bool VEC>
 __global__ __launch_bounds__(256) void gemm_pw_kernel(GemmArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int BN = 64 * PT;      // pixels per workgroup
     constexpr int BNP = BN + 16;     // row stride: rows k and k+1 land on disjoint bank halves
     constexpr int BK = 16;           // input channels per stage
@@ -265,26 +264,18 @@ __global__ __launch_bounds__(256) void gemm_pw_kernel(GemmArgs a) {
     }
 }
 
-__device__ __attribute__((noinline)) float irm_act_slow(float v, int act) { return irm_act(v, act); }
 
 // Masked-off lanes of the epilogue stores write here instead of being skipped, so that every wave
 // issues exactly PT*CT store instructions per pass and the counted vmcnt waits stay exact.
 __device__ float4 irm_dump[256 * 64];
 
-template <int N>
-__device__ __forceinline__ void irm_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // F16: the GEMM proper runs on the fp16 matrix cores as an fp32 emulation - both operands are split into
 // fp16 hi + lo parts (x = hi + lo exactly up to 2^-22 |x|; the weights are split on the host), three
 // 16x16x16 MFMAs (lo*hi, hi*lo, hi*hi) accumulate in fp32: 2^-21 relative per product instead of 2^-24, at
 // 24 instead of 128 matrix cycles per tile and 16 channels, and off the fp32 datapath the VALU needs.
-typedef _Float16 irm_h4 __attribute__((ext_vector_type(4)));
 
 template <int PT, int CT, int NS, int LN, bool RES, bool F16 = false>
 __global__ __launch_bounds__(256, (PT == 2 && NS == 3) ? 3 : 2) void gemm_ring_kernel(GemmArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int BN = 64 * PT, BK = 16;            // pixels per workgroup, channels per stage
     constexpr int RPU = 256 / BN;                   // X rows per 1 KiB DMA instruction (PT 2: 2, PT 4: 1)
     constexpr int XS = BK * BN;                 // floats of X per stage
@@ -513,7 +504,7 @@ __global__ __launch_bounds__(256, (PT == 2 && NS == 3) ? 3 : 2) void gemm_ring_k
 #pragma unroll
                     for (int p = 0; p < PT; ++p)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[p][c][e] = irm_act_slow(acc[p][c][e], a.act);
+                        for (int e = 0; e < 4; ++e) acc[p][c][e] = irm_act_noinline(acc[p][c][e], a.act);
             }
             if (RES && R) {
 #pragma unroll
@@ -568,11 +559,9 @@ static int launch_ring(const GemmArgs& a, int B, int ygroups, hipStream_t stream
     // Not the split kernel at CT 4: that 3-deep instantiation (no spills, 136 VGPRs) returns wrong values in pixel
     // tile p = 1 of output tile 0 for every shape (tests/test_gpu_gemm_variants.py), while its 4-deep sibling, the
     // exact-f32 CT 4 and the split CT 3 / 6 3-deep instantiations are right; no production launch uses it.
-#ifndef IRM_NO_RING3                              // (variant builds for A/B: tools/build_variant.sh NAME -DIRM_NO_RING3 gemm_pw.hip)
     if constexpr (PT == 2 && RES && CT <= 6 && !(F16 && CT == 4)) {
         if (a.K <= 512) return launch_ring_ns<PT, CT, 3, LN, RES, F16>(a, B, ygroups, stream);
     }
-#endif
     return launch_ring_ns<PT, CT, PT == 2 ? 4 : 3, LN, RES, F16>(a, B, ygroups, stream);
 }
 

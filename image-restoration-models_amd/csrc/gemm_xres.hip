@@ -9,7 +9,6 @@
 #include "irm_common.h"
 #include <stdlib.h>
 
-typedef _Float16 xr_h4 __attribute__((ext_vector_type(4)));
 
 struct XresArgs {
     const float* Wp;              // pack_gemm_weight_split: [mtile][stage][hi 64x4 | lo 64x4] halves
@@ -22,16 +21,9 @@ struct XresArgs {
     int ln_mode, act;
 };
 
-template <int N>
-__device__ __forceinline__ void xr_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
-__device__ __attribute__((noinline)) float xr_act(float v, int act) { return irm_act(v, act); }
 
-typedef _Float16 xr_h8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ xr_h8 xr_cat(xr_h4 a, xr_h4 b) {
+__device__ __forceinline__ irm_h8 xr_cat(irm_h4 a, irm_h4 b) {
     return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);      // register-tuple concatenation, no moves
 }
 
@@ -43,7 +35,6 @@ __device__ __forceinline__ xr_h8 xr_cat(xr_h4 a, xr_h4 b) {
 // split this way the compute waves never wait on memory, the stage barrier is the only hand-over.
 template <int KT, int CT, int NS, int WP, int NPT>
 __global__ __launch_bounds__((NPT / WP + 1) * 64, 1) void gemm_xres_kernel(XresArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int NW = NPT / WP;                   // compute waves, WP pixel tiles each
     constexpr int BN = NPT * 16;                   // pixels per workgroup (256 for K <= 96, 128 / 64 for K <= 192 / 384:
                                                    // the resident input is 96 KiB in every case)
@@ -100,8 +91,8 @@ __global__ __launch_bounds__((NPT / WP + 1) * 64, 1) void gemm_xres_kernel(XresA
             if (j < TOT) issue(j);
         __syncthreads();                           // pairs with the barrier after the input conversion
         for (int it = 0; it < TOT; ++it) {
-            if (TOT - 1 - it >= NS - 2 && NS >= 3) xr_wait_vmcnt<(NS - 2) * CT * 2>();
-            else xr_wait_vmcnt<0>();
+            if (TOT - 1 - it >= NS - 2 && NS >= 3) irm_wait_vmcnt<(NS - 2) * CT * 2>();
+            else irm_wait_vmcnt<0>();
             asm volatile("s_barrier" ::: "memory");   // stage it is in LDS; everybody is done with stage it-1
             if (it + NS - 1 < TOT) issue(it + NS - 1);
         }
@@ -134,7 +125,7 @@ __global__ __launch_bounds__((NPT / WP + 1) * 64, 1) void gemm_xres_kernel(XresA
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int kg = q * NPAR + par, s = kg >> 2, gg = kg & 3;
-            xr_h4 h, l;
+            irm_h4 h, l;
             float xn[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -148,8 +139,8 @@ __global__ __launch_bounds__((NPT / WP + 1) * 64, 1) void gemm_xres_kernel(XresA
             irm_split4(xn, h, l);
             // image of a (stage pair, pixel tile): [hi even stage | hi odd stage | lo even | lo odd], 512 B each
             const int off = (((s >> 1) * NPT + pt) * 4 + (s & 1)) * 128 + (gg * 16 + i) * 2;   // floats
-            *reinterpret_cast<xr_h4*>(ah + off) = h;
-            *reinterpret_cast<xr_h4*>(ah + off + 256) = l;
+            *reinterpret_cast<irm_h4*>(ah + off) = h;
+            *reinterpret_cast<irm_h4*>(ah + off + 256) = l;
         }
     }
     __syncthreads();                               // the resident tile is complete and visible
@@ -167,24 +158,24 @@ __global__ __launch_bounds__((NPT / WP + 1) * 64, 1) void gemm_xres_kernel(XresA
     for (int it = 0; it < TOT; ++it) {
         asm volatile("s_barrier" ::: "memory");
         const float* wb = wring + (it % NS) * WST;
-        xr_h8 xh[WP], xl[WP];
+        irm_h8 xh[WP], xl[WP];
 #pragma unroll
         for (int p = 0; p < WP; ++p) {
             const float* xa = ah + ((t * NPT + wave * WP + p) * 4) * 128 + lane * 2;
-            xh[p] = xr_cat(*reinterpret_cast<const xr_h4*>(xa), *reinterpret_cast<const xr_h4*>(xa + 128));
-            xl[p] = xr_cat(*reinterpret_cast<const xr_h4*>(xa + 256), *reinterpret_cast<const xr_h4*>(xa + 384));
+            xh[p] = xr_cat(*reinterpret_cast<const irm_h4*>(xa), *reinterpret_cast<const irm_h4*>(xa + 128));
+            xl[p] = xr_cat(*reinterpret_cast<const irm_h4*>(xa + 256), *reinterpret_cast<const irm_h4*>(xa + 384));
         }
         // groups of CG tiles: their weights in registers, then the three partial products as three sweeps over the
         // 2 x CG independent accumulators (small terms first)
         constexpr int CG = WP >= 4 ? (CT % 3 == 0 ? 3 : 2) : CT;   // WP 2: all weight operands of the stage up front (one LDS round trip)
 #pragma unroll
         for (int c0 = 0; c0 < CT; c0 += CG) {
-            xr_h8 bh[CG], bl[CG];
+            irm_h8 bh[CG], bl[CG];
 #pragma unroll
             for (int c = 0; c < CG; ++c) {
                 const float* w = wb + (c0 + c) * 512 + lane * 2;
-                bh[c] = xr_cat(*reinterpret_cast<const xr_h4*>(w), *reinterpret_cast<const xr_h4*>(w + 128));
-                bl[c] = xr_cat(*reinterpret_cast<const xr_h4*>(w + 256), *reinterpret_cast<const xr_h4*>(w + 384));
+                bh[c] = xr_cat(*reinterpret_cast<const irm_h4*>(w), *reinterpret_cast<const irm_h4*>(w + 128));
+                bl[c] = xr_cat(*reinterpret_cast<const irm_h4*>(w + 256), *reinterpret_cast<const irm_h4*>(w + 384));
             }
 #pragma unroll
             for (int c = 0; c < CG; ++c)
@@ -214,7 +205,7 @@ __global__ __launch_bounds__((NPT / WP + 1) * 64, 1) void gemm_xres_kernel(XresA
                 for (int p = 0; p < WP; ++p) {
                     float4 v = make_float4(acc[p][c][0] + bv, acc[p][c][1] + bv, acc[p][c][2] + bv, acc[p][c][3] + bv);
                     if (a.act != IRM_ACT_NONE) {
-                        v.x = xr_act(v.x, a.act); v.y = xr_act(v.y, a.act); v.z = xr_act(v.z, a.act); v.w = xr_act(v.w, a.act);
+                        v.x = irm_act_noinline(v.x, a.act); v.y = irm_act_noinline(v.y, a.act); v.z = irm_act_noinline(v.z, a.act); v.w = irm_act_noinline(v.w, a.act);
                     }
                     if (row_ok && pixs[p] < a.N) *reinterpret_cast<float4*>(Y + (long)co * a.N + pixs[p]) = v;
                     acc[p][c] = (f32x4){0.f, 0.f, 0.f, 0.f};

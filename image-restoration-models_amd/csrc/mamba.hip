@@ -21,7 +21,6 @@
 // [B][R][C] -> [B][C][R] through a padded 32x32 LDS tile
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, long in_bs,
                                                         float* __restrict__ out, long out_bs, int R, int C) {
-    IRM_KERNEL_ENTRY();
     __shared__ float tile[32][33];
     const int b = blockIdx.z;
     const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
@@ -77,9 +76,6 @@ __device__ __forceinline__ float irm_softplus(float x) {
     return fmaxf(x, 0.0f) + (dd == 0.0f ? e : l);
 }
 
-typedef float sc_v2 __attribute__((ext_vector_type(2)));
-typedef float sc_v4 __attribute__((ext_vector_type(4)));
-
 // The per-step row [dt_raw R | B N | C N] of a (direction, pixel) is wave-uniform.  It is fetched with ONE coalesced
 // vector load per 64 elements (lane j holds element j) two batches of TU steps ahead - vector loads return in
 // order, so the prefetch depth is free of the one-wait-for-everything rule of scalar loads -, parked in a small
@@ -92,8 +88,8 @@ typedef float sc_v4 __attribute__((ext_vector_type(4)));
 // dt_rank R is a template argument on its own: MaIRUNet has R = 3N/4, MaIR ceil(embed_dim / 16) (4 at embed 60).
 template <int N, int R, bool EMIT>
 __global__ __launch_bounds__(64, (N <= 8 ? 4 : N == 16 ? 3 : 2)) void scan_chunk_kernel(ScanArgs a) {
-    IRM_KERNEL_ENTRY();   // (waves per SIMD: caps the
-    constexpr int J = R + 2 * N, JV = (J + 63) / 64;                                                    // scheduler's read hoisting)
+    // (waves per SIMD: caps the scheduler's read hoisting)
+    constexpr int J = R + 2 * N, JV = (J + 63) / 64;
     constexpr int TU = 8;                                     // time steps per batch
     constexpr int RP = (R + 3) & ~3;                          // LDS row: [dt_raw, padded to 16 bytes | B | C]
     constexpr int JS = (RP + 2 * N + 3) & ~3;                // rows stay 16-byte aligned (N = 1: [dt | B C pad])
@@ -107,7 +103,7 @@ __global__ __launch_bounds__(64, (N <= 8 ? 4 : N == 16 ? 3 : 2)) void scan_chunk
     const bool on = d < a.D;
     const int dc = on ? d : a.D - 1;                          // idle lanes shadow a valid channel
 
-    sc_v2 Ac[NP], h[NP];
+    irm_v2 Ac[NP], h[NP];
     float wdt[R];
 #pragma unroll
     for (int n = 0; n < N; ++n) Ac[n / 2][n % 2] = a.A[((long)k * a.D + dc) * N + n] * 1.44269504088896341f;   // exp(x) = exp2(x log2 e)
@@ -173,14 +169,14 @@ __global__ __launch_bounds__(64, (N <= 8 ? 4 : N == 16 ? 3 : 2)) void scan_chunk
             float dt = bias;
 #pragma unroll
             for (int r = 0; r < RP; r += 4) {
-                const sc_v4 q = *reinterpret_cast<const sc_v4*>(row + r);
+                const f32x4 q = *reinterpret_cast<const f32x4*>(row + r);
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (r + e < R) dt = fmaf(wdt[r + e], q[e], dt);
             }
             dt = irm_softplus(dt) * (live ? 1.0f : 0.0f);
             const float du = dt * u0[i];
-            sc_v2 y2 = {dsk * u0[i], 0.f};
+            irm_v2 y2 = {dsk * u0[i], 0.f};
             if constexpr (N == 1) {
                 const float e = __builtin_amdgcn_exp2f(dt * Ac[0].x);
                 h[0].x = fmaf(e, h[0].x, du * row[RP]);
@@ -188,15 +184,15 @@ __global__ __launch_bounds__(64, (N <= 8 ? 4 : N == 16 ? 3 : 2)) void scan_chunk
             }
 #pragma unroll
             for (int n = 0; n < (N == 1 ? 0 : N); n += 4) {
-                const sc_v4 Bq = *reinterpret_cast<const sc_v4*>(row + RP + n);
-                const sc_v4 Cq = *reinterpret_cast<const sc_v4*>(row + RP + N + n);
+                const f32x4 Bq = *reinterpret_cast<const f32x4*>(row + RP + n);
+                const f32x4 Cq = *reinterpret_cast<const f32x4*>(row + RP + N + n);
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     const int m = (n + 2 * hh) / 2;
-                    const sc_v2 x = (sc_v2){dt, dt} * Ac[m];
-                    const sc_v2 e = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-                    const sc_v2 Bv = {Bq[2 * hh], Bq[2 * hh + 1]}, Cv = {Cq[2 * hh], Cq[2 * hh + 1]};
-                    h[m] = e * h[m] + (sc_v2){du, du} * Bv;
+                    const irm_v2 x = (irm_v2){dt, dt} * Ac[m];
+                    const irm_v2 e = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
+                    const irm_v2 Bv = {Bq[2 * hh], Bq[2 * hh + 1]}, Cv = {Cq[2 * hh], Cq[2 * hh + 1]};
+                    h[m] = e * h[m] + (irm_v2){du, du} * Bv;
                     if (EMIT) y2 = h[m] * Cv + y2;
                 }
             }
@@ -235,7 +231,6 @@ __global__ __launch_bounds__(64, (N <= 8 ? 4 : N == 16 ? 3 : 2)) void scan_chunk
 // group again to emit the initial states.  A workgroup owns 8 states of 64 channels.
 template <int N>
 __global__ __launch_bounds__(1024) void scan_carry_kernel(ScanArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int NB = N < 8 ? N : 8, G = 16;
     __shared__ float comp[G][NB + 1][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -290,7 +285,6 @@ __global__ __launch_bounds__(1024) void scan_carry_kernel(ScanArgs a) {
 // per (batch, direction, channel block): ysum[chunk 0] <- sum over chunks (fixed order: 16 interleaved partial
 // sums, four loads in flight each, combined in wave order), so the gate reads one value per channel
 __global__ __launch_bounds__(1024) void ysum_reduce_kernel(float* __restrict__ ysum, int nchunk) {
-    IRM_KERNEL_ENTRY();
     __shared__ float part[16][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float* p = ysum + (long)blockIdx.x * nchunk * 64 + lane;
@@ -329,7 +323,6 @@ static int scan_launch(const ScanArgs& a, int B, hipStream_t stream) {
 // are shared; the padding slots of the last channel block are not written (nothing reads them into a result).
 template <int N, int R, bool EMIT>
 __global__ __launch_bounds__(64) void scan_chunk_flat_kernel(ScanArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int J = R + 2 * N;
     constexpr int TU = N == 1 ? 8 : 2;                        // steps per prefetched batch (2 J TU row registers)
     const int lane = threadIdx.x, c = blockIdx.x, b = blockIdx.z;
@@ -452,7 +445,6 @@ extern "C" int irm_selective_scan_f32(const float* xT, const float* pT, const in
 __global__ __launch_bounds__(256) void gate_kernel(const float* __restrict__ ysum, const float* __restrict__ gw,
                                                    const float* __restrict__ gb, float* __restrict__ gate, int D,
                                                    int DB, int nchunk, float inv_L) {
-    IRM_KERNEL_ENTRY();
     const int b = blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;           // e = kq * D + d
     if (e >= 4 * D) return;
@@ -485,7 +477,6 @@ struct CombArgs {
 
 template <int DV, int PW>      // DV = ceil(D / 64) values per lane
 __global__ __launch_bounds__(256) void combine_kernel(CombArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int PX = 4 * PW, TS = PX + 1;
     extern __shared__ float tile[];                          // [D][PX + 1]
     const int b = blockIdx.y, p0 = blockIdx.x * PX;

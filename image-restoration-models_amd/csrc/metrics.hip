@@ -42,7 +42,6 @@ __device__ __forceinline__ V block_sum256(V v, V* part) {
 // evaluates its SSIM.
 template <typename T, typename A, int C>
 __global__ __launch_bounds__(256) void ssim_tile_kernel(MetricsArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int twp = MT_OUT / C, rw = (twp + 6) * C;     // output pixels, loaded values per tile row
     constexpr int NLD = ((MT_ROWS + 6) * rw + 255) / 256;   // loads per thread
     __shared__ T sx[MT_ROWS + 6][rw], sy[MT_ROWS + 6][rw];
@@ -152,7 +151,6 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(MetricsArgs a) {
 __global__ __launch_bounds__(256) void metrics_reduce_kernel(const unsigned long long* sse_part, const double* ssim_part,
                                                              int ntiles, double count, unsigned long long* sse,
                                                              double* ssim) {
-    IRM_KERNEL_ENTRY();
     __shared__ double dpart[4];
     __shared__ unsigned long long upart[4];
     const long base = (long)blockIdx.x * ntiles;

@@ -59,7 +59,6 @@ __device__ __forceinline__ float bt_value(const T* p, int j, float range, int bg
 // moments of one staged column, then each thread sums 11 of those horizontally for one output value.
 template <typename T, int C, bool Y>
 __global__ __launch_bounds__(256) void basicsr_tile_kernel(BasicsrArgs a) {
-    IRM_KERNEL_ENTRY();
     constexpr int CE = Y ? 1 : C;
     constexpr int twp = BT_OUT / CE, rw = (twp + BT_HALO) * CE;
     __shared__ float sx[BT_ROWS + BT_HALO][rw], sy[BT_ROWS + BT_HALO][rw];
@@ -169,7 +168,6 @@ template <bool Y>
 __global__ __launch_bounds__(256) void basicsr_reduce_kernel(const unsigned long long* sse_part, const double* ssim_part,
                                                              int ntiles, double count, unsigned long long* sse,
                                                              double* ssim) {
-    IRM_KERNEL_ENTRY();
     __shared__ double dpart[4], epart[4];
     __shared__ unsigned long long upart[4];
     const long base = (long)blockIdx.x * ntiles;

@@ -65,7 +65,6 @@ __device__ __forceinline__ double nq_plane(const U* F, int W, int y, int x, int 
 
 template <typename U, int C>
 __global__ __launch_bounds__(NQ_THREADS) void niqe_block_kernel(NiqeArgs a) {
-    IRM_KERNEL_ENTRY();
     extern __shared__ double sm[];
     double* tile = sm;                 // [T][T] plane values, then [B][B] MSCN values
     double* part = sm + NQ_OFF_PART;

@@ -45,7 +45,6 @@ __device__ __forceinline__ int block_min256(int v, int* part) {
 
 template <typename T, int C, bool OUT_FLOAT>
 __global__ __launch_bounds__(256) void imresize_kernel(ResizeArgs a) {
-    IRM_KERNEL_ENTRY();
     __shared__ float mid[RZ_LDS_FLOATS];
     __shared__ int ipart[4];
     const int tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x, k = blockIdx.y;

@@ -19,7 +19,6 @@ struct ExtractArgs {
 };
 
 __global__ __launch_bounds__(256) void tile_extract_kernel(ExtractArgs a) {
-    IRM_KERNEL_ENTRY();
     const long total = (long)a.T * a.C * a.ph * a.pw;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
@@ -84,7 +83,6 @@ struct BlendArgs {
 // SCALED (irm_window_blend_scaled): every extent above is already at output scale; only the origins are scaled here.
 template <bool SCALED>
 __global__ __launch_bounds__(256) void blend_kernel(BlendArgs a) {
-    IRM_KERNEL_ENTRY();
     const long total = (long)a.H * a.W * a.Co;
     unsigned long long err = 0;
     const bool albu = a.post_scale != 1.0f || a.post_shift != 0.0f;

@@ -338,6 +338,13 @@ def test_no_experiment_switches():
             text = f.read()
         for word in ("irm_probe_", "IRM_PROBES", "IRM_DBG"):
             assert word not in text, (path, word)
+        # no compile-time experiment switches either: the kernel sources and headers hold no preprocessor conditional
+        # (irm_common.h uses #pragma once); the public C header keeps its include guard and its extern "C" pair
+        if path.endswith((".hip", ".h")):
+            allowed = {"#ifndef IRM_HIP_H", "#ifdef __cplusplus"} if os.path.basename(path) == "irm_hip.h" else set()
+            for line in text.splitlines():
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                    assert line.strip() in allowed, (path, line)
 
 
 def test_asan_host_build_rejects_bad_arguments(tmp_path):

@@ -1,6 +1,7 @@
 #!/bin/bash
-# usage: tools/build_variant.sh NAME "-DFLAG=.." file.hip [file2.hip ...]  -> tools/vbuild/libirm_NAME.so
-# (experiment builds for A/B timing in one gpurun call; not part of the product build)
+# usage: tools/build_variant.sh NAME "EXTRA FLAGS" file.hip [file2.hip ...]  -> tools/vbuild/libirm_NAME.so
+# Rebuilds the named (edited) kernel files, links them with the product's objects of the others; load the result through
+# IRM_HIP_LIB for an A/B.  The sources have no -D switches: EXTRA FLAGS is for compiler options and may be "".
 set -e
 cd "$(dirname "$0")/../image-restoration-models_amd/csrc"
 name=$1; flags=$2; shift 2
