@@ -72,6 +72,13 @@ SIGNATURES = {
     "irm_ensemble_merge_f32": [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],
 }
 
+#: the fp16 entry points (conv3x3_h.hip), mirrors include/irm_hip_half.h one to one
+SIGNATURES_HALF = {
+    "irm_conv3x3_h_in_f32": [_P, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P],
+    "irm_conv3x3_h_f16": [_P, _F, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "irm_conv3x3_h_out_f32": [_P, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -90,7 +97,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(make -C image-restoration-models_amd/csrc).  There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I
@@ -357,6 +364,32 @@ def pack_conv3x3_weight_split(w: torch.Tensor):
         return t.view(mt, 16, st, 4, 8, 9).permute(0, 2, 5, 3, 1, 4)
     packed = torch.stack([arr(hi), arr(lo)], dim=3).contiguous()          # [mt][st][tap][2][g][m][8]
     return packed.view(-1).view(torch.float32), 16.0 / s
+
+
+def pack_conv3x3_h(w: torch.Tensor):
+    """W [Co][Ci][3][3] (Ci, Co multiples of 64) -> operands of irm_conv3x3_h_f16: (wp, inv_scale) with wp a float16
+    tensor [Ci/64 stages][9 taps][Co/16][2 k-steps][lane = 16 g + m][8 halves j] =
+    RNE_fp16(W[16 mtile + m][64 stage + 32 ks + 8 g + j][tap] * s), s a power of two with max|W| s in [2^13, 2^14) (the
+    convention of pack_conv3x3_weight_split: small BN-merged weights stay out of the fp16 subnormals; all-zero weights
+    get s = 1) and inv_scale = 1 / s, which the kernel applies in fp32."""
+    dev = w.device
+    w = w.detach().float().cpu()
+    co, ci = w.shape[:2]
+    if co % 64 or ci % 64 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"pack_conv3x3_h: expected [Co][Ci][3][3] with Ci, Co multiples of 64, got {tuple(w.shape)}")
+    s = _pow2_scale(w)
+    q = (w.reshape(co, ci, 9) * s).half()                  # (a power of two: the product is exact, one rounding)
+    # [mt][16 m][st][2 ks][4 g][8 j][9 tap] -> [st][tap][mt][ks][g][m][j]
+    packed = q.view(co // 16, 16, ci // 64, 2, 4, 8, 9).permute(2, 6, 0, 3, 4, 1, 5).contiguous().view(-1)
+    return packed.to(dev), 1.0 / s
+
+
+def unpack_conv3x3_h(packed: torch.Tensor, inv_scale: float, co: int, ci: int) -> torch.Tensor:
+    """Inverse of pack_conv3x3_h: the weights the kernel multiplies with, RNE_fp16(W s) / s, as float32 [Co][Ci][3][3]
+    (tests, the quantised-chain model)."""
+    q = packed.detach().cpu().view(ci // 64, 9, co // 16, 2, 4, 16, 8).float()
+    w = q.permute(2, 5, 0, 3, 4, 6, 1).reshape(co, ci, 3, 3)
+    return w * float(inv_scale)
 
 
 class ConvWeight:

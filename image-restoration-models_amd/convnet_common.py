@@ -11,6 +11,34 @@ def conv3x3(wp, x, y, ci, co, bias=None, relu1=False, res=None, res_mode=0, relu
     ops.conv3x3(wp, x, y, ci, co, bias=bias, relu1=relu1, res=res, res_mode=res_mode, relu2=relu2)
 
 
+#: the values of a conv stack's `precision` keyword; "fp16" runs the native-fp16 kernels (conv3x3_h.hip) and is NOT
+#: reference-parity: every hidden activation is rounded to 11 significant bits
+PRECISIONS = ("fp32", "fp16")
+
+
+def check_precision(precision, what, features=None):
+    if precision not in PRECISIONS:
+        raise ValueError(f"{what}: precision must be one of {PRECISIONS}, got {precision!r}")
+    if precision == "fp16" and features is not None and features not in (64, 128):
+        raise ValueError(f"{what}: precision='fp16' needs 64 or 128 hidden channels, got {features}")
+    return precision
+
+
+def thin_weight(w):
+    """The plain fp32 weight of a first / last layer of the fp16 mode (ops.conv3x3_h_in / conv3x3_h_out)."""
+    return w.detach().float().contiguous()
+
+
+def half_workspace(ws, key, names, shape, device):
+    """fp16 channel-last buffers `names` of `shape` [B, H, W, C], kept in the dict `ws` while `key` is unchanged."""
+    if ws.get("key") != key:
+        ws.clear()
+        ws["key"] = key
+        for n in names:
+            ws[n] = torch.empty(shape, dtype=torch.float16, device=device)
+    return ws
+
+
 class PackedCache:
     """Rebuilds packed weights when the parameters of `module` change."""
 

@@ -3,19 +3,23 @@
 Same constructor and state_dict keys as the reference (``model.<2i>.weight/bias``:
 B.conv with mode 'C'+'R' puts a ReLU module after every conv but the last,
 basicblock.py:61-98).  Every layer is one irm_conv3x3_f32 launch with bias+ReLU
-in the epilogue; the last layer also folds the residual ``x - n``."""
+in the epilogue; the last layer also folds the residual ``x - n``.
+
+``precision="fp16"`` (opt-in, not reference-parity) keeps the hidden activations as fp16 channel-last tensors and runs
+irm_conv3x3_h_in_f32 -> irm_conv3x3_h_f16 x (nb - 2) -> irm_conv3x3_h_out_f32; input, output and state_dict are the same."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from ... import _hip
-from ...convnet_common import PackedCache, conv3x3, require_cuda
+from ... import _hip, ops
+from ...convnet_common import PackedCache, check_precision, conv3x3, half_workspace, require_cuda, thin_weight
 
 
 class DnCNN(nn.Module):
-    def __init__(self, in_nc=1, out_nc=1, nc=64, nb=17, act_mode='BR'):
+    def __init__(self, in_nc=1, out_nc=1, nc=64, nb=17, act_mode='BR', precision="fp32"):
         super().__init__()
+        self.precision = check_precision(precision, "DnCNN", nc)
         if 'B' in act_mode:
             raise NotImplementedError("inference uses BN-merged weights (act_mode='R', src/dncnn/__init__.py:8)")
         assert 'R' in act_mode, 'only ReLU activation is used by the reference loader'
@@ -27,7 +31,7 @@ class DnCNN(nn.Module):
             if i + 1 < nb:
                 layers.append(nn.ReLU(inplace=True))
         self.model = nn.Sequential(*layers)      # parameter holder: never called
-        self._cache = PackedCache(self, self._build)
+        self._cache = PackedCache(self, self._build_half if precision == "fp16" else self._build)
         self.hip_graph = True      # the tiler replays the per-batch forward from a HIP graph (utils.graphed_forward)
         self._ws = {}
 
@@ -37,6 +41,13 @@ class DnCNN(nn.Module):
     def _build(self):
         return [(_hip.pack_conv3x3(m.weight), m.bias.detach().float().contiguous(),
                  m.in_channels, m.out_channels) for m in self._convs()]
+
+    def _build_half(self):
+        convs = self._convs()
+        bias = [m.bias.detach().float().contiguous() for m in convs]
+        return ([(thin_weight(convs[0].weight), bias[0])]
+                + [(_hip.pack_conv3x3_h(m.weight), b) for m, b in zip(convs[1:-1], bias[1:-1])]
+                + [(thin_weight(convs[-1].weight), bias[-1])])
 
     def load_synthetic(self, seed=42):
         from ... import synth
@@ -55,6 +66,8 @@ class DnCNN(nn.Module):
         B, _, H, W = x.shape
         layers = self._cache.get()
         key = (B, H, W, str(x.device))
+        if self.precision == "fp16":
+            return self._forward_half(x, layers, key)
         if self._ws.get("key") != key:
             self._ws = {"key": key,
                         "a": torch.empty(B, self.nc, H, W, dtype=torch.float32, device=x.device),
@@ -67,4 +80,16 @@ class DnCNN(nn.Module):
                 cur, nxt = nxt, (self._ws["b"] if nxt is self._ws["a"] else self._ws["a"])
             else:
                 conv3x3(wp, cur, out, ci, co, bias=bias, res=x, res_mode=2)    # x - n
+        return out
+
+    def _forward_half(self, x, layers, key):
+        B, _, H, W = x.shape
+        ws = half_workspace(self._ws, key, ("a", "b"), (B, H, W, self.nc), x.device)
+        cur, nxt = ws["a"], ws["b"]
+        ops.conv3x3_h_in(layers[0][0], x, cur, self.in_nc, self.nc, bias=layers[0][1], relu1=True)
+        for wp, bias in layers[1:-1]:
+            ops.conv3x3_h(wp, cur, nxt, self.nc, self.nc, bias=bias, relu1=True)
+            cur, nxt = nxt, cur
+        out = torch.empty(B, self.out_nc, H, W, dtype=torch.float32, device=x.device)
+        ops.conv3x3_h_out(layers[-1][0], cur, out, self.nc, self.out_nc, bias=layers[-1][1], res=x, res_mode=2)    # x - n
         return out

@@ -624,3 +624,18 @@ def upsample_add(src, out, scale, add=None):
     _launch("upsample_add", 0.0, 4.0 * B * C * Hs * Ws * (1 + scale * scale * (2 if add is not None else 1)),
             "irm_upsample_add_f32", _hip.ptr(src), _bs(src), _hip.ptr(add), _bs(add), _hip.ptr(out), _bs(out), B, C, Hs, Ws,
             int(scale), tag=f"C{C} {Hs}x{Ws} x{scale} B{B}")
+
+
+# --------------------------------------------------------------------------- fp16 mode of the conv stacks (ops_half.py)
+_HALF_WRAPPERS = ("conv3x3_h_in", "conv3x3_h", "conv3x3_h_out")
+
+
+def __getattr__(name):
+    """ops.conv3x3_h_in / conv3x3_h / conv3x3_h_out: the wrappers of ops_half.py, bound here at their first use (that
+    module imports this one, so neither depends on which of the two is imported first)."""
+    if name in _HALF_WRAPPERS:
+        from . import ops_half
+        for n in _HALF_WRAPPERS:
+            globals()[n] = getattr(ops_half, n)
+        return globals()[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

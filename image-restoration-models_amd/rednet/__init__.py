@@ -9,8 +9,8 @@ from .rednet import REDNet  # noqa: E402
 __all__ = ["REDNet", "get_model", "SYNTH_RULES"]
 
 
-def get_model(weights_path: str, device: torch.device):
-    model = REDNet()
+def get_model(weights_path: str, device: torch.device, precision: str = "fp32"):
+    model = REDNet(precision=precision)
     state_dict = torch.load(weights_path, map_location="cpu", weights_only=True)
     model.load_state_dict(state_dict, strict=False)
     model.to(device)

@@ -2,27 +2,32 @@
 
 Same state_dict keys (conv1..15, deconv1..15).  ConvTranspose2d(k=3,s=1,p=1) is
 run as a conv3x3 with the weight transposed and flipped at pack time; the
-symmetric skips ``relu(relu(deconv) + c)`` and the final ``+ x`` are conv epilogues."""
+symmetric skips ``relu(relu(deconv) + c)`` and the final ``+ x`` are conv epilogues.
+
+``precision="fp16"`` (opt-in, not reference-parity) keeps the hidden activations and the skip features as fp16
+channel-last tensors: irm_conv3x3_h_in_f32 -> irm_conv3x3_h_f16 x 28 -> irm_conv3x3_h_out_f32."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from .. import _hip
-from ..convnet_common import PackedCache, conv3x3, require_cuda
+from .. import _hip, ops
+from ..convnet_common import PackedCache, check_precision, conv3x3, half_workspace, require_cuda, thin_weight
 
 
 class REDNet(nn.Module):
-    def __init__(self, num_channels=1, num_features=128):
+    def __init__(self, num_channels=1, num_features=128, precision="fp32"):
         super().__init__()
+        self.precision = check_precision(precision, "REDNet", num_features)
         self.num_channels, self.num_features = num_channels, num_features
         for i in range(1, 16):
             setattr(self, f"conv{i}", nn.Conv2d(num_channels if i == 1 else num_features, num_features, 3, padding=1))
         for i in range(1, 16):
             setattr(self, f"deconv{i}", nn.ConvTranspose2d(num_features, num_channels if i == 15 else num_features,
                                                            3, padding=1))
-        self._cache = PackedCache(self, self._build)
+        self._cache = PackedCache(self, self._build_half if precision == "fp16" else self._build)
         self.hip_graph = True      # the tiler replays the per-batch forward from a HIP graph (utils.graphed_forward)
+        self._ws = {}              # fp16 mode: ping-pong and skip buffers of one (B, H, W, device)
 
     def _build(self):
         enc = [(_hip.pack_conv3x3(m.weight), m.bias.detach().float().contiguous(), m.in_channels, m.out_channels)
@@ -30,6 +35,21 @@ class REDNet(nn.Module):
         dec = [(_hip.pack_conv3x3(_hip.deconv_as_conv_weight(m.weight)), m.bias.detach().float().contiguous(),
                 m.in_channels, m.out_channels) for m in (getattr(self, f"deconv{i}") for i in range(1, 16))]
         return enc, dec
+
+    def _build_half(self):
+        convs = [getattr(self, f"conv{i}") for i in range(1, 16)]
+        deconvs = [getattr(self, f"deconv{i}") for i in range(1, 16)]
+
+        def bias(m):
+            return m.bias.detach().float().contiguous()
+        first = (thin_weight(convs[0].weight), bias(convs[0]))
+        enc = [(_hip.pack_conv3x3_h(m.weight), bias(m)) for m in convs[1:]]
+        dec = [(_hip.pack_conv3x3_h(_hip.deconv_as_conv_weight(m.weight)), bias(m)) for m in deconvs[:-1]]
+        last = (thin_weight(_hip.deconv_as_conv_weight(deconvs[-1].weight)), bias(deconvs[-1]))
+        return first, enc, dec, last
+
+    def release_workspace(self):
+        self._ws = {}
 
     def load_synthetic(self, seed=42):
         from .. import synth
@@ -43,6 +63,8 @@ class REDNet(nn.Module):
         require_cuda(x, "REDNet")
         x = x.float().contiguous()
         B, _, H, W = x.shape
+        if self.precision == "fp16":
+            return self._forward_half(x)
         enc, dec = self._cache.get()
         F = self.num_features
 
@@ -67,4 +89,32 @@ class REDNet(nn.Module):
         wp, b, ci, co = dec[14]
         out = new(self.num_channels)
         conv3x3(wp, d, out, ci, co, bias=b, res=x, res_mode=1)      # d15 + x (rednet.py:133-136)
+        return out
+
+    def _forward_half(self, x):
+        B, _, H, W = x.shape
+        first, enc, dec, last = self._cache.get()
+        F = self.num_features
+        # the features the decoder adds back (c2, c4 ... c14) own a buffer each, everything else ping-pongs
+        skips = tuple(f"c{k}" for k in range(2, 15, 2))
+        ws = half_workspace(self._ws, (B, H, W, str(x.device)), ("a", "b") + skips, (B, H, W, F), x.device)
+
+        def other(t):
+            return ws["b"] if t is ws["a"] else ws["a"]
+
+        cur = ws["a"]
+        ops.conv3x3_h_in(first[0], x, cur, self.num_channels, F, bias=first[1], relu1=True)     # c1
+        for k, (wp, b) in enumerate(enc, start=2):                                              # c2..c15
+            nxt = ws[f"c{k}"] if k % 2 == 0 and k < 15 else other(cur)
+            ops.conv3x3_h(wp, cur, nxt, F, F, bias=b, relu1=True)
+            cur = nxt
+        for i, (wp, b) in enumerate(dec, start=1):                                              # deconv1..14
+            nxt = other(cur)
+            if i % 2 == 1:                                # relu(relu(deconv) + c_{15-i})
+                ops.conv3x3_h(wp, cur, nxt, F, F, bias=b, relu1=True, res=ws[f"c{15 - i}"], res_mode=1, relu2=True)
+            else:
+                ops.conv3x3_h(wp, cur, nxt, F, F, bias=b, relu1=True)
+            cur = nxt
+        out = torch.empty(B, self.num_channels, H, W, dtype=torch.float32, device=x.device)
+        ops.conv3x3_h_out(last[0], cur, out, F, self.num_channels, bias=last[1], res=x, res_mode=1)    # d15 + x
         return out

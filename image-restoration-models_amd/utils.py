@@ -19,6 +19,7 @@ import torch
 from torch.nn import Module
 
 from . import _hip, deblurganv2, dncnn, mair, ops, rednet, restormer
+from .convnet_common import check_precision
 from .configs import PATCH_CONFIG, ROOT_RESULTS_DIR, ROOT_WEIGHTS_DIR
 from .dncnn import DnCNN
 from .rednet import REDNet
@@ -95,21 +96,33 @@ def _restormer_opt(name: str) -> str:
     return os.path.join(_PKG_DIR, 'restormer', 'options', name + '.yml')
 
 
+#: the model families that have the reduced-precision mode (get_model_instance(..., precision="fp16"))
+HALF_PRECISION_FAMILIES = ('DnCNN', 'REDNet')
+
+
 def get_model_instance(task, subtask, model_name, device: torch.device, gray=False,
-                       sigma: int | float | None = None) -> torch.nn.Module:
-    """src/utils.py:216-267: same (task, subtask, model, gray, sigma) -> weights table."""
+                       sigma: int | float | None = None, precision: str = "fp32") -> torch.nn.Module:
+    """src/utils.py:216-267: same (task, subtask, model, gray, sigma) -> weights table.  precision="fp16" (DnCNN and
+    REDNet only, not reference-parity) selects their native-fp16 kernels."""
     model_key = model_name.split(' ')[0]
+    check_precision(precision, "get_model_instance")
+    if precision == "fp16" and model_key not in HALF_PRECISION_FAMILIES:
+        raise ValueError(f"precision='fp16' is available for {' and '.join(HALF_PRECISION_FAMILIES)} only, "
+                         f"not for {model_key}")
     if model_key == 'REDNet':
         if task == 'denoising' and subtask == 'gaussian' and sigma is not None:
-            return rednet.get_model(f'{ROOT_WEIGHTS_DIR}/REDNet/{sigma}.pt', device)
+            return rednet.get_model(f'{ROOT_WEIGHTS_DIR}/REDNet/{sigma}.pt', device, precision=precision)
     elif model_key == 'DnCNN':
         if task == 'denoising' and subtask == 'gaussian':
             if gray:
                 if sigma is not None:
-                    return dncnn.get_model(f'{ROOT_WEIGHTS_DIR}/DnCNN/dncnn_{sigma}.pth', 1, 17, device)
-                return dncnn.get_model(f'{ROOT_WEIGHTS_DIR}/DnCNN/dncnn_gray_blind.pth', 1, 20, device)
+                    return dncnn.get_model(f'{ROOT_WEIGHTS_DIR}/DnCNN/dncnn_{sigma}.pth', 1, 17, device,
+                                           precision=precision)
+                return dncnn.get_model(f'{ROOT_WEIGHTS_DIR}/DnCNN/dncnn_gray_blind.pth', 1, 20, device,
+                                       precision=precision)
             if sigma is None:
-                return dncnn.get_model(f'{ROOT_WEIGHTS_DIR}/DnCNN/dncnn_color_blind.pth', 3, 20, device)
+                return dncnn.get_model(f'{ROOT_WEIGHTS_DIR}/DnCNN/dncnn_color_blind.pth', 3, 20, device,
+                                       precision=precision)
     elif model_key == 'Restormer':
         kind = 'Gray' if gray else 'Color'
         if task == 'denoising':

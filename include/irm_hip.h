@@ -526,6 +526,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
                          const float* nw, const float* nb, const float* z, long z_bs, float* out, long out_bs,
                          int B, int L, int D, int nchunk, float eps, irm_stream_t stream);
 
+/* ---- fp16 inference mode of the conv stacks: irm_conv3x3_h_in_f32, irm_conv3x3_h_f16, irm_conv3x3_h_out_f32 */
+#include "irm_hip_half.h"
+
 #ifdef __cplusplus
 }
 #endif
