@@ -8,7 +8,8 @@ model's magnitude (packed by the same packer), inputs scaled to the recorded max
 layout.  The replay must log the same kernel and tag, and pass the bar of tests/test_gpu_precision.py image by image:
 e <= K * e_32 + F * max|y64| with y64 in float64 and y32 in float32 (TF32 off), both on the device; the emulated
 conv (conv3x3_f16x3) is held to its op-test bar instead, 2x the exact-f32 conv kernel on the same inputs.  Every GEMM launch
-recorded must also be a variant tests/test_gpu_gemm_variants.py tests."""
+recorded must also be a variant tests/test_gpu_gemm_variants.py tests, and every conv launch a variant and a pass structure
+tests/test_gpu_conv_variants.py tests."""
 import os
 import re
 
@@ -17,6 +18,7 @@ import torch
 import torch.nn.functional as TF
 
 from irm_amd import _hip, deblurganv2, dncnn, mair, ops, rednet, restormer
+from test_gpu_conv_variants import CASE_STRUCTURES, CONV_VARIANTS, expected_conv_variant, pass_structure, passes_per_group
 from test_gpu_gemm_variants import VARIANTS, expected_variant
 from test_gpu_precision import F, K
 
@@ -397,3 +399,33 @@ def test_production_gemms_are_in_the_grid(dev, monkeypatch, name):
         print(f"{name:24s} {launch:70s} -> {v}")
     missing = sorted({f"{v} ({launch})" for launch, v in out if v not in VARIANTS})
     assert not missing, f"production runs variants the grid does not test: {missing}"
+
+
+def _conv_variant(r):
+    """(CONV_VARIANTS entry, pass structure) a recorded conv launch maps to, from its kernel group and plan (tag) and its
+    buffers; packed weights are whole allocations, 16-byte aligned."""
+    d = r["ds"]
+    kind = {"conv3x3_thin": "thin", "conv3x3_f16x3": "split", "conv3x3": "exact"}[r["launch"].split(" ")[0]]
+    tag = dict(re.findall(r"\b(ct|yg)(\d+)\b", r["launch"]))
+    ct = int(tag["ct"]) if kind != "thin" else None
+    res = d["res"]
+    v = expected_conv_variant(kind, r["ci"], r["co"], d["x"]["shape"][3], ct, d["x"]["stride"][0], d["y"]["stride"][0],
+                              res["stride"][0] if res is not None else 0, d["x"]["align"] == 0, d["y"]["align"] == 0,
+                              res is None or res["align"] == 0, True)
+    if v is None:
+        return None, None
+    structure = "single" if kind == "thin" else pass_structure(passes_per_group((r["co"] + 15) // 16, ct, int(tag["yg"])))
+    return v[0], structure
+
+
+@pytest.mark.parametrize("name", list(WORKLOADS))
+def test_production_convs_are_in_the_grid(dev, monkeypatch, name):
+    """Every conv launch production issues maps to a CONV_VARIANTS entry, and runs a pass structure (a single pass per
+    workgroup, or several with an even or an uneven split over the groups) that variant has a case for."""
+    recs = record(name, dev, monkeypatch)
+    out = [(r["launch"], *_conv_variant(r)) for r in recs if r["op"] == "conv"]
+    for launch, v, structure in out:
+        print(f"{name:24s} {launch:70s} -> {v} {structure}")
+    missing = sorted({f"{v} {structure} ({launch})" for launch, v, structure in out
+                      if v not in CONV_VARIANTS or structure not in CASE_STRUCTURES[v]})
+    assert not missing, f"production runs conv variants or pass structures the grid does not test: {missing}"

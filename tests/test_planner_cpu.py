@@ -3,6 +3,7 @@ they make must be one the C switches accept, with no workgroup group left withou
 import pytest
 
 from irm_amd import ops
+from test_gpu_conv_variants import CASE_STRUCTURES, CONV_VARIANTS, expected_conv_variant, pass_structure, passes_per_group
 from test_gpu_gemm_variants import VARIANTS, expected_variant
 
 GEMM_CTS = {3, 4, 6, 8, 9}               # gemm_entry (gemm_pw.hip)
@@ -11,7 +12,9 @@ CONV_F16_CTS = {1, 2, 3, 4, 8, 12}       # irm_conv3x3_f16x3_f32 (conv3x3_f16.hi
 
 # (N, B): single small images up to the 1280 x 720 frame and the bench batches
 GEMM_SHAPES = [(16, 1), (240, 1), (4096, 1), (4096, 9), (65536, 1), (65536, 24), (1280 * 720, 1)]
-CONV_SHAPES = [(4, 4, 1), (8, 32, 1), (13, 21, 2), (64, 64, 1), (128, 128, 9), (256, 256, 8), (720, 1280, 1)]
+# with W % 4 != 0 (a BSD68 image, a 1023-wide one) the exact planner's launches run on the generic kernel
+CONV_SHAPES = [(4, 4, 1), (8, 32, 1), (13, 21, 2), (64, 64, 1), (128, 128, 9), (256, 256, 8), (720, 1280, 1),
+               (321, 481, 1), (1023, 1024, 1), (1024, 1023, 1)]
 
 
 def _ms(step):
@@ -77,6 +80,16 @@ def test_conv_plan_sweep(H, W, B, split):
         assert 1 <= yg <= nchunks and _groups_nonempty(nchunks, yg), (co, H, W, B, ct, yg)
         if split:
             assert nchunks % yg == 0, (co, H, W, B, ct, yg)      # equal passes per group
+            if W % 4:
+                continue                                         # ops.conv3x3 sends such an image to the exact kernel
+        # dense tensors: the kernel the plan lands on (tests/test_gpu_conv_variants.py tests it), and its pass structure
+        bs = 64 * H * W
+        v = expected_conv_variant("split" if split else "exact", 64, co, W, ct, bs, co * H * W, 0, True, True, True, True)
+        assert v is not None and v[0] in CONV_VARIANTS, (co, H, W, B, ct, yg, v)
+        assert v == expected_conv_variant("split" if split else "exact", 64, co, W, ct, bs, co * H * W, co * H * W, True,
+                                          True, True, True)     # ... with a residual too
+        structure = pass_structure(passes_per_group(mt, ct, yg))
+        assert structure in CASE_STRUCTURES[v[0]], (co, H, W, B, ct, yg, v, structure)
 
 
 def test_conv_plan_explicit_values_kept():
