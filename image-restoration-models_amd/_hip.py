@@ -79,6 +79,13 @@ SIGNATURES_HALF = {
     "irm_conv3x3_h_out_f32": [_P, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P],
 }
 
+#: float32 frames in the tiled-patch loop (tiler_f32.hip), mirrors include/irm_hip_frames.h one to one
+SIGNATURES_FRAMES = {
+    "irm_frame_minmax_f32": [_P, _L, _P, _P, _L, _P],
+    "irm_tile_extract_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "irm_window_blend_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -97,7 +104,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(make -C image-restoration-models_amd/csrc).  There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF}.items():
+        for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

@@ -849,6 +849,29 @@ def _window_on(device, ps: int) -> torch.Tensor:
     return _WINDOW_CACHE[key]
 
 
+_UNIT_RANGE_CACHE: dict = {}
+#: floats of workspace irm_frame_minmax_f32 never needs more than (include/irm_hip_frames.h)
+_MINMAX_WS_FLOATS = 2048
+
+
+def _unit_range_on(device) -> torch.Tensor:
+    """The constant value range (lo, hi, mul) = (0, 1, 1) of a frame that is in [0, 1] by contract, as the three-float
+    device buffer the float32 tiler kernels read: no division on the way in, clip(v, 0, 1) on the way out."""
+    key = str(device)
+    if key not in _UNIT_RANGE_CACHE:
+        _UNIT_RANGE_CACHE[key] = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float32).to(device)
+    return _UNIT_RANGE_CACHE[key]
+
+
+def _frame_range_on(img_dev: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """(min, max, max) of a float32 device frame, the reference's value range for a float image (utils.py:159-171,
+    450-454), as a three-float device buffer; enqueued, never read by the host.  Non-finite values are outside the
+    contract."""
+    rng = torch.empty(3, dtype=torch.float32, device=img_dev.device)
+    _hip.call("irm_frame_minmax_f32", _hip.ptr(img_dev), img_dev.numel(), _hip.ptr(rng), _hip.ptr(ws), ws.numel())
+    return rng
+
+
 #: bound of the per-model graph cache: entries, and bytes of graph-owned memory (static buffers + workspaces)
 _GRAPH_MAX_ENTRIES, _GRAPH_MAX_BYTES = 8, 96 << 30
 
@@ -915,27 +938,45 @@ def graphed_forward(model: Module, x: torch.Tensor) -> torch.Tensor:
 
 def tiled_forward_device(model: Module, img_dev: torch.Tensor, patch_size, patch_overlap, pad8: bool,
                          noise_sigma=None, target_dev: torch.Tensor | None = None, max_batch: int = 8,
-                         keep_tiles: list | None = None, hooks: str | None = None):
-    """Device pipeline for one uint8/uint16 HWC image already on the GPU.
+                         keep_tiles: list | None = None, hooks: str | None = None, unit_range: bool = False,
+                         out: str = "same"):
+    """Device pipeline for one uint8/uint16/float32 HWC image already on the GPU.
 
-    Returns (out uint8/uint16 HWC device tensor, sse device tensor or None).
+    Returns (out HWC device tensor, sse device tensor or None): uint8/uint16 like the input, float32 for a float32
+    input or with out="float32" (tiled_forward_device_batch has the rules for float frames).
     Nothing here synchronises with the host.  hooks="deblurganv2" selects that model's normalize / pad /
     postprocess (src/deblurganv2/__init__.py:11-28) instead of /255 and the reflect pad to 8.
     """
     outs = tiled_forward_device_batch(model, [img_dev], patch_size, patch_overlap, pad8, noise_sigma,
-                                      None if target_dev is None else [target_dev], max_batch, keep_tiles, hooks)
+                                      None if target_dev is None else [target_dev], max_batch, keep_tiles, hooks,
+                                      unit_range, out)
     return outs[0]
 
 
 def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_overlap, pad8: bool,
                                noise_sigma=None, targets_dev: list | None = None, max_batch: int = 8,
-                               keep_tiles: list | None = None, hooks: str | None = None) -> list:
+                               keep_tiles: list | None = None, hooks: str | None = None, unit_range: bool = False,
+                               out: str = "same") -> list:
     """The device pipeline for SEVERAL images of one shape at once (throughput serving; the reference's loop,
     src/utils.py:353-454, is one image and one tile at a time): the tiles of all images form one batch axis, so the
     low-resolution levels of the network fill the GPU and every kernel's tail is paid once per batch instead of once per
     image (Restormer, 1280x720: 53.8 ms for one frame, 52.3 ms per frame for two, tools/bench_batch.py).  Each image is
     extracted, blended, requantised and scored exactly as in the single-image call - a tile's result does not depend on
-    its batch (tests/test_gpu_fullsize.py) - and the list of (out, sse) pairs is returned in order."""
+    its batch (tests/test_gpu_fullsize.py) - and the list of (out, sse) pairs is returned in order.
+
+    Float frames.  A float32 [H, W, C] frame gives a float32 [s H, s W, min(3, C)] frame.  unit_range=False is the
+    reference's rule for a float image (utils.py:159-171, 450-454): the frame's own min / max are reduced on the device
+    (irm_frame_minmax_f32), the frame is divided by max where max > 1, and the result is clip(v * max, min, max) - a max
+    below 1 multiplies too, as it does there.  unit_range=True takes the frame as in [0, 1] by contract: no reduction,
+    no division, the result is clip(v, 0, 1).  out="float32" returns the float32 frame for a uint8 / uint16 input as
+    well: extracted as always (/255, /65535), blended with the unit range and not rounded; out="uint8" / "uint16" (the
+    bit pattern in an int16 tensor, as on the way in) requantises a float32 frame that is in [0, 1] (unit_range=True) as
+    an integer frame is: rint(clip(v * peak, 0, peak)).  A float32 result has no
+    integer squared error (targets_dev raises ValueError), and hooks="deblurganv2" is defined on raw integer values
+    with an integer result (a float32 input or out="float32" raises ValueError).  Non-finite values in a float frame
+    are outside the contract."""
+    if out not in ("same", "float32", "uint8", "uint16"):
+        raise ValueError(f"out must be 'same', 'float32', 'uint8' or 'uint16', not {out!r}")
     norm_mean, norm_inv_std, post_scale, post_shift = 0.0, 1.0, 1.0, 0.0
     pad_mode = "reflect8" if pad8 else "none"
     if hooks == "deblurganv2":
@@ -950,6 +991,21 @@ def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_
     if any(tuple(im.shape) != (h, w, c) or im.dtype != img0.dtype for im in imgs_dev):
         raise ValueError("tiled_forward_device_batch: the images of a batch must share shape and dtype")
     is_u16 = img0.dtype in (torch.uint16, torch.int16)
+    is_f32 = img0.dtype == torch.float32
+    if img0.dtype.is_floating_point and not is_f32:
+        raise ValueError(f"the device pipeline takes uint8, uint16 and float32 frames, not {img0.dtype}")
+    own = "float32" if is_f32 else "uint16" if is_u16 else "uint8"
+    kind = own if out == "same" else out
+    f32_out = kind == "float32"
+    if not f32_out and kind != own and not (is_f32 and unit_range):
+        raise ValueError(f"out={out!r} for a {own} frame: an integer result comes from a frame of that type, or from a "
+                         "float32 frame with unit_range=True")
+    out_dtype = img0.dtype if kind == own else torch.uint8 if kind == "uint8" else torch.int16
+    out_u16 = kind == "uint16"
+    if (is_f32 or f32_out) and hooks == "deblurganv2":
+        raise ValueError("hooks='deblurganv2' normalises raw integer values and requantises: no float32 frames")
+    if f32_out and targets_dev is not None:
+        raise ValueError("targets_dev needs an integer result: a float32 frame has no integer squared error")
     dev = img0.device
     if patch_size:
         ps = min(patch_size, max(h, w))
@@ -973,7 +1029,15 @@ def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_
         np.random.seed(seed=0)                       # utils.py:33: same field for every tile
         noise = torch.from_numpy(np.random.normal(0, noise_sigma / 255., (th, tw, c))).to(dev)
     tiles = torch.empty(K * T, c, ph, pw, dtype=torch.float32, device=dev)
+    ranges = [_unit_range_on(dev)] * K if (is_f32 or f32_out) else None
+    if is_f32 and not unit_range:
+        ws = torch.empty(_MINMAX_WS_FLOATS, dtype=torch.float32, device=dev)      # (one stream: the frames take turns)
+        ranges = [_frame_range_on(im, ws) for im in imgs_dev]
     for k, im in enumerate(imgs_dev):
+        if is_f32:
+            _hip.call("irm_tile_extract_f32", _hip.ptr(im), _hip.ptr(ranges[k]), _hip.ptr(org), _hip.ptr(noise),
+                      _hip.ptr(tiles[k * T:]), h, w, c, th, tw, ph, pw, T, int(pad_mode == "zero32"))
+            continue
         _hip.call("irm_tile_extract", _hip.ptr(im), int(is_u16), _hip.ptr(org), _hip.ptr(noise),
                   _hip.ptr(tiles[k * T:]), h, w, c, th, tw, ph, pw, T, float(norm_mean), float(norm_inv_std),
                   int(pad_mode == "zero32"))
@@ -1025,20 +1089,28 @@ def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_
         keep_tiles.append(pred[:, :c_out, :s * th, :s * tw].clone())
     results = []
     for k in range(K):
-        out = torch.empty(s * h, s * w, c_out, dtype=img0.dtype, device=dev)
+        if f32_out:
+            # extents in input pixels, predictions and window at output scale (irm_hip_frames.h)
+            frame = torch.empty(s * h, s * w, c_out, dtype=torch.float32, device=dev)
+            _hip.call("irm_window_blend_f32", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, s * ps)),
+                      _hip.ptr(frame), _hip.ptr(ranges[k]), h, w, c_out, pred.shape[1], th, tw, pred.shape[2] // s,
+                      pred.shape[3] // s, ps, T, s)
+            results.append((frame, None))
+            continue
+        frame = torch.empty(s * h, s * w, c_out, dtype=out_dtype, device=dev)
         sse, tgt = None, None
         if targets_dev is not None and targets_dev[k] is not None:
             sse, tgt = torch.zeros(1, dtype=torch.int64, device=dev), targets_dev[k]
         if s > 1:
             # tiles cut at input scale, blended at output scale: origins x s, window of s * ps (irm_hip.h)
             _hip.call("irm_window_blend_scaled", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, s * ps)),
-                      _hip.ptr(out), int(is_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw, ph, pw,
+                      _hip.ptr(frame), int(out_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw, ph, pw,
                       ps, T, s, post_scale, post_shift)
         else:
-            _hip.call("irm_window_blend", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, ps)), _hip.ptr(out),
-                      int(is_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw,
+            _hip.call("irm_window_blend", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, ps)), _hip.ptr(frame),
+                      int(out_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw,
                       pred.shape[2], pred.shape[3], ps, T, post_scale, post_shift)
-        results.append((out, sse))
+        results.append((frame, sse))
     return results
 
 
@@ -1048,10 +1120,12 @@ def run_model_inference(model: Module, input_img: np.ndarray, device: torch.devi
                         postprocess: Callable | None = None, progress_bar=None):
     """Run inference; returns (prediction, inference_time_ms) like src/utils.py:353-454.
 
-    uint8/uint16 images with the stock normalize/pad hooks take the device
-    pipeline; anything else (float images, custom hooks) takes a per-tile loop
-    with the reference's host-side blend - the model forward is the HIP path
-    in both."""
+    uint8/uint16 and float32 HWC images with the stock normalize/pad hooks take
+    the device pipeline (a float32 image by the reference's rule for float
+    images: divided by its max where that exceeds 1, clipped to its own min /
+    max, float32 out); anything else (float64 / float16 images, custom hooks,
+    DeblurGANv2 on a float image) takes a per-tile loop with the reference's
+    host-side blend - the model forward is the HIP path in both."""
     output_img, ms, _ = _run_model_inference(model, input_img, device, normalize, patch_size, patch_overlap,
                                              need_degradation, noise_level, pad, postprocess)
     return output_img, ms
@@ -1059,8 +1133,8 @@ def run_model_inference(model: Module, input_img: np.ndarray, device: torch.devi
 
 def _run_model_inference(model, input_img, device, normalize=normalize, patch_size=None, patch_overlap=32,
                          need_degradation=False, noise_level=None, pad=None, postprocess=None):
-    """run_model_inference that also hands back the device pipeline's output tensor (uint8, or uint16 as int16 bits;
-    None after the per-tile host loop): (prediction, inference_time_ms, out_dev).  The time covers the same work as
+    """run_model_inference that also hands back the device pipeline's output tensor (uint8, uint16 as int16 bits, or
+    float32; None after the per-tile host loop): (prediction, inference_time_ms, out_dev).  The time covers the same work as
     run_model_inference's, input upload through output download."""
     start_time = time.time()
     out = None
@@ -1069,11 +1143,13 @@ def _run_model_inference(model, input_img, device, normalize=normalize, patch_si
     dg = (normalize is deblurganv2.normalize and pad is deblurganv2.pad and postprocess is deblurganv2.postprocess
           and input_img.dtype == np.uint8)
     stock = dg or (normalize is globals()['normalize'] and (pad is None or pad is globals()['pad'])
-                   and postprocess is None and input_img.dtype in (np.uint8, np.uint16))
+                   and postprocess is None
+                   and (input_img.dtype in (np.uint8, np.uint16)
+                        or (input_img.dtype == np.float32 and input_img.ndim == 3)))
     with torch.no_grad():
         if stock:
             dev = torch.device(device)
-            src = input_img if input_img.dtype == np.uint8 else input_img.view(np.int16)
+            src = input_img.view(np.int16) if input_img.dtype == np.uint16 else input_img
             img_dev = torch.from_numpy(np.ascontiguousarray(src)).to(dev)
             sigma = noise_level if (need_degradation and noise_level is not None) else None
             out, _ = tiled_forward_device(model, img_dev, patch_size, patch_overlap, pad is not None, sigma,
@@ -1148,3 +1224,69 @@ def _get_model_prediction(model, input_image, device, patch_size, patch_overlap,
     if isinstance(model, _PAD8_MODELS):
         return _run_model_inference(model, input_image, device, pad=pad, **kw)
     return _run_model_inference(model, input_image, device, **kw)
+
+
+def _chain_hooks(model) -> bool:
+    """pad8 of a chain stage, by the model class as _get_model_prediction dispatches; DeblurGANv2 is refused."""
+    if isinstance(model, FPNMobileNet) or type(model).__module__.startswith(deblurganv2.__name__ + "."):
+        raise ValueError("run_model_chain: DeblurGANv2 normalises raw integer values and has no float32 frames; "
+                         "run it on its own with get_model_prediction")
+    return isinstance(model, _PAD8_MODELS)
+
+
+def run_model_chain(stages, input_img: np.ndarray, device: torch.device, need_degradation=False, noise_level=None,
+                    out: str = "same"):
+    """Run several restoration models one after another on one frame: denoise then deblur, denoise then
+    super-resolve.  Returns (image, inference_time_ms), the time from input upload through output download.
+
+    `stages` is a sequence of (model, patch_config) with patch_config = {'patch_size': .., 'patch_overlap': ..} as
+    get_patch_config returns it.  Every stage is the device pipeline of run_model_inference with the hooks
+    get_model_prediction picks for the model class (reflect pad to 8 for Restormer / MaIR); a DeblurGANv2 model
+    raises ValueError.  The frame is uploaded once and downloaded once.
+
+    The reference has no chain; these semantics are this package's own:
+      1. the first stage reads the input as run_model_inference does (uint8 / 255, uint16 / 65535); a float32 input is
+         taken as in [0, 1] already (unit_range=True of tiled_forward_device: no division by its max);
+      2. every frame between two stages is float32, clipped to [0, 1] and never rounded to 255 levels - the next model
+         does not see a quantisation step as new noise - and stays on the device;
+      3. need_degradation / noise_level apply to the first stage only;
+      4. the last stage requantises to the input's dtype as run_model_inference does, or returns the float32 frame in
+         [0, 1] for a float32 input or with out="float32".
+    Super-resolving stages enlarge the frame for the stages after them; a 6-channel first stage yields 3 channels.  A
+    one-stage chain on a uint8 / uint16 frame returns exactly what get_model_prediction returns."""
+    try:
+        stages = [(m, dict(cfg)) for m, cfg in stages]
+    except (TypeError, ValueError):
+        raise ValueError("run_model_chain: stages is a sequence of (model, patch_config) pairs") from None
+    if not stages:
+        raise ValueError("run_model_chain: at least one stage")
+    for m, cfg in stages:
+        if not callable(m) or set(cfg) != {"patch_size", "patch_overlap"}:
+            raise ValueError("run_model_chain: a stage is (model, {'patch_size': .., 'patch_overlap': ..})")
+    pad8 = [_chain_hooks(m) for m, _ in stages]
+    if out not in ("same", "float32"):
+        raise ValueError(f"out must be 'same' or 'float32', not {out!r}")
+    if (not isinstance(input_img, np.ndarray) or input_img.ndim != 3
+            or input_img.dtype not in (np.uint8, np.uint16, np.float32)):
+        raise ValueError("run_model_chain: a uint8, uint16 or float32 [H, W, C] array")
+    if need_degradation and int(getattr(stages[0][0], "upscale", 1) or 1) > 1:
+        raise ValueError("need_degradation with a super-resolution model: the reference defines no SR degradation")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _hip.HipLibraryError("run_model_chain runs on the GPU only (no CPU fallback); pass a 'cuda' device")
+    start_time = time.time()
+    with torch.no_grad():
+        src = input_img.view(np.int16) if input_img.dtype == np.uint16 else input_img
+        frame = torch.from_numpy(np.ascontiguousarray(src)).to(dev)
+        sigma = noise_level if (need_degradation and noise_level is not None) else None
+        last = len(stages) - 1
+        final = "float32" if out == "float32" else str(input_img.dtype)      # the last stage requantises
+        for i, ((m, cfg), p8) in enumerate(zip(stages, pad8)):
+            kind = final if i == last else "float32"
+            frame, _ = tiled_forward_device(m, frame, cfg["patch_size"], cfg["patch_overlap"], p8,
+                                            sigma if i == 0 else None,
+                                            max_batch=getattr(m, 'max_tiles_per_batch', 8), unit_range=True, out=kind)
+        output_img = frame.cpu().numpy()
+    if output_img.dtype == np.int16:
+        output_img = output_img.view(np.uint16)
+    return output_img, (time.time() - start_time) * 1000

@@ -529,6 +529,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- fp16 inference mode of the conv stacks: irm_conv3x3_h_in_f32, irm_conv3x3_h_f16, irm_conv3x3_h_out_f32 */
 #include "irm_hip_half.h"
 
+/* ---- float32 frames in the tiled-patch loop: irm_frame_minmax_f32, irm_tile_extract_f32, irm_window_blend_f32 */
+#include "irm_hip_frames.h"
+
 #ifdef __cplusplus
 }
 #endif
