@@ -15,9 +15,12 @@ import numpy as np
 import torch
 
 from . import synth
-from .utils import (_get_model_prediction, calculate_metrics, calculate_metrics_basicsr,
-                    calculate_metrics_basicsr_device, calculate_metrics_device, calculate_niqe, calculate_niqe_device,
-                    get_model_prediction, get_model_total_parameters, imresize_device, mod_crop)
+from .frames import to_device, to_host
+from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,
+                      calculate_metrics_device, psnr)
+from .niqe import calculate_niqe, calculate_niqe_device
+from .resize import imresize_device, mod_crop
+from .utils import _get_model_prediction, get_model_prediction, get_model_total_parameters
 
 COLUMNS = ['Task', 'Type', 'Dataset', 'Sigma', 'Model', 'Model_Params', 'PSNR', 'SSIM', 'Std_PSNR', 'Std_SSIM',
            'Avg_Time_ms', 'Std_Time_ms']
@@ -64,7 +67,6 @@ def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: s
                 if with_ssim:
                     p, s = calculate_metrics(pred, target_img)
                 else:
-                    from .utils import psnr
                     p, s = psnr(target_img, pred, 255 if pred.dtype == np.uint8 else 65535), float('nan')
         except Exception as e:                                  # noqa: BLE001 (reported, not swallowed)
             if not skip_failed or "out of memory" in str(e).lower():
@@ -87,22 +89,8 @@ def _device_metrics(pred, pred_dev, target_img, device):
     if not isinstance(target_img, np.ndarray) or target_img.dtype not in (np.uint8, np.uint16):
         raise ValueError("metrics='device' needs uint8 or uint16 target frames")
     if pred_dev is None:
-        pred_dev = torch.from_numpy(np.ascontiguousarray(pred.view(np.int16) if pred.dtype == np.uint16 else pred))
-        pred_dev = pred_dev.to(device)
-    tgt = target_img.view(np.int16) if target_img.dtype == np.uint16 else target_img
-    tgt_dev = torch.from_numpy(np.ascontiguousarray(tgt)).to(pred_dev.device)
-    return calculate_metrics_device(pred_dev, tgt_dev)
-
-
-def _to_device(img: np.ndarray, device) -> torch.Tensor:
-    """A uint8 / uint16 host frame on the GPU (uint16 as its int16 bit pattern, as the tiler takes it)."""
-    src = img.view(np.int16) if img.dtype == np.uint16 else img
-    return torch.from_numpy(np.ascontiguousarray(src)).to(device)
-
-
-def _to_host(t: torch.Tensor, dtype) -> np.ndarray:
-    a = t.view(torch.int16).cpu().numpy() if t.dtype == torch.uint16 else t.cpu().numpy()
-    return a.view(np.uint16) if dtype == np.uint16 else a
+        pred_dev = to_device(pred, device)
+    return calculate_metrics_device(pred_dev, to_device(target_img, pred_dev.device))
 
 
 def sr_pairs(hr_loader, scale: int, device):
@@ -117,8 +105,8 @@ def sr_pairs(hr_loader, scale: int, device):
         if not isinstance(hr, np.ndarray) or hr.dtype not in (np.uint8, np.uint16):
             raise ValueError("sr_pairs needs uint8 or uint16 HR frames")
         hr = np.ascontiguousarray(mod_crop(hr, scale))
-        lr = imresize_device(_to_device(hr, device), 1.0 / scale, out="same")
-        yield _to_host(lr, hr.dtype), hr, name
+        lr = imresize_device(to_device(hr, device), 1.0 / scale, out="same")
+        yield to_host(lr), hr, name
 
 
 def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, task: str = "super-resolution",
@@ -151,8 +139,8 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
         try:
             if model is None:
                 start = time.time()
-                pred_dev = imresize_device(_to_device(lr, device), scale, out="same")
-                pred = _to_host(pred_dev, lr.dtype)
+                pred_dev = imresize_device(to_device(lr, device), scale, out="same")
+                pred = to_host(pred_dev)
                 ms = (time.time() - start) * 1000
             else:
                 pred, ms, pred_dev = _get_model_prediction(model, lr, device, **patch_config)
@@ -160,8 +148,8 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
                 raise ValueError(f"prediction {pred.shape} for an HR frame {hr.shape}")
             if metrics == "device":
                 if pred_dev is None:
-                    pred_dev = _to_device(pred, device)
-                p, s = calculate_metrics_basicsr_device(pred_dev, _to_device(hr, pred_dev.device), crop, test_y_channel,
+                    pred_dev = to_device(pred, device)
+                p, s = calculate_metrics_basicsr_device(pred_dev, to_device(hr, pred_dev.device), crop, test_y_channel,
                                                         channel_order)
             else:
                 p, s = calculate_metrics_basicsr(pred, hr, crop, test_y_channel, channel_order)
@@ -209,7 +197,7 @@ def evaluate_blind(model, loader, device, patch_config: dict, *, niqe_params, cr
                 if not isinstance(pred, np.ndarray) or pred.dtype not in (np.uint8, np.uint16):
                     raise ValueError("metrics='device' needs uint8 or uint16 frames")
                 if pred_dev is None:
-                    pred_dev = _to_device(pred, device)
+                    pred_dev = to_device(pred, device)
                 q = calculate_niqe_device(pred_dev, crop_border, niqe_params, channel_order=channel_order)
             else:
                 q = calculate_niqe(pred, crop_border, niqe_params, channel_order=channel_order)

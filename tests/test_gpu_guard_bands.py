@@ -15,7 +15,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from irm_amd import _hip, ensemble, ops, synth, utils
+from irm_amd import _hip, ensemble, ops, resize, synth, utils
 from oracle import mair_ref, tiler_ref
 
 from guards import banded, has_nan, intact, sentinel_out, two_fills
@@ -361,7 +361,7 @@ def test_imresize_bicubic(dev, dtype, C, scale, H, W):
     K = 2
     rng = np.random.default_rng(17)
     frames = _frame(rng, (K, H, W, C), dtype)
-    s, shrink = utils._resize_factor(scale)
+    s, shrink = resize._resize_factor(scale)
     (wh, ih), (ww, iw) = utils.resize_table(H, scale), utils.resize_table(W, scale)
     assert wh.shape[1] == H                                     # the side equals the tap count
     OH, OW = wh.shape[0], ww.shape[0]

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from irm_amd import _hip, harness, utils
+from irm_amd import _hip, harness, niqe, utils
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -82,11 +82,11 @@ def test_roll_wraps_inside_the_block(params):
     block = rng.normal(0.0, 1.0, (96, 96))
     big = rng.normal(0.0, 500.0, (288, 288))
     big[96:192, 96:192] = block
-    assert utils._niqe_block_features(big[96:192, 96:192], gam, r_gam) == utils._niqe_block_features(block, gam, r_gam)
+    assert niqe._niqe_block_features(big[96:192, 96:192], gam, r_gam) == niqe._niqe_block_features(block, gam, r_gam)
     # the partners are the wrapped ones: row 0 pairs with row 95, column 0 with column 95, column 95 with column 0
     probe = np.zeros((96, 96))
     probe[0, 0], probe[95, 95], probe[0, 95], probe[95, 0], probe[95, 1] = 2.0, 3.0, 5.0, 7.0, 11.0
-    prods = [probe * np.roll(probe, s, axis=(0, 1)) for s in utils._NIQE_SHIFTS]
+    prods = [probe * np.roll(probe, s, axis=(0, 1)) for s in niqe._NIQE_SHIFTS]
     assert [float(p[0, 0]) for p in prods] == [2.0 * 5.0, 2.0 * 7.0, 2.0 * 3.0, 2.0 * 11.0]
     calm = rng.normal(120.0, 10.0, (96, 99))
 

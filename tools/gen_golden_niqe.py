@@ -168,6 +168,7 @@ def generate(out_json):
 def device_bound(out_json):
     import torch
     from irm_amd import harness
+    from irm_amd.frames import to_device
     params = utils.load_niqe_params(PARAMS)
     meta = json.load(open(os.path.join(GOLD, "niqe.json")))
     z = np.load(os.path.join(GOLD, "niqe.npz"))
@@ -177,7 +178,7 @@ def device_bound(out_json):
         """`frames`: one frame, or a list of frames of one shape (one call with K = len)."""
         many = isinstance(frames, list)
         stack = frames if many else [frames]
-        up = [harness._to_device(np.ascontiguousarray(f), "cuda:0") for f in stack]
+        up = [to_device(np.ascontiguousarray(f), "cuda:0") for f in stack]
         dev = utils.niqe_features_device(up if many else up[0], crop, params, channel_order=order).cpu().numpy()
         for i, f in enumerate(stack):
             host = utils.niqe_features(utils.niqe_plane(f, crop, "HWC", order), params)

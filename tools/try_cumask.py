@@ -9,7 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import irm_amd  # noqa
-from irm_amd import restormer, synth, utils
+from irm_amd import frames, restormer, synth, utils
 from irm_amd.configs import PATCH_CONFIG
 
 hip = ctypes.CDLL("libamdhip64.so")
@@ -31,9 +31,8 @@ def run(name, streams, steps=6):
     inp, tgt = synth.synth_image_pair(0, 720, 1280, 3)
     img = torch.from_numpy(inp).to(dev)
     if streams:
-        utils._SIDE_STREAMS.clear()
-        for i, s in enumerate(streams):
-            utils._SIDE_STREAMS[(str(dev), i)] = s
+        for i, s in enumerate(streams):                     # what utils._side_stream(dev, i) returns
+            frames._DEVICE_CONSTANTS[("side_stream", str(dev), i)] = s
     for _ in range(2):
         utils.tiled_forward_device(model, img, cfg["patch_size"], cfg["patch_overlap"], True, max_batch=9)
     torch.cuda.synchronize()
