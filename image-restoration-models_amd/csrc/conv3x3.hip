@@ -16,21 +16,15 @@
 // the A operand is the LDS tile shifted by (dy,dx), the B operand the packed
 // weight of that tap:  Wp[tap][mtile][kstep][lane] =
 // W[16 mtile + (lane&15)][4 kstep + (lane>>4)][tap/3][tap%3].
-#include "irm_common.h"
+#include "conv_epilogue.h"
 #include <stdlib.h>
 
 #define CV_TH 8
-#define CV_TW 32
+#define CV_TW IRM_CONV_TW
 #define CV_CK 8
 #define CV_ROWS (CV_TH + 2)
 #define CV_TWP 40
 #define CV_PLANE (CV_ROWS * CV_TWP)   // 400
-
-__device__ __forceinline__ float cv_res(float v, float r, int mode) {
-    if (mode == 1) return v + r;
-    if (mode == 2) return r - v;
-    return fminf(fmaxf(tanhf(v) + r, -1.0f), 1.0f);      // DeblurGANv2 output: fpn_mobilenet.py:68-70
-}
 
 struct ConvArgs {
     const float* Wp;              // packed [9][mtiles][ksteps][64]
@@ -180,69 +174,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(ConvArgs a) {
                     if (y >= a.H || x >= a.W) continue;
                     float v[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v[e] = acc[p][c][e] + bv;
-                        if (a.relu1 == 1) v[e] = fmaxf(v[e], 0.0f);
-                        else if (a.relu1 == 2) v[e] = v[e] > 0.0f ? v[e] : v[e] * a.slope;
-                    }
-                    if (a.store_mode == 0) {
-                        const long off = (long)co * plane + (long)y * a.W + x;
-                        if (a.vec) {
-                            if (a.res_mode) {
-                                const float4 rr = *reinterpret_cast<const float4*>(R + off);
-                                const float rv[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = cv_res(v[e], rv[e], a.res_mode);
-                            }
-                            if (a.relu2) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
-                            }
-                            *reinterpret_cast<float4*>(Y + off) = make_float4(v[0], v[1], v[2], v[3]);
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                if (x + e < a.W) {
-                                    float t = v[e];
-                                    if (a.res_mode) t = cv_res(t, R[off + e], a.res_mode);
-                                    if (a.relu2) t = fmaxf(t, 0.0f);
-                                    Y[off + e] = t;
-                                }
-                            }
-                        }
-                    } else if (a.store_mode == 1) {
-                        // PixelUnshuffle(2): out[co*4 + (y&1)*2 + (x&1)][y/2][x/2]; H, W even
-                        const int oh = a.H >> 1, ow = a.W >> 1;
-                        const long op = (long)oh * ow;
-                        const int oc = co * 4 + (y & 1) * 2;
-                        const long o = (long)(y >> 1) * ow + (x >> 1);
-                        if (a.vec) {
-                            *reinterpret_cast<float2*>(Y + (long)oc * op + o) = make_float2(v[0], v[2]);
-                            *reinterpret_cast<float2*>(Y + (long)(oc + 1) * op + o) = make_float2(v[1], v[3]);
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (x + e < a.W) Y[(long)(oc + (e & 1)) * op + o + (e >> 1)] = v[e];
-                        }
-                    } else if (a.ps_r == 2) {
-                        // PixelShuffle(2): out[co/4][2y + ((co>>1)&1)][2x + (co&1)]
-                        const int ow = a.W * 2;
-                        const long op = (long)a.H * 2 * ow;
-                        const int oc = co >> 2, i = (co >> 1) & 1, jx = co & 1;
-                        float* o = Y + (long)oc * op + (long)(2 * y + i) * ow + 2 * x + jx;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (x + e < a.W) o[2 * e] = v[e];
-                    } else {
-                        // PixelShuffle(r): out[co/r^2][r y + (co/r)%r][r x + co%r]
-                        const int pr = a.ps_r, ow = a.W * pr;
-                        const long op = (long)a.H * pr * ow;
-                        const int oc = co / (pr * pr), i = (co / pr) % pr, jx = co % pr;
-                        float* o = Y + (long)oc * op + (long)(pr * y + i) * ow + pr * x + jx;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (x + e < a.W) o[pr * e] = v[e];
-                    }
+                    for (int e = 0; e < 4; ++e) v[e] = irm_conv_act1(acc[p][c][e] + bv, a);
+                    irm_conv_store<true>(v, co, y, x, plane, Y, R, a, a.vec);
                 }
             }
         }
@@ -371,48 +304,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_ring_kernel(ConvArgs a) {
                     const int x = tx0 + (p & 1) * 16 + g * 4;
                     float v[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        v[e] = acc[p][c][e] + bv;
-                        if (a.relu1 == 1) v[e] = fmaxf(v[e], 0.0f);
-                        else if (a.relu1 == 2) v[e] = v[e] > 0.0f ? v[e] : v[e] * a.slope;
-                    }
+                    for (int e = 0; e < 4; ++e) v[e] = irm_conv_act1(acc[p][c][e] + bv, a);
                     acc[p][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
                     if (!row_ok || y >= a.H || x >= a.W) continue;
-                    if (a.store_mode == 0) {
-                        const long off = (long)co * plane + (long)y * a.W + x;
-                        if (a.res_mode) {
-                            const float4 rr = *reinterpret_cast<const float4*>(R + off);
-                            const float rv[4] = {rr.x, rr.y, rr.z, rr.w};
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = cv_res(v[e], rv[e], a.res_mode);
-                        }
-                        if (a.relu2) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
-                        }
-                        *reinterpret_cast<float4*>(Y + off) = make_float4(v[0], v[1], v[2], v[3]);
-                    } else if (a.store_mode == 1) {
-                        const int oh = a.H >> 1, ow = a.W >> 1;
-                        const long op = (long)oh * ow;
-                        const int oc = co * 4 + (y & 1) * 2;
-                        const long o = (long)(y >> 1) * ow + (x >> 1);
-                        *reinterpret_cast<float2*>(Y + (long)oc * op + o) = make_float2(v[0], v[2]);
-                        *reinterpret_cast<float2*>(Y + (long)(oc + 1) * op + o) = make_float2(v[1], v[3]);
-                    } else if (a.ps_r == 2) {
-                        const int ow = a.W * 2;
-                        const long op = (long)a.H * 2 * ow;
-                        const int oc = co >> 2, i = (co >> 1) & 1, jx = co & 1;
-                        float* o = Y + (long)oc * op + (long)(2 * y + i) * ow + 2 * x + jx;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[2 * e] = v[e];
-                    } else {
-                        const int pr = a.ps_r, ow = a.W * pr;
-                        const long op = (long)a.H * pr * ow;
-                        const int oc = co / (pr * pr), i = (co / pr) % pr, jx = co % pr;
-                        float* o = Y + (long)oc * op + (long)(pr * y + i) * ow + pr * x + jx;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[pr * e] = v[e];
-                    }
+                    irm_conv_store<false>(v, co, y, x, plane, Y, R, a, true);
                 }
             }
             s = 0;
@@ -445,25 +340,11 @@ extern "C" int irm_conv3x3_ep_f32(const float* wp, const float* x, long x_bs, fl
                                   long r_bs, const float* bias, int B, int Ci, int Co, int H, int W, int act1, float slope,
                                   int res_mode, int relu2, int store_mode, int shuffle, int ct, int ygroups,
                                   hipStream_t stream) {
-    if (!wp || !x || !y || B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return IRM_EINVAL;
-    if (res_mode < 0 || res_mode > 3 || (res_mode && !res) || store_mode < 0 || store_mode > 2) return IRM_EINVAL;
-    if (act1 < 0 || act1 > 2 || shuffle < 2 || shuffle > 4) return IRM_EINVAL;
-    if (store_mode != 0 && res_mode != 0) return IRM_EINVAL;
-    if (store_mode == 1 && ((H & 1) || (W & 1))) return IRM_EINVAL;
-    if (store_mode == 2 && (Co % (shuffle * shuffle))) return IRM_EINVAL;
-    if (B > 65535) return IRM_EINVAL;
     ConvArgs a;
-    a.Wp = wp; a.X = x; a.x_bs = x_bs; a.Y = y; a.y_bs = y_bs; a.R = res; a.r_bs = r_bs; a.bias = bias;
-    a.Ci = Ci; a.Co = Co; a.H = H; a.W = W;
-    a.mtiles = (Co + 15) / 16; a.ksteps = 2 * ((Ci + 7) / 8);
-    a.relu1 = act1; a.slope = slope; a.ps_r = shuffle;
-    a.res_mode = res_mode; a.relu2 = relu2; a.store_mode = store_mode;
-    a.tiles_x = (W + CV_TW - 1) / CV_TW;
+    if (int rc = irm_conv_common(a, wp, x, x_bs, y, y_bs, res, r_bs, bias, B, Ci, Co, H, W, act1, slope, res_mode, relu2,
+                                 store_mode, shuffle, ct, ygroups)) return rc;
+    a.ksteps = 2 * ((Ci + 7) / 8);
     a.vec = !(W & 3) && !(y_bs & 3) && !(r_bs & 3) && irm_aligned16(y) && irm_aligned16(res);
-    if (ct <= 0) return IRM_EINVAL;
-    const int nchunks = (a.mtiles + ct - 1) / ct;
-    if (ygroups <= 0) ygroups = 1;
-    if (ygroups > nchunks) ygroups = nchunks;
     const bool fast = a.vec && !(x_bs & 3) && irm_aligned16(x) && irm_aligned16(wp);
     if (fast) {
         switch (ct) {

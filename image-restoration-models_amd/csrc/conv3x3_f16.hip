@@ -13,12 +13,13 @@
 //      ds_read_b128 give the A operands (lane (r, g) = pixel r, channels 8 g .. 8 g + 7); the split weights of 3 taps at a
 //      time stream through a double-buffered LDS area (host packed, scaled by a power of two, L2 resident).
 // Pixels are the MFMA row index, so a lane ends up with 4 consecutive pixels of one output channel: the epilogue (bias,
-// ReLU, residual modes, PixelUnshuffle / PixelShuffle folded into the store) is the one of conv3x3.hip.
-#include "irm_common.h"
+// ReLU, residual modes, PixelUnshuffle / PixelShuffle folded into the store) computes what irm_conv_store<false> of
+// conv_epilogue.h computes, but stays this kernel's own copy (see there); the entry checks are the shared ones.
+#include "conv_epilogue.h"
 
 
 #define CF_TH 8
-#define CF_TW 32
+#define CF_TW IRM_CONV_TW
 #define CF_PLANE 400                    // raw plane: 10 rows x 40 floats (columns tx0 - 4 .. tx0 + 35)
 #define CF_HC 34
 #define CF_NP 340
@@ -28,7 +29,7 @@
 #define CF_NRAW 7                       // raw DMA instructions per lane and stage (3200 chunks / 512 lanes)
 
 
-__device__ __forceinline__ float cf_res(float v, float r, int mode) {
+__device__ __forceinline__ float cf_res(float v, float r, int mode) {      // irm_conv_res for mode 1 ... 3
     if (mode == 1) return v + r;
     if (mode == 2) return r - v;
     return fminf(fmaxf(tanhf(v) + r, -1.0f), 1.0f);
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_f16x3_kernel(ConvF16Args a) {
                 }
             }
         }
-        // ---- epilogue (as conv3x3_ring_kernel)
+        // ---- epilogue: irm_conv_act1 / irm_conv_store<false> written out (conv_epilogue.h says why)
 #pragma unroll
         for (int c = 0; c < TT; ++c) {
             const int co = (mt0 + c) * 16 + r;
@@ -259,22 +260,12 @@ extern "C" int irm_conv3x3_f16x3_ep_f32(const float* wp_split, float inv_scale, 
                                         long y_bs, const float* res, long r_bs, const float* bias, int B, int Ci, int Co,
                                         int H, int W, int act1, float slope, int res_mode, int relu2, int store_mode,
                                         int shuffle, int ct, int ygroups, hipStream_t stream) {
-    if (!wp_split || !x || !y || B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return IRM_EINVAL;
-    if (res_mode < 0 || res_mode > 3 || (res_mode && !res) || store_mode < 0 || store_mode > 2) return IRM_EINVAL;
-    if (act1 < 0 || act1 > 2 || shuffle < 2 || shuffle > 4) return IRM_EINVAL;
-    if (store_mode != 0 && res_mode != 0) return IRM_EINVAL;
-    if (store_mode == 1 && ((H & 1) || (W & 1))) return IRM_EINVAL;
-    if (store_mode == 2 && (Co % (shuffle * shuffle))) return IRM_EINVAL;
-    if (B > 65535 || (W & 3) || (x_bs & 3) || (y_bs & 3) || (r_bs & 3)) return IRM_EINVAL;
-    if (!irm_aligned16(x) || !irm_aligned16(y) || !irm_aligned16(res) || !irm_aligned16(wp_split)) return IRM_EINVAL;
     ConvF16Args a;
-    a.Wp = wp_split; a.X = x; a.x_bs = x_bs; a.Y = y; a.y_bs = y_bs; a.R = res; a.r_bs = r_bs; a.bias = bias;
-    a.Ci = Ci; a.Co = Co; a.H = H; a.W = W; a.mtiles = (Co + 15) / 16; a.S = (Ci + 31) / 32;
-    a.relu1 = act1; a.res_mode = res_mode; a.relu2 = relu2; a.store_mode = store_mode;
-    a.tiles_x = (W + CF_TW - 1) / CF_TW; a.inv_s = inv_scale; a.slope = slope; a.ps_r = shuffle;
-    const int nchunks = (a.mtiles + ct - 1) / (ct > 0 ? ct : 1);
-    if (ygroups <= 0) ygroups = 1;
-    if (ygroups > nchunks) ygroups = nchunks;
+    if (int rc = irm_conv_common(a, wp_split, x, x_bs, y, y_bs, res, r_bs, bias, B, Ci, Co, H, W, act1, slope, res_mode,
+                                 relu2, store_mode, shuffle, ct, ygroups)) return rc;
+    if ((W & 3) || (x_bs & 3) || (y_bs & 3) || (r_bs & 3)) return IRM_EINVAL;
+    if (!irm_aligned16(x) || !irm_aligned16(y) || !irm_aligned16(res) || !irm_aligned16(wp_split)) return IRM_EINVAL;
+    a.S = (Ci + 31) / 32; a.inv_s = inv_scale;
     switch (ct) {                     // output tiles per pass: 1 ... 4 (one weight chunk), 8 / 12 (2 / 3 chunks of 4)
         case 1: return launch_conv_f16<1>(a, B, ygroups, stream);
         case 2: return launch_conv_f16<2>(a, B, ygroups, stream);

@@ -7,7 +7,7 @@
 // Work item = 4 consecutive columns x RS rows (16-byte row accesses, 3-row register window); the weights of a wave are
 // wave-uniform (scalar loads).  Zero pad 1, stride 1, W % 4 == 0, 16-byte aligned rows; epilogue as irm_conv3x3_f32
 // (bias, relu1, res_mode 1 / 2 / 3, relu2), store_mode 0 only.
-#include "irm_common.h"
+#include "conv_epilogue.h"
 
 struct ThinArgs {
     const float* w;                // [Co][Ci][3][3]
@@ -36,9 +36,7 @@ __device__ __forceinline__ void thin_row(const float* plane, int row, int H, int
 __device__ __forceinline__ float thin_epilogue(float v, float bias, float r, const ThinArgs& a) {
     v += bias;
     if (a.relu1) v = fmaxf(v, 0.0f);
-    if (a.res_mode == 1) v += r;
-    else if (a.res_mode == 2) v = r - v;
-    else if (a.res_mode == 3) v = fminf(fmaxf(tanhf(v) + r, -1.0f), 1.0f);
+    v = irm_conv_res(v, r, a.res_mode);
     if (a.relu2) v = fmaxf(v, 0.0f);
     return v;
 }

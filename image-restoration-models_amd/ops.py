@@ -157,15 +157,9 @@ def gemm1x1(wp: torch.Tensor, x: torch.Tensor, y: torch.Tensor, M: int, K: int, 
                                ygroups=ygroups)
     nbytes = 4.0 * B * N * (K + M + (M if res is not None else 0) + (2 if stats is not None else 0)
                             + (2 if stats_out is not None else 0))
-    if split:
-        # wp from _hip.pack_gemm_weight_split: fp32 emulation on the fp16 matrix cores (no residual)
-        _launch("gemm1x1_f16x3", 2.0 * B * M * K * N, nbytes, "irm_gemm1x1_f16x3_f32", _hip.ptr(wp), int(w_bs), _hip.ptr(x), _bs(x),
-                _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), _hip.ptr(stats), _hip.ptr(lnw),
-                _hip.ptr(lnb), int(ln_mode), int(act), B, M, K, N, ct, ygroups, _hip.ptr(stats_out), float(eps),
-                _hip.ptr(res_scale),
-                tag=f"M{M} K{K} N{N} B{B} ln{int(ln_mode)} res{int(res is not None)} ct{ct} yg{ygroups}")
-        return
-    _launch("gemm1x1", 2.0 * B * M * K * N, nbytes, "irm_gemm1x1_f32", _hip.ptr(wp), int(w_bs), _hip.ptr(x), _bs(x),
+    # split: wp from _hip.pack_gemm_weight_split, fp32 emulation on the fp16 matrix cores (no residual)
+    kernel, entry = ("gemm1x1_f16x3", "irm_gemm1x1_f16x3_f32") if split else ("gemm1x1", "irm_gemm1x1_f32")
+    _launch(kernel, 2.0 * B * M * K * N, nbytes, entry, _hip.ptr(wp), int(w_bs), _hip.ptr(x), _bs(x),
             _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), _hip.ptr(stats), _hip.ptr(lnw),
             _hip.ptr(lnb), int(ln_mode), int(act), B, M, K, N, ct, ygroups, _hip.ptr(stats_out), float(eps),
             _hip.ptr(res_scale), tag=f"M{M} K{K} N{N} B{B} ln{int(ln_mode)} res{int(res is not None)} ct{ct} yg{ygroups}")
@@ -285,13 +279,9 @@ def dwgemm(wp, dwp, x, y, M: int, K: int, *, gate: bool, res=None, bias=None, w_
     nbytes = 4.0 * B * N * ((2 * K if gate else K) + M + (M if res is not None else 0)
                             + (2 if stats_out is not None else 0))
     flops = B * N * (2.0 * M * K + (36.0 if gate else 18.0) * K)
-    if split:
-        # wp from _hip.pack_gemm_weight_split: the 1x1 part as an fp32 emulation on the fp16 matrix cores
-        _launch("dwgemm_f16x3", flops, nbytes, "irm_dwgemm_f16x3_f32", _hip.ptr(wp), int(w_bs), _hip.ptr(dwp), _hip.ptr(x), _bs(x),
-                _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), int(bool(gate)), B, M, K, H, W,
-                _hip.ptr(stats_out), float(eps), tag=f"M{M} K{K} {H}x{W} B{B} gate{int(bool(gate))}")
-        return
-    _launch("dwgemm", flops, nbytes, "irm_dwgemm_f32", _hip.ptr(wp), int(w_bs), _hip.ptr(dwp), _hip.ptr(x), _bs(x),
+    # split: wp from _hip.pack_gemm_weight_split, the 1x1 part as an fp32 emulation on the fp16 matrix cores
+    kernel, entry = ("dwgemm_f16x3", "irm_dwgemm_f16x3_f32") if split else ("dwgemm", "irm_dwgemm_f32")
+    _launch(kernel, flops, nbytes, entry, _hip.ptr(wp), int(w_bs), _hip.ptr(dwp), _hip.ptr(x), _bs(x),
             _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), int(bool(gate)), B, M, K, H, W,
             _hip.ptr(stats_out), float(eps), tag=f"M{M} K{K} {H}x{W} B{B} gate{int(bool(gate))}")
 
@@ -518,17 +508,13 @@ def conv3x3(wp, x, y, ci: int, co: int, *, bias=None, relu1=False, res=None, res
             return
         wp = (wp.split, wp.inv_scale) if (wp.split is not None and aligned) else wp.exact
     if isinstance(wp, tuple):
-        wps, inv_scale = wp
-        ct, ygroups = plan_conv3x3(co, H, W, B, split=True, ct=ct, ygroups=ygroups)
-        _launch("conv3x3_f16x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_f16x3_ep_f32", _hip.ptr(wps),
-                float(inv_scale), _hip.ptr(x), _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci,
-                co, H, W, act1, slope, int(res_mode), int(relu2), int(store_mode), int(shuffle), ct, ygroups,
-                tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}{extra}")
-        return
-    ct, ygroups = plan_conv3x3(co, H, W, B, split=False, ct=ct, ygroups=ygroups)
-    _launch("conv3x3", 18.0 * B * ci * co * H * W, nbytes, "irm_conv3x3_ep_f32", _hip.ptr(wp), _hip.ptr(x), _bs(x),
-            _hip.ptr(y), _bs(y), _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, act1, slope, int(res_mode),
-            int(relu2), int(store_mode), int(shuffle), ct, ygroups,
+        kernel, entry, lead = "conv3x3_f16x3", "irm_conv3x3_f16x3_ep_f32", (_hip.ptr(wp[0]), float(wp[1]))
+    else:
+        kernel, entry, lead = "conv3x3", "irm_conv3x3_ep_f32", (_hip.ptr(wp),)
+    ct, ygroups = plan_conv3x3(co, H, W, B, split=isinstance(wp, tuple), ct=ct, ygroups=ygroups)
+    _launch(kernel, 18.0 * B * ci * co * H * W, nbytes, entry, *lead, _hip.ptr(x), _bs(x), _hip.ptr(y), _bs(y),
+            _hip.ptr(res), _bs(res), _hip.ptr(bias), B, ci, co, H, W, act1, slope, int(res_mode), int(relu2),
+            int(store_mode), int(shuffle), ct, ygroups,
             tag=f"ci{ci} co{co} {H}x{W} B{B} ct{ct} yg{ygroups} st{store_mode}{extra}")
 
 

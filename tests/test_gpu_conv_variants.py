@@ -30,13 +30,13 @@ from irm_amd import _hip, ops, synth
 from test_gpu_precision import F, K
 
 SENTINEL = 7.0
-EXACT_CTS = (1, 2, 3, 4, 6)             # the ct switches of irm_conv3x3_ep_f32 (conv3x3.hip:469-484)
-SPLIT_CTS = (1, 2, 3, 4, 8, 12)         # output tiles per pass of irm_conv3x3_f16x3_ep_f32 (conv3x3_f16.hip:278-285)
+EXACT_CTS = (1, 2, 3, 4, 6)             # the two ct switches of irm_conv3x3_ep_f32 (conv3x3.hip)
+SPLIT_CTS = (1, 2, 3, 4, 8, 12)         # output tiles per pass: the ct switch of irm_conv3x3_f16x3_ep_f32
 
 
 # --------------------------------------------------------------------------- the variant table and its dispatch mirror
 def ring(ct):
-    return f"conv3x3_ring_kernel<{ct}, 3>"              # launch_conv_ring: NS = 3 (conv3x3.hip:426)
+    return f"conv3x3_ring_kernel<{ct}, 3>"              # launch_conv_ring (conv3x3.hip): NS = 3
 
 
 def generic(ct):
@@ -44,7 +44,7 @@ def generic(ct):
 
 
 def split(ct):
-    """ct 1 ... 4: one weight chunk of ct tiles; 8 / 12: 2 / 3 chunks of 4 (conv3x3_f16.hip:278-285)."""
+    """ct 1 ... 4: one weight chunk of ct tiles; 8 / 12: 2 / 3 chunks of 4 (the ct switch of irm_conv3x3_f16x3_ep_f32)."""
     return f"conv3x3_f16x3_kernel<{min(ct, 4)}, {max(1, ct // 4)}>"
 
 
@@ -67,17 +67,17 @@ def expected_conv_variant(kind, ci, co, W, ct, x_bs, y_bs, r_bs, x_al, y_al, r_a
     batch strides in floats (0 without a residual), *_al: the pointer is 16-byte aligned (a null residual is).  vec is
     ConvArgs.vec, the 16-byte store path of the generic kernel; the split and the thin kernels always store 16 bytes."""
     all_vec = W % 4 == 0 and x_bs % 4 == 0 and y_bs % 4 == 0 and r_bs % 4 == 0 and x_al and y_al and r_al
-    if kind == "exact":                                             # conv3x3.hip:462-485
+    if kind == "exact":                                             # irm_conv3x3_ep_f32 (conv3x3.hip)
         if ct not in EXACT_CTS:
             return None
-        vec = W % 4 == 0 and y_bs % 4 == 0 and r_bs % 4 == 0 and y_al and r_al      # conv3x3.hip:462
-        fast = vec and x_bs % 4 == 0 and x_al and wp_al                             # conv3x3.hip:467
+        vec = W % 4 == 0 and y_bs % 4 == 0 and r_bs % 4 == 0 and y_al and r_al      # a.vec
+        fast = vec and x_bs % 4 == 0 and x_al and wp_al                             # fast
         return (ring(ct) if fast else generic(ct)), vec
-    if kind == "split":                                             # conv3x3_f16.hip:268-269, 278-285
+    if kind == "split":                                             # irm_conv3x3_f16x3_ep_f32: alignment, ct switch
         if not (all_vec and wp_al) or ct not in SPLIT_CTS:
             return None
         return split(ct), True
-    if kind == "thin":                                              # conv3x3_thin.hip:195-197, 199-222
+    if kind == "thin":                                              # irm_conv3x3_thin_f32: checks, Co / Ci dispatch
         if not all_vec or (co > 4 and ci > 4):
             return None
         return (thin_out(co) if co <= 4 and ci > 4 else thin_in(ci)), True
@@ -85,8 +85,8 @@ def expected_conv_variant(kind, ci, co, W, ct, x_bs, y_bs, r_bs, x_al, y_al, r_a
 
 
 def passes_per_group(mtiles, ct, ygroups):
-    """Output-channel passes each workgroup group runs: ygroups is clamped to [1, nchunks] (conv3x3.hip:464-466,
-    conv3x3_f16.hip:275-277) and group y takes passes y, y + ygroups, ... (my_chunks, conv3x3.hip:295)."""
+    """Output-channel passes each workgroup group runs: ygroups is clamped to [1, nchunks] (irm_conv_common,
+    conv_epilogue.h) and group y takes passes y, y + ygroups, ... (my_chunks in conv3x3_ring_kernel)."""
     nchunks = -(-mtiles // ct)
     yg = min(max(ygroups, 1), nchunks)
     return [(nchunks - y + yg - 1) // yg for y in range(yg)]
