@@ -86,6 +86,11 @@ SIGNATURES_FRAMES = {
     "irm_window_blend_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 
+#: the Gram pass with the q, k depth-wise conv inside (dw_gram.hip), mirrors include/irm_hip_gram.h one to one
+SIGNATURES_GRAM = {
+    "irm_dw_gram_cm_f16x3_f32": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -104,7 +109,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(make -C image-restoration-models_amd/csrc).  There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES}.items():
+        for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

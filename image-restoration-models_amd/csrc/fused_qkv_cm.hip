@@ -21,14 +21,7 @@
 // {4-11} at g + 1 - then touch 16 different bank quads.
 // Whole tiles only (H % 8 == 0, W % 32 == 0), C % 16 == 0, M = 3 C; q, k tile-major, v channel-last or planar.
 #include "irm_common.h"
-
-#define QC_TH 8
-#define QC_TW 32
-#define QC_PITCH 36                              // pixel slots per halo row (34 used)
-#define QC_SLOTS ((QC_TH + 2) * QC_PITCH)        // 360
-#define QC_PT 23                                 // 16-slot MFMA tiles (368 slots)
-#define QC_CS 1728                               // bytes between channel rows
-#define QC_IMG (32 * QC_CS)                      // bytes per image
+#include "gram_cm.h"                             // the image's geometry (QC_*, qc_row) and the Gram part
 
 struct QcArgs {
     const float* X; long x_bs;
@@ -43,17 +36,6 @@ struct QcArgs {
     const float* gscale;                         // [2C] power-of-two operand scales of q, k (_hip.gram_scales)
     float* part;
 };
-#define QC_NCH 4
-
-// byte offset of channel row c (0 .. 31) inside an image
-__device__ __forceinline__ unsigned qc_row(int c) {
-    const int i = c & 15;
-    const int rk = i < 4 ? i : i < 12 ? i - 4 : i - 8;                 // rank inside {0-3, 12-15} or inside {4-11}
-    const int o = (rk >> 1) * 4 + (rk & 1);                            // 0, 1, 4, 5, 8, 9, 12, 13
-    // the row's bank-quad phase is (c CS / 16 + o) mod 16; CS / 16 = 108 = 12 (mod 16): take that out so that the phase is o
-    const int fix = (16 - ((c * (QC_CS / 16)) & 15)) & 15;
-    return (unsigned)(c * QC_CS + 16 * ((o + fix) & 15));
-}
 
 // GRAM (KS == 2, C = 48, one head of 48 channels): the stencil outputs of q and k ARE fragments of the Gram MFMA (channel on the
 // lane, the wave's 32 pixels of row w as the k index), so the wave keeps its three q tiles as fp16 hi/lo operands (24 registers),
@@ -93,14 +75,8 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
     if (item >= a.items) return;
     float xr[3][KS][8];                             // raw input of the item (free again after the LayerNorm phase: the
                                                     // next item's input is requested into it three iterations before the end)
-    f32x4 gacc[GRAM ? 3 : 1][GRAM ? 3 : 1];         // GRAM: [q tile][k tile], over the tiles of the chunk
-    float gnq[3] = {0.f, 0.f, 0.f}, gnk[3] = {0.f, 0.f, 0.f};
-    if constexpr (GRAM) {
-#pragma unroll
-        for (int x = 0; x < 3; ++x)
-#pragma unroll
-            for (int y = 0; y < 3; ++y) gacc[x][y] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
+    QcGram gram;                                    // GRAM: accumulators over the tiles of the chunk, the wave's q operands (gram_cm.h)
+    if constexpr (GRAM) qc_gram_clear(gram);
     for (;;) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
@@ -290,7 +266,7 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
 #pragma unroll
             for (int t = 0; t < 10; ++t) stap[t] = irm_ld<float>(lds, vt, slot * SLOT_B + CF_OFF + t * 128);
         };
-        irm_h8 gqh[GRAM ? 3 : 1], gql[GRAM ? 3 : 1];      // GRAM: the wave's q tiles as MFMA operands (this tile's 32 pixels of row w)
+        irm_h8 gqh[3], gql[3];      // GRAM: the wave's q tiles as MFMA operands (this tile's 32 pixels of row w)
         auto st_comp = [&](int st, int hct, auto UC) {
             {
                 constexpr int U = decltype(UC)::value;             // GRAM: 16-channel tile index 2 st + hct at compile time
@@ -310,25 +286,8 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
                     }
                 }
                 if constexpr (GRAM && U >= 0 && U < 6) {
-                    // q (U < 3) or k tile: scaled by the channel's power of two (exact), squared norm in fp32, fp16 hi/lo split;
-                    // a k tile goes straight into the 3 x 3 MFMAs against the resident q tiles (the product order of
-                    // mdta_gram_f16x3_kernel: q_lo k_hi, q_hi k_lo, q_hi k_hi)
-                    const float sc = a.gscale[16 * U + r];         // (C = 48: the k scales start at index 48 = 16 * 3)
-                    float nn = 0.f, xs[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { nn = fmaf(o[e], o[e], nn); xs[e] = o[e] * sc; }
-                    irm_h8 hi, lo;
-                    irm_split8(xs, hi, lo);
-                    if constexpr (U < 3) {
-                        gnq[U] += nn; gqh[U] = hi; gql[U] = lo;
-                    } else {
-                        gnk[U - 3] += nn;
-#pragma unroll
-                        for (int x = 0; x < 3; ++x) {
-                            f32x4& t = gacc[x][U - 3];
-                            t = irm_mfma3_f16(gqh[x], gql[x], hi, lo, t);
-                        }
-                    }
+                    // q (U < 3) or k tile: into the Gram state, never stored (C = 48: the k scales start at index 48 = 16 * 3)
+                    qc_gram_unit<U>(gram, gqh, gql, o, a.gscale[16 * U + r]);
                     return;
                 }
                 if (ch >= a.M) return;
@@ -410,42 +369,8 @@ __global__ __launch_bounds__(512, 2) void qkv_cm_kernel(QcArgs a) {
         if constexpr (GRAM) {
             if (round % QC_NCH == QC_NCH - 1) {
                 // ---- end of the chunk: the 8 waves' partial records meet in LDS (the image area is free) in wave order
-                constexpr int REC = 48 * 48 + 96;
-#pragma unroll
-                for (int t = 0; t < 3; ++t) {
-                    gnq[t] += __shfl_xor(gnq[t], 16); gnq[t] += __shfl_xor(gnq[t], 32);
-                    gnk[t] += __shfl_xor(gnk[t], 16); gnk[t] += __shfl_xor(gnk[t], 32);
-                }
-                float* mine = reinterpret_cast<float*>(smem) + PL_OFF / 4 + wave * REC;
-                float isk[3];
-#pragma unroll
-                for (int y = 0; y < 3; ++y) isk[y] = 1.0f / a.gscale[48 + 16 * y + r];
-#pragma unroll
-                for (int x = 0; x < 3; ++x) {
-                    const f32x4 sq4 = *reinterpret_cast<const f32x4*>(a.gscale + 16 * x + 4 * g);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float isq = 1.0f / sq4[e];           // (powers of two: exact)
-#pragma unroll
-                        for (int y = 0; y < 3; ++y) mine[(16 * x + 4 * g + e) * 48 + 16 * y + r] = gacc[x][y][e] * (isq * isk[y]);
-                    }
-                    if (g == 0) { mine[48 * 48 + 16 * x + r] = gnq[x]; mine[48 * 48 + 48 + 16 * x + r] = gnk[x]; }
-                }
-                __syncthreads();
-                const float* all = reinterpret_cast<const float*>(smem) + PL_OFF / 4;
-                float* out = a.part + ((long)b * (a.tiles / QC_NCH) + tile / QC_NCH) * REC;
-                for (int e = threadIdx.x; e < REC; e += 512) {
-                    float sum = all[e];
-#pragma unroll
-                    for (int w = 1; w < 8; ++w) sum += all[w * REC + e];
-                    out[e] = sum;
-                }
-#pragma unroll
-                for (int x = 0; x < 3; ++x) {
-                    gnq[x] = 0.f; gnk[x] = 0.f;
-#pragma unroll
-                    for (int y = 0; y < 3; ++y) gacc[x][y] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
+                qc_gram_flush(gram, reinterpret_cast<float*>(smem) + PL_OFF / 4, a.gscale, a.gscale + 48,
+                              a.part, (long)b * (a.tiles / QC_NCH) + tile / QC_NCH, wave, g, r);
             }
         }
         if (nitem >= a.items) break;

@@ -411,6 +411,32 @@ def qkv_gram_cm(pk, x, y, gram_scale, part, C: int, *, ln_mode, eps: float = 1e-
     return nchunk
 
 
+def can_dw_gram(C: int, heads: int, H: int, W: int) -> bool:
+    """dw_gram: the depth-wise conv of q, k inside the Gram pass (dw(q), dw(k) never written) at the levels whose qkv is a
+    GEMM of its own: C = 192 / 384 with 48 channels per head, whole 8 x 32 tiles in chunks of QKV_GRAM_NCH.  Both levels are
+    faster in the model (per block at 24 tiles, depth-wise + Gram launches: C = 192 at 128^2 468 -> 334 us, C = 384 at 64^2
+    251 -> 169 us)."""
+    return (C in (192, 384) and C == 48 * heads and H % 8 == 0 and W % 32 == 0
+            and ((H // 8) * (W // 32)) % QKV_GRAM_NCH == 0 and 3 * C * H * W < 1 << 30)
+
+
+def dw_gram(qkv, w9, gram_scale, part, C: int, heads: int, *, bias=None) -> int:
+    """The Gram partial records of dw3x3(q), dw3x3(k) into `part`, from the raw planar qkv (irm_dw_gram_cm_f16x3_f32); w9
+    [2C][9] and bias [2C]: the q, k rows of the depth-wise conv.  Returns nchunk, the records per (image, head), for
+    mdta_fold(..., nchunk_ready=nchunk)."""
+    _chk(qkv, "qkv")
+    B, _, H, W = qkv.shape
+    N = H * W
+    assert can_dw_gram(C, heads, H, W) and qkv.shape[1] >= 2 * C and gram_scale.numel() == 2 * C and gram_scale.is_contiguous()
+    assert w9.shape == (2 * C, 9) and w9.is_contiguous() and (bias is None or (bias.numel() == 2 * C and bias.is_contiguous()))
+    nchunk = (H // 8) * (W // 32) // QKV_GRAM_NCH
+    assert part.numel() >= B * heads * nchunk * (48 * 48 + 96)
+    _launch("dw_gram", B * N * (18.0 * 2 * C + 2.0 * 48 * C), 4.0 * B * N * 2 * C, "irm_dw_gram_cm_f16x3_f32", _hip.ptr(qkv),
+            _bs(qkv), _hip.ptr(w9), _hip.ptr(bias), _hip.ptr(gram_scale), _hip.ptr(part), B, C, heads, H, W,
+            tag=f"C{C} h{heads} {H}x{W} B{B}")
+    return nchunk
+
+
 def mdta_fold(qkv, part, gsum, temperature, wout, mfold, C: int, heads: int, attn=None, split: bool = False,
               gram_scale=None, frag: bool = False, tm: bool = False, nchunk_ready: int | None = None):
     """Gram pass + finalize: mfold[b] <- packed(W_out @ blockdiag(softmax(...))) (restormer.py:115-131);
@@ -422,7 +448,7 @@ def mdta_fold(qkv, part, gsum, temperature, wout, mfold, C: int, heads: int, att
     N = H * W
     chunk, nchunk, rec = mdta_plan(B, C, heads, N)
     if nchunk_ready is not None:
-        nchunk = nchunk_ready                      # the partial records are there already (qkv_gram_cm)
+        nchunk = nchunk_ready                      # the partial records are there already (qkv_gram_cm, dw_gram)
     assert part.numel() >= B * heads * nchunk * rec and gsum.numel() >= B * heads * rec
     c = C // heads
     assert not tm or (c in (48, 96) and N % 256 == 0), "tile-major q, k: the LDS-DMA ring passes only"

@@ -214,6 +214,10 @@ class Restormer(nn.Module):
                                           m.norm1.b, m.norm1.mode == ops.LN_WITHBIAS)
                     if gs is not None:
                         pk[name]["gram_s"] = gs.to(a.qkv.weight.device)
+                        if m.dim in (192, 384):
+                            # the q, k rows of the depth-wise conv for the Gram pass that runs it itself (dw_gram.hip)
+                            c2, dwb = 2 * m.dim, a.qkv_dwconv.bias
+                            pk[name]["qk_dw"] = (f32(a.qkv_dwconv.weight.reshape(-1, 9)[:c2]), None if dwb is None else f32(dwb[:c2]))
                 if self._split and ops.can_fuse_gdfn(m.dim, 4):
                     # whole-branch kernels (fused_block.hip): LN + qkv + dwconv, and the complete GDFN
                     pk[name].update(
@@ -311,20 +315,29 @@ class Restormer(nn.Module):
             ops.gemm1x1(w["qkv_s" if s_qkv else "qkv"], x, qkv, 3 * C, C, bias=w["qkv_b"], stats=stats, lnw=w["n1w"],
                         lnb=w["n1b"], ln_mode=blk.norm1.mode, split=s_qkv)
         fuse_dw = "v_dwp" in w and ops.can_fuse_dw(C, W)
-        if fuse_dw:
+        # C = 192 / 384: the Gram pass reads raw q, k and runs their depth-wise conv itself - dw(q), dw(k) are never written
+        gram_dw = split and "gram_s" in w and "qk_dw" in w and ops.can_dw_gram(C, heads, H, W)
+        _, nchunk, rec = ops.mdta_plan(B, C, heads, N)
+        if gram_dw:
+            nchunk = (H // 8) * (W // 32) // ops.QKV_GRAM_NCH
+        part = self._buf("gram_part", B * heads * nchunk * rec, dev)
+        nready = None
+        if gram_dw:
+            nready = ops.dw_gram(qkv, w["qk_dw"][0], w["gram_s"], part, C, heads, bias=w["qk_dw"][1])
+            ops.dwconv3x3(qkv[:, 2 * C:], w["qkv_dw"][2 * C:], qkv2[:, 2 * C:],
+                          bias=None if w["qkv_dw_b"] is None else w["qkv_dw_b"][2 * C:])
+        elif fuse_dw:
             # q, k only: the depth-wise conv of v happens inside the apply GEMM below
             ops.dwconv3x3(qkv[:, :2 * C], w["qkv_dw"], qkv2[:, :2 * C],
                           bias=None if w["qkv_dw_b"] is None else w["qkv_dw_b"][:2 * C])
         else:
             ops.dwconv3x3(qkv, w["qkv_dw"], qkv2, bias=w["qkv_dw_b"])
-        _, nchunk, rec = ops.mdta_plan(B, C, heads, N)
-        part = self._buf("gram_part", B * heads * nchunk * rec, dev)
         gsum = self._buf("gram_sum", B * heads * rec, dev)
         mfold_n = ops.mfold_numel(C)
         mfold = self._zeros(("mfold", C, B), B * mfold_n, dev)
         # the folded per-image matrix in the order of the kernel that applies it (fp16 hi/lo when emulated)
         ops.mdta_fold(qkv2, part, gsum, w["temp"], w["wout"], mfold, C, heads, split=s_fold,
-                      gram_scale=w.get("gram_s") if split else None)
+                      gram_scale=w.get("gram_s") if split else None, nchunk_ready=nready)
         if fuse_dw:
             ops.dwgemm(mfold, w["v_dwp"], qkv[:, 2 * C:], x, C, C, gate=False, res=x, bias=w["wout_b"],
                        w_bs=mfold_n, stats_out=stats if fuse else None, split=s_fold)

@@ -532,6 +532,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- float32 frames in the tiled-patch loop: irm_frame_minmax_f32, irm_tile_extract_f32, irm_window_blend_f32 */
 #include "irm_hip_frames.h"
 
+/* ---- the q, k depth-wise conv inside the Gram pass at C = 192 / 384: irm_dw_gram_cm_f16x3_f32 */
+#include "irm_hip_gram.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ git -C "$ROOT" archive "$REV" "$CSRC" | tar -x -C "$WORK/old/src"
 compile() {  # <source dir> <output dir>: one .s per .hip that has none yet
     (cd "$1" && ls *.hip | xargs -P "${JOBS:-8}" -I{} sh -c '
         [ -s "$1/{}.s" ] && exit 0
-        case {} in fused_block.hip|fused_tail.hip|fused_qkv_cm.hip) X=-fno-slp-vectorize;; *) X=;; esac
+        case {} in fused_block.hip|fused_tail.hip|fused_qkv_cm.hip|dw_gram.hip) X=-fno-slp-vectorize;; *) X=;; esac
         "$0" -O3 -std=c++17 -fPIC --offload-arch=gfx950 --cuda-device-only -Wno-unused-command-line-argument -S $X {} -o "$1/{}.s.tmp" && mv "$1/{}.s.tmp" "$1/{}.s"' \
         "$HIPCC" "$2")
 }
