@@ -19,8 +19,8 @@ import torch
 import torch.nn as nn
 
 from ... import _hip, ops
-from ...convnet_common import PackedCache, require_cuda
-from .fpn_mobilenet import FPNHead
+from ...host import ModelHost, f32
+from .fpn_mobilenet import FPNHead, FPNMobileNet
 
 ENC_CHANNELS = (32, 64, 192, 1088, 2080)          # conv2d_1a, maxpool_3a, maxpool_5a, mixed_6a, mixed_7a outputs
 
@@ -40,7 +40,9 @@ class _FPNTop(nn.Module):
         self.lateral0 = nn.Conv2d(ENC_CHANNELS[0], num_filters // 2, 1, bias=False)
 
 
-class FPNInceptionDecoder(nn.Module):
+class FPNInceptionDecoder(ModelHost):
+    SYNTH_RULES, SYNTH_SKIP = FPNMobileNet.SYNTH_RULES, FPNMobileNet.SYNTH_SKIP
+
     def __init__(self, norm_layer=None, output_ch=3, num_filters=128, num_filters_fpn=256):
         super().__init__()
         if norm_layer is None:
@@ -54,18 +56,8 @@ class FPNInceptionDecoder(nn.Module):
         self.smooth2 = nn.Sequential(nn.Conv2d(num_filters, num_filters // 2, 3, padding=1), norm_layer(num_filters // 2),
                                      nn.ReLU())
         self.final = nn.Conv2d(num_filters // 2, output_ch, 3, padding=1)
-        self._cache = PackedCache(self, self._build)
-
-    def load_synthetic(self, seed=42):
-        from ... import synth
-        from .. import SYNTH_RULES
-        shapes = {k: tuple(v.shape) for k, v in self.state_dict().items()
-                  if not k.endswith(("running_mean", "running_var", "num_batches_tracked"))}
-        self.load_state_dict(synth.synth_state_dict(shapes, seed=seed, rules=SYNTH_RULES), strict=False)
-        return self
 
     def _build(self):
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()      # noqa: E731
         c3 = lambda conv: (_hip.pack_conv3x3(conv.weight), f32(conv.bias))    # noqa: E731
         pk = {f"lateral{i}": _hip.pack_gemm_weight(getattr(self.fpn, f"lateral{i}").weight) for i in range(5)}
         for n in ("td1", "td2", "td3"):
@@ -78,11 +70,11 @@ class FPNInceptionDecoder(nn.Module):
 
     @torch.no_grad()
     def forward(self, x, enc0, enc1, enc2, enc3, enc4):
-        require_cuda(x, "FPNInceptionDecoder")
+        self._require_cuda(x)
         x = x.float().contiguous()
         B, _, H, W = x.shape
         dev = x.device
-        pk = self._cache.get()
+        pk = self._pack()
         Fp, nf = self.nfpn, self.nf
         new = lambda c, h, w: torch.empty(B, c, h, w, dtype=torch.float32, device=dev)     # noqa: E731
         rpad = lambda t, p: torch.nn.functional.pad(t, p, "reflect").contiguous()          # noqa: E731

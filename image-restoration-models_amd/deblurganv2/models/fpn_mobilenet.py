@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from ... import _hip, ops
-from ...convnet_common import PackedCache, require_cuda
+from ...host import ModelHost, f32
 from .. import SYNTH_RULES
 
 _SETTING = [(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]
@@ -79,7 +79,10 @@ class FPN(nn.Module):
         self.lateral0 = nn.Conv2d(16, num_filters // 2, 1, bias=False)
 
 
-class FPNMobileNet(nn.Module):
+class FPNMobileNet(ModelHost):
+    SYNTH_RULES = SYNTH_RULES
+    SYNTH_SKIP = r"(running_mean|running_var|num_batches_tracked)$|^fpn\.enc"      # norm buffers; aliases of fpn.features
+
     def __init__(self, norm_layer=None, output_ch=3, num_filters=64, num_filters_fpn=128, pretrained=False):
         super().__init__()
         if norm_layer is None:
@@ -93,20 +96,11 @@ class FPNMobileNet(nn.Module):
         self.smooth2 = nn.Sequential(nn.Conv2d(num_filters, num_filters // 2, 3, padding=1), norm_layer(num_filters // 2),
                                      nn.ReLU())
         self.final = nn.Conv2d(num_filters // 2, output_ch, 3, padding=1)
-        self._cache = PackedCache(self, self._build)
         self.max_tiles_per_batch = 2
         self.hip_graph = True      # the tiler replays the per-batch forward from a HIP graph (utils.graphed_forward)
 
     # ------------------------------------------------------------------ weights
-    def load_synthetic(self, seed=42):
-        from ... import synth
-        shapes = {k: tuple(v.shape) for k, v in self.state_dict().items()
-                  if not (k.endswith(("running_mean", "running_var", "num_batches_tracked")) or k.startswith("fpn.enc"))}
-        self.load_state_dict(synth.synth_state_dict(shapes, seed=seed, rules=SYNTH_RULES), strict=False)
-        return self
-
     def _build(self):
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()      # noqa: E731
         g1 = lambda conv: _hip.pack_gemm_weight(conv.weight)                         # noqa: E731
         c3 = lambda conv: (_hip.pack_conv3x3(conv.weight), f32(conv.bias))    # noqa: E731
         pk = {"stem_w": f32(self.fpn.features[0][0].weight), "stem_bn": (f32(self.fpn.features[0][1].weight),
@@ -136,13 +130,13 @@ class FPNMobileNet(nn.Module):
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, x):
-        require_cuda(x, "FPNMobileNet")
+        self._require_cuda(x)
         x = x.float().contiguous()
         B, _, H, W = x.shape
         if H % 32 or W % 32:
             raise ValueError("FPNMobileNet needs H and W to be multiples of 32 (deblurganv2.pad)")
         dev = x.device
-        pk = self._cache.get()
+        pk = self._pack()
         new = lambda c, h, w: torch.empty(B, c, h, w, dtype=torch.float32, device=dev)     # noqa: E731
 
         def norm(t, wb, act, res=None):

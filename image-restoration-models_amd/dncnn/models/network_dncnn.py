@@ -13,10 +13,14 @@ import torch
 import torch.nn as nn
 
 from ... import _hip, ops
-from ...convnet_common import PackedCache, check_precision, conv3x3, half_workspace, require_cuda, thin_weight
+from .. import SYNTH_RULES
+from ...convnet_common import check_precision, half_workspace
+from ...host import ModelHost, f32
 
 
-class DnCNN(nn.Module):
+class DnCNN(ModelHost):
+    SYNTH_RULES = SYNTH_RULES
+
     def __init__(self, in_nc=1, out_nc=1, nc=64, nb=17, act_mode='BR', precision="fp32"):
         super().__init__()
         self.precision = check_precision(precision, "DnCNN", nc)
@@ -31,7 +35,6 @@ class DnCNN(nn.Module):
             if i + 1 < nb:
                 layers.append(nn.ReLU(inplace=True))
         self.model = nn.Sequential(*layers)      # parameter holder: never called
-        self._cache = PackedCache(self, self._build_half if precision == "fp16" else self._build)
         self.hip_graph = True      # the tiler replays the per-batch forward from a HIP graph (utils.graphed_forward)
         self._ws = {}
 
@@ -39,32 +42,24 @@ class DnCNN(nn.Module):
         return [m for m in self.model if isinstance(m, nn.Conv2d)]
 
     def _build(self):
-        return [(_hip.pack_conv3x3(m.weight), m.bias.detach().float().contiguous(),
-                 m.in_channels, m.out_channels) for m in self._convs()]
+        if self.precision == "fp16":
+            return self._build_half()
+        return [(_hip.pack_conv3x3(m.weight), f32(m.bias), m.in_channels, m.out_channels) for m in self._convs()]
 
     def _build_half(self):
         convs = self._convs()
-        bias = [m.bias.detach().float().contiguous() for m in convs]
-        return ([(thin_weight(convs[0].weight), bias[0])]
+        bias = [f32(m.bias) for m in convs]
+        # (first / last layer of the fp16 mode: the plain fp32 weight, ops.conv3x3_h_in / conv3x3_h_out)
+        return ([(f32(convs[0].weight), bias[0])]
                 + [(_hip.pack_conv3x3_h(m.weight), b) for m, b in zip(convs[1:-1], bias[1:-1])]
-                + [(thin_weight(convs[-1].weight), bias[-1])])
-
-    def load_synthetic(self, seed=42):
-        from ... import synth
-        from .. import SYNTH_RULES
-        shapes = {k: tuple(v.shape) for k, v in self.state_dict().items()}
-        self.load_state_dict(synth.synth_state_dict(shapes, seed=seed, rules=SYNTH_RULES), strict=True)
-        return self
-
-    def release_workspace(self):
-        self._ws = {}
+                + [(f32(convs[-1].weight), bias[-1])])
 
     @torch.no_grad()
     def forward(self, x):
-        require_cuda(x, "DnCNN")
+        self._require_cuda(x)
         x = x.float().contiguous()
         B, _, H, W = x.shape
-        layers = self._cache.get()
+        layers = self._pack()
         key = (B, H, W, str(x.device))
         if self.precision == "fp16":
             return self._forward_half(x, layers, key)
@@ -76,10 +71,10 @@ class DnCNN(nn.Module):
         out = torch.empty(B, self.out_nc, H, W, dtype=torch.float32, device=x.device)
         for i, (wp, bias, ci, co) in enumerate(layers):
             if i + 1 < len(layers):
-                conv3x3(wp, cur, nxt, ci, co, bias=bias, relu1=True)
+                ops.conv3x3(wp, cur, nxt, ci, co, bias=bias, relu1=True)
                 cur, nxt = nxt, (self._ws["b"] if nxt is self._ws["a"] else self._ws["a"])
             else:
-                conv3x3(wp, cur, out, ci, co, bias=bias, res=x, res_mode=2)    # x - n
+                ops.conv3x3(wp, cur, out, ci, co, bias=bias, res=x, res_mode=2)    # x - n
         return out
 
     def _forward_half(self, x, layers, key):

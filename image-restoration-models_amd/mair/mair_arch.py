@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip, ops
-from . import SYNTH_RULES
+from ..host import f32
 from .mairunet_arch import MambaHost, VSSBlock, pack_block, scan_ids
 
 RGB_MEAN = (0.4488, 0.4371, 0.4040)
@@ -99,21 +99,10 @@ class MaIR(MambaHost):
             self.ps_factors = []
             self.conv_last = nn.Conv2d(embed_dim, in_chans, 3, 1, 1)
         self.upscale = int(upscale) if upsampler is not None else 1
-        self._init_host()
         self.max_tiles_per_batch = 8
         self.hip_graph = True      # the tiler replays the per-batch forward from a HIP graph (utils.graphed_forward)
 
-    def load_synthetic(self, seed=42):
-        from .. import synth
-        shapes = {k: tuple(v.shape) for k, v in self.state_dict().items()}
-        self.load_state_dict(synth.synth_state_dict(shapes, seed=seed, rules=SYNTH_RULES), strict=True)
-        return self
-
-    def _pack(self):
-        key = self._param_key()
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()       # noqa: E731
+    def _build(self):
         c3 = lambda conv: (_hip.pack_conv3x3(conv.weight), f32(conv.bias))     # noqa: E731
         dev = self.conv_first.weight.device
         E = self.embed_dim
@@ -136,7 +125,6 @@ class MaIR(MambaHost):
         # chan_norm_act computes (x - m) * s: shift in = (x - mean) * r ; shift out = (y + mean * r) / r
         pk["shift_in"] = torch.stack([mean, torch.full_like(mean, r)], dim=1).contiguous()
         pk["shift_out"] = torch.stack([-mean * r, torch.full_like(mean, 1.0 / r)], dim=1).contiguous()
-        self._packed, self._packed_key = pk, key
         return pk
 
     def _layer_norm(self, x, y, wb, pk):
@@ -147,8 +135,7 @@ class MaIR(MambaHost):
 
     @torch.no_grad()
     def forward(self, inp: torch.Tensor) -> torch.Tensor:
-        if not inp.is_cuda:
-            raise _hip.HipLibraryError("irm_amd MaIR runs on the GPU only (no CPU fallback); move the model and input to 'cuda'")
+        self._require_cuda(inp)
         x = inp.float().contiguous()
         B, Cin, H, W = x.shape
         dev, E = x.device, self.embed_dim

@@ -25,7 +25,8 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _hip, ops
+from .. import _hip, ops, unet
+from ..host import ModelHost, f32
 from . import SYNTH_RULES
 
 _IDS_CACHE: dict = {}
@@ -125,8 +126,6 @@ class _Resample(nn.Module):
 
 def pack_block(m: VSSBlock) -> dict:
     """Packed / flattened device copies of one block's weights."""
-    def f32(t):
-        return None if t is None else t.detach().float().contiguous()
     a = m.self_attention
     D = a.d_inner
     # the two LayerNorm-prologue GEMMs (in_proj, fc1) also in the hi/lo fp16 order of irm_gemm1x1_f16x3_f32
@@ -155,25 +154,9 @@ def pack_block(m: VSSBlock) -> dict:
         fc2=_hip.pack_gemm_weight(m.ffn.fc2.weight), fc2_b=f32(m.ffn.fc2.bias))
 
 
-class MambaHost(nn.Module):
-    """Workspace + the VSSBlock driver shared by MaIRUNet and the flat MaIR."""
-
-    def _init_host(self):
-        self._packed, self._packed_key, self._ws_by_stream = None, None, {}
-
-    def _param_key(self):
-        return _hip.param_key(self)
-
-    def _buf(self, name, numel, device):
-        ws = self._ws_by_stream.setdefault(torch.cuda.current_stream().cuda_stream, {})
-        t = ws.get(name)
-        if t is None or t.numel() < numel or t.device != device:
-            t = torch.empty(int(numel), dtype=torch.float32, device=device)
-            ws[name] = t
-        return t[:numel]
-
-    def release_workspace(self):
-        self._ws_by_stream.clear()
+class MambaHost(ModelHost):
+    """The VSSBlock driver shared by MaIRUNet and the flat MaIR."""
+    SYNTH_RULES = SYNTH_RULES
 
     # ------------------------------------------------------------------ one VSSBlock, in place on x
     def _block(self, blk: VSSBlock, w: dict, x: torch.Tensor, ids: torch.Tensor, have_stats=False, want_stats=True):
@@ -225,7 +208,6 @@ class MambaHost(nn.Module):
         return emit
 
 
-
 class MaIRUNet(MambaHost):
     def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=(4, 6, 6, 8), ssm_ratio=1.5,
                  num_refinement_blocks=4, drop_path_rate=0., bias=False, dual_pixel_task=False, flp_ratio=2,
@@ -258,91 +240,30 @@ class MaIRUNet(MambaHost):
         if dual_pixel_task:
             self.skip_conv = nn.Conv2d(d1, d2, 1, bias=bias)
         self.output = nn.Conv2d(d2, out_channels, 3, padding=1, bias=bias)
-        self._init_host()
         self.max_tiles_per_batch = 4
         self.hip_graph = True      # the tiler replays the per-batch forward from a HIP graph (utils.graphed_forward)
 
-    # ------------------------------------------------------------------ weights
-    def load_synthetic(self, seed=42):
-        from .. import synth
-        shapes = {k: tuple(v.shape) for k, v in self.state_dict().items()}
-        self.load_state_dict(synth.synth_state_dict(shapes, seed=seed, rules=SYNTH_RULES), strict=True)
-        return self
-
-    def _pack(self):
-        key = self._param_key()
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-
-        def f32(t):
-            return None if t is None else t.detach().float().contiguous()
-
+    def _build(self):
         pk = {name: pack_block(m) for name, m in self.named_modules() if isinstance(m, VSSBlock)}
-        for name in ("down1_2", "down2_3", "down3_4", "up4_3", "up3_2", "up2_1"):
-            pk[name] = _hip.pack_conv3x3(getattr(self, name).body[0].weight)
-        pk["patch_embed"] = _hip.pack_conv3x3(self.patch_embed.proj.weight)
-        pk["output"] = _hip.pack_conv3x3(self.output.weight)
-        pk["output_b"] = f32(self.output.bias)
-        for name in ("reduce_chan_level3", "reduce_chan_level2") + (("skip_conv",) if self.dual_pixel_task else ()):
-            pk[name] = _hip.pack_gemm_weight(getattr(self, name).weight)
-            pk[name + "_b"] = f32(getattr(self, name).bias)
-        self._packed, self._packed_key = pk, key
+        pk.update(unet.pack_unet(self))
         return pk
-
-    def _run_stage(self, name, pk, x, ids):
-        blocks = getattr(self, name)
-        have = False
-        for i, blk in enumerate(blocks):
-            have = self._block(blk, pk[f"{name}.{i}"], x, ids, have, want_stats=i + 1 < len(blocks))
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, inp_img: torch.Tensor) -> torch.Tensor:
-        if not inp_img.is_cuda:
-            raise _hip.HipLibraryError("irm_amd MaIRUNet runs on the GPU only (no CPU fallback); "
-                                       "move the model and input to 'cuda'")
+        self._require_cuda(inp_img)
         x = inp_img.float().contiguous()
-        B, Cin, H, W = x.shape
+        H, W = x.shape[2:]
         if H % 8 or W % 8:
             raise ValueError("MaIRUNet needs H and W to be multiples of 8 (the tiler pads, utils.pad)")
-        dev = x.device
         pk = self._pack()
-        d1, d2, d3, d4 = self.dim, self.dim * 2, self.dim * 4, self.dim * 8
-        sz = [(H, W), (H // 2, W // 2), (H // 4, W // 4), (H // 8, W // 8)]
-        ids = [scan_ids(h, w, self.scan_len, dev) for h, w in sz]
+        ids = [scan_ids(H >> lv, W >> lv, self.scan_len, x.device) for lv in range(4)]
 
-        def buf(name, ch, hw):
-            return self._buf(name, B * ch * hw[0] * hw[1], dev).view(B, ch, hw[0], hw[1])
+        def run_stage(names, t, level):
+            # every stage starts without LayerNorm statistics, decoder_level1 and refinement included
+            for name in names:
+                blocks, have = getattr(self, name), False
+                for i, blk in enumerate(blocks):
+                    have = self._block(blk, pk[f"{name}.{i}"], t, ids[level], have, want_stats=i + 1 < len(blocks))
 
-        cat1, cat2, cat3 = buf("cat1", 2 * d1, sz[0]), buf("cat2", 2 * d2, sz[1]), buf("cat3", 2 * d3, sz[2])
-        lat, dec3, dec2 = buf("latent", d4, sz[3]), buf("dec3", d3, sz[2]), buf("dec2", d2, sz[1])
-        e1 = cat1[:, d1:]
-        ops.conv3x3(pk["patch_embed"], x, e1, Cin, d1)
-        if self.dual_pixel_task:
-            e1_in = buf("enc1_in", d1, sz[0])
-            e1_in.copy_(e1)
-        self._run_stage("encoder_level1", pk, e1, ids[0])
-        e2 = cat2[:, d2:]
-        ops.conv3x3(pk["down1_2"], e1, e2, d1, d1 // 2, store_mode=1)
-        self._run_stage("encoder_level2", pk, e2, ids[1])
-        e3 = cat3[:, d3:]
-        ops.conv3x3(pk["down2_3"], e2, e3, d2, d2 // 2, store_mode=1)
-        self._run_stage("encoder_level3", pk, e3, ids[2])
-        ops.conv3x3(pk["down3_4"], e3, lat, d3, d3 // 2, store_mode=1)
-        self._run_stage("latent", pk, lat, ids[3])
-        ops.conv3x3(pk["up4_3"], lat, cat3[:, :d3], d4, d4 * 2, store_mode=2)
-        ops.gemm1x1(pk["reduce_chan_level3"], cat3, dec3, d3, 2 * d3, bias=pk["reduce_chan_level3_b"])
-        self._run_stage("decoder_level3", pk, dec3, ids[2])
-        ops.conv3x3(pk["up3_2"], dec3, cat2[:, :d2], d3, d3 * 2, store_mode=2)
-        ops.gemm1x1(pk["reduce_chan_level2"], cat2, dec2, d2, 2 * d2, bias=pk["reduce_chan_level2_b"])
-        self._run_stage("decoder_level2", pk, dec2, ids[1])
-        ops.conv3x3(pk["up2_1"], dec2, cat1[:, :d1], d2, d2 * 2, store_mode=2)
-        self._run_stage("decoder_level1", pk, cat1, ids[0])
-        self._run_stage("refinement", pk, cat1, ids[0])
-        out = torch.empty(B, self.out_channels, H, W, dtype=torch.float32, device=dev)
-        if self.dual_pixel_task:
-            ops.gemm1x1(pk["skip_conv"], e1_in, cat1, d2, d1, res=cat1, bias=pk["skip_conv_b"])
-            ops.conv3x3(pk["output"], cat1, out, d2, self.out_channels, bias=pk["output_b"])
-        else:
-            ops.conv3x3(pk["output"], cat1, out, d2, self.out_channels, bias=pk["output_b"], res=x, res_mode=1)
-        return out
+        return unet.forward(self, x, pk, run_stage)

@@ -12,10 +12,14 @@ import torch
 import torch.nn as nn
 
 from .. import _hip, ops
-from ..convnet_common import PackedCache, check_precision, conv3x3, half_workspace, require_cuda, thin_weight
+from . import SYNTH_RULES
+from ..convnet_common import check_precision, half_workspace
+from ..host import ModelHost, f32
 
 
-class REDNet(nn.Module):
+class REDNet(ModelHost):
+    SYNTH_RULES = SYNTH_RULES
+
     def __init__(self, num_channels=1, num_features=128, precision="fp32"):
         super().__init__()
         self.precision = check_precision(precision, "REDNet", num_features)
@@ -25,47 +29,36 @@ class REDNet(nn.Module):
         for i in range(1, 16):
             setattr(self, f"deconv{i}", nn.ConvTranspose2d(num_features, num_channels if i == 15 else num_features,
                                                            3, padding=1))
-        self._cache = PackedCache(self, self._build_half if precision == "fp16" else self._build)
         self.hip_graph = True      # the tiler replays the per-batch forward from a HIP graph (utils.graphed_forward)
         self._ws = {}              # fp16 mode: ping-pong and skip buffers of one (B, H, W, device)
 
     def _build(self):
-        enc = [(_hip.pack_conv3x3(m.weight), m.bias.detach().float().contiguous(), m.in_channels, m.out_channels)
+        if self.precision == "fp16":
+            return self._build_half()
+        enc = [(_hip.pack_conv3x3(m.weight), f32(m.bias), m.in_channels, m.out_channels)
                for m in (getattr(self, f"conv{i}") for i in range(1, 16))]
-        dec = [(_hip.pack_conv3x3(_hip.deconv_as_conv_weight(m.weight)), m.bias.detach().float().contiguous(),
-                m.in_channels, m.out_channels) for m in (getattr(self, f"deconv{i}") for i in range(1, 16))]
+        dec = [(_hip.pack_conv3x3(_hip.deconv_as_conv_weight(m.weight)), f32(m.bias), m.in_channels, m.out_channels)
+               for m in (getattr(self, f"deconv{i}") for i in range(1, 16))]
         return enc, dec
 
     def _build_half(self):
         convs = [getattr(self, f"conv{i}") for i in range(1, 16)]
         deconvs = [getattr(self, f"deconv{i}") for i in range(1, 16)]
-
-        def bias(m):
-            return m.bias.detach().float().contiguous()
-        first = (thin_weight(convs[0].weight), bias(convs[0]))
-        enc = [(_hip.pack_conv3x3_h(m.weight), bias(m)) for m in convs[1:]]
-        dec = [(_hip.pack_conv3x3_h(_hip.deconv_as_conv_weight(m.weight)), bias(m)) for m in deconvs[:-1]]
-        last = (thin_weight(_hip.deconv_as_conv_weight(deconvs[-1].weight)), bias(deconvs[-1]))
+        # (first / last layer of the fp16 mode: the plain fp32 weight, ops.conv3x3_h_in / conv3x3_h_out)
+        first = (f32(convs[0].weight), f32(convs[0].bias))
+        enc = [(_hip.pack_conv3x3_h(m.weight), f32(m.bias)) for m in convs[1:]]
+        dec = [(_hip.pack_conv3x3_h(_hip.deconv_as_conv_weight(m.weight)), f32(m.bias)) for m in deconvs[:-1]]
+        last = (f32(_hip.deconv_as_conv_weight(deconvs[-1].weight)), f32(deconvs[-1].bias))
         return first, enc, dec, last
-
-    def release_workspace(self):
-        self._ws = {}
-
-    def load_synthetic(self, seed=42):
-        from .. import synth
-        from . import SYNTH_RULES
-        shapes = {k: tuple(v.shape) for k, v in self.state_dict().items()}
-        self.load_state_dict(synth.synth_state_dict(shapes, seed=seed, rules=SYNTH_RULES), strict=True)
-        return self
 
     @torch.no_grad()
     def forward(self, x):
-        require_cuda(x, "REDNet")
+        self._require_cuda(x)
         x = x.float().contiguous()
         B, _, H, W = x.shape
         if self.precision == "fp16":
             return self._forward_half(x)
-        enc, dec = self._cache.get()
+        enc, dec = self._pack()
         F = self.num_features
 
         def new(c=F):
@@ -74,7 +67,7 @@ class REDNet(nn.Module):
         feats, cur = [], x
         for (wp, b, ci, co) in enc:                       # c1..c15 (rednet.py:66-80)
             nxt = new()
-            conv3x3(wp, cur, nxt, ci, co, bias=b, relu1=True)
+            ops.conv3x3(wp, cur, nxt, ci, co, bias=b, relu1=True)
             feats.append(nxt)
             cur = nxt
         d = cur
@@ -82,18 +75,18 @@ class REDNet(nn.Module):
             wp, b, ci, co = dec[i - 1]
             nxt = new()
             if i % 2 == 1:                                # relu(relu(deconv) + c_{15-i})
-                conv3x3(wp, d, nxt, ci, co, bias=b, relu1=True, res=feats[14 - i], res_mode=1, relu2=True)
+                ops.conv3x3(wp, d, nxt, ci, co, bias=b, relu1=True, res=feats[14 - i], res_mode=1, relu2=True)
             else:
-                conv3x3(wp, d, nxt, ci, co, bias=b, relu1=True)
+                ops.conv3x3(wp, d, nxt, ci, co, bias=b, relu1=True)
             d = nxt
         wp, b, ci, co = dec[14]
         out = new(self.num_channels)
-        conv3x3(wp, d, out, ci, co, bias=b, res=x, res_mode=1)      # d15 + x (rednet.py:133-136)
+        ops.conv3x3(wp, d, out, ci, co, bias=b, res=x, res_mode=1)      # d15 + x (rednet.py:133-136)
         return out
 
     def _forward_half(self, x):
         B, _, H, W = x.shape
-        first, enc, dec, last = self._cache.get()
+        first, enc, dec, last = self._pack()
         F = self.num_features
         # the features the decoder adds back (c2, c4 ... c14) own a buffer each, everything else ping-pongs
         skips = tuple(f"c{k}" for k in range(2, 15, 2))

@@ -12,10 +12,9 @@ drives the HIP kernels:
     mdta_finalize (softmax + fold with project_out) -> gemm1x1(Mfold, v, +x)
     ln_stats -> gemm1x1(project_in, LN prologue) -> dwconv3x3_gate ->
     gemm1x1(project_out, +x)
-  and conv3x3 (patch embed, down/up-sampling with the pixel (un)shuffle folded
-  into the store, output conv + input residual).  The U-Net concatenations
-  (restormer.py:264-273) are not copies: producers write straight into channel
-  slices of the concat buffers.
+  Everything between the stages (patch embed, down/up-sampling, reduce_chan,
+  output conv) is the U-Net walk shared with MaIRUNet: unet.py.  Weight cache,
+  workspace and synthetic weights come from host.ModelHost.
 
 There is no PyTorch fallback: without the HIP library ``forward`` raises.
 """
@@ -26,7 +25,8 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _hip, ops
+from .. import _hip, ops, unet
+from ..host import ModelHost, f32
 
 #: synthetic-weight rules (see synth.py): keep the restored image in range
 SYNTH_RULES = (
@@ -107,7 +107,77 @@ def _stage(dim, heads, n, f, bias, ln):
     return nn.Sequential(*[TransformerBlock(dim, heads, f, bias, ln) for _ in range(n)])
 
 
-class Restormer(nn.Module):
+def pack_block(m: TransformerBlock, split: bool) -> dict:
+    """Packed / flattened device copies of one block's weights; split: also the operands of the fp16-emulated kernels."""
+    a, ff = m.attn, m.ffn
+    w = dict(
+        qkv=_hip.pack_gemm_weight(a.qkv.weight), qkv_b=f32(a.qkv.bias),
+        qkv_dw=f32(a.qkv_dwconv.weight.reshape(-1, 9)), qkv_dw_b=f32(a.qkv_dwconv.bias),
+        wout=f32(a.project_out.weight.reshape(m.dim, m.dim)), wout_b=f32(a.project_out.bias),
+        temp=f32(a.temperature.reshape(-1)),
+        pin=_hip.pack_gemm_weight(ff.project_in.weight), pin_b=f32(ff.project_in.bias),
+        ffn_dw=f32(ff.dwconv.weight.reshape(-1, 9)), ffn_dw_b=f32(ff.dwconv.bias),
+        pout=_hip.pack_gemm_weight(ff.project_out.weight), pout_b=f32(ff.project_out.bias),
+        n1w=f32(m.norm1.w), n1b=f32(m.norm1.b), n2w=f32(m.norm2.w), n2b=f32(m.norm2.b))
+    if split:
+        # per layer: outside the safe range of the unscaled split (trained checkpoints with large LayerNorm
+        # gains or tiny / huge weights) the layer stays on the exact f32 MFMA (_hip.split_is_safe)
+        if _hip.split_is_safe(a.qkv.weight, m.norm1.w, m.norm1.b):
+            w["qkv_s"] = _hip.pack_gemm_weight_split(a.qkv.weight)
+        if _hip.split_is_safe(ff.project_in.weight, m.norm2.w, m.norm2.b):
+            w["pin_s"] = _hip.pack_gemm_weight_split(ff.project_in.weight)
+        if _hip.split_is_safe(ff.project_out.weight):
+            w["pout_s"] = _hip.pack_gemm_weight_split(ff.project_out.weight)
+        w["mfold_split"] = _hip.split_is_safe(a.project_out.weight)
+        if m.dim == 192:
+            # GDFN tail in one kernel (fused_tail.hip): project_in with its halves padded to a multiple of 16
+            # channels, written tile-major channel-last; taps / project_out packed for irm_gdfn_tail_f16x3_f32
+            hp = 64 * -(-ff.hidden // 64)
+            frag, s_w, bp = _hip.pack_pin_padded(ff.project_in.weight, ff.project_in.bias, hp)
+            s_x = _hip.ln_split_scale(m.norm2.w, m.norm2.b, m.dim, m.norm2.mode == ops.LN_WITHBIAS)
+            w["pin_cl"] = (frag, 1.0 / (s_w * s_x), s_x, bp, hp)
+            w["tail"] = _hip.pack_gdfn_tail(ff.dwconv.weight, ff.dwconv.bias, ff.project_out.weight)
+        if m.dim in (192, 384):
+            # LayerNorm + qkv / project_in with pre-split operands (gemm_ps.hip): (fragments, 1 / (s_w s_x), s_x);
+            # power-of-two scales on both operands - no range guard needed
+            for slot, conv, nrm in (("qkv_ps", a.qkv, m.norm1), ("pin_ps", ff.project_in, m.norm2)):
+                frag, s_w = _hip.pack_gemm_weight_presplit(conv.weight)
+                s_x = _hip.ln_split_scale(nrm.w, nrm.b, m.dim, nrm.mode == ops.LN_WITHBIAS)
+                w[slot] = (frag, 1.0 / (s_w * s_x), s_x)
+        # Gram pass on the fp16 matrix cores where a static bound of |q|, |k| exists (WithBias LayerNorm)
+        gs = _hip.gram_scales(a.qkv.weight, a.qkv.bias, a.qkv_dwconv.weight, a.qkv_dwconv.bias, m.norm1.w,
+                              m.norm1.b, m.norm1.mode == ops.LN_WITHBIAS)
+        if gs is not None:
+            w["gram_s"] = gs.to(a.qkv.weight.device)
+            if m.dim in (192, 384):
+                # the q, k rows of the depth-wise conv for the Gram pass that runs it itself (dw_gram.hip)
+                c2, dwb = 2 * m.dim, a.qkv_dwconv.bias
+                w["qk_dw"] = (f32(a.qkv_dwconv.weight.reshape(-1, 9)[:c2]), None if dwb is None else f32(dwb[:c2]))
+    if split and ops.can_fuse_gdfn(m.dim, 4):
+        # whole-branch kernels (fused_block.hip): LN + qkv + dwconv, and the complete GDFN
+        w.update(
+            qkv_f=_hip.pack_qkv_fused(a.qkv.weight, a.qkv.bias, a.qkv_dwconv.weight, a.qkv_dwconv.bias,
+                                      m.norm1.w, m.norm1.b),
+            gdfn_f=_hip.pack_gdfn_fused(ff.project_in.weight, ff.project_in.bias, ff.dwconv.weight,
+                                        ff.dwconv.bias, ff.project_out.weight, m.norm2.w, m.norm2.b))
+        if w["mfold_split"] and m.dim % 16 == 0:
+            # attention apply inside the GDFN kernel (irm_attn_gdfn_fused_f16x3_f32): project_in's
+            # input channels in the order its first MFMA leaves x' in the registers
+            w["gdfn_fa"] = _hip.pack_gdfn_fused(
+                ff.project_in.weight, ff.project_in.bias, ff.dwconv.weight, ff.dwconv.bias,
+                ff.project_out.weight, m.norm2.w, m.norm2.b, kperm=True)
+    if ops.can_fuse_dw(m.dim, 4):
+        # depth-wise coefficient tables of the fused dw + 1x1 kernel (irm_dwgemm_f32)
+        c, dw, dwb = m.dim, a.qkv_dwconv.weight.reshape(-1, 9), a.qkv_dwconv.bias
+        w.update(
+            v_dwp=_hip.pack_dw_table(dw[2 * c:], None if dwb is None else dwb[2 * c:], c, False),
+            ffn_dwp=_hip.pack_dw_table(ff.dwconv.weight, ff.dwconv.bias, ff.hidden, True))
+    return w
+
+
+class Restormer(ModelHost):
+    SYNTH_RULES = SYNTH_RULES
+
     def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=(4, 6, 6, 8),
                  num_refinement_blocks=4, heads=(1, 2, 4, 8), ffn_expansion_factor=2.66, bias=False,
                  LayerNorm_type="WithBias", dual_pixel_task=False):
@@ -136,148 +206,26 @@ class Restormer(nn.Module):
         if dual_pixel_task:
             self.skip_conv = nn.Conv2d(d1, d2, 1, bias=bias)
         self.output = nn.Conv2d(d2, out_channels, 3, padding=1, bias=bias)
-        self._packed = None
-        self._packed_key = None
         self._split = False
-        self._ws_by_stream = {}
         #: tiles of one image processed per forward by the device tiler (utils.tiled_forward_device)
         self.max_tiles_per_batch = 12     # (two 1280x720 frames: utils.tiled_forward_device_batch)
         self.hip_graph = True      # the tiler replays the per-batch forward from a HIP graph (utils.graphed_forward)
         self._tap = None           # tests: a dict that receives a copy of the `refinement` output (restormer.py:274)
 
     # ------------------------------------------------------------------ weights
-    def load_synthetic(self, seed=42):
-        """Fill every parameter from the deterministic generator (synth.py)."""
-        from .. import synth
-        shapes = {k: tuple(v.shape) for k, v in self.state_dict().items()}
-        self.load_state_dict(synth.synth_state_dict(shapes, seed=seed, rules=SYNTH_RULES), strict=True)
-        return self
-
-    def _param_key(self):
-        return _hip.param_key(self)
-
-    def _pack(self):
-        """Packed / flattened device copies of the weights, rebuilt when parameters change."""
-        key = self._param_key()
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        pk = {}
-
-        def f32(t):
-            return None if t is None else t.detach().float().contiguous()
-
+    def _build(self):
         # the two LayerNorm-prologue GEMMs of a block (qkv, project_in: 2/3 of the GEMM FLOPs) run as an fp32
         # emulation on the fp16 matrix cores (irm_gemm1x1_f16x3_f32; its error against float64 is not larger
         # than the exact-fp32 kernel's, and a LayerNorm output cannot leave the fp16 range): weights split into
         # fp16 hi/lo here.  IRM_GEMM_EXACT=1 keeps every GEMM on the f32-input MFMA.
         self._split = not os.environ.get("IRM_GEMM_EXACT")
-
-        for name, m in self.named_modules():
-            if isinstance(m, TransformerBlock):
-                a, ff = m.attn, m.ffn
-                pk[name] = dict(
-                    qkv=_hip.pack_gemm_weight(a.qkv.weight), qkv_b=f32(a.qkv.bias),
-                    qkv_dw=f32(a.qkv_dwconv.weight.reshape(-1, 9)), qkv_dw_b=f32(a.qkv_dwconv.bias),
-                    wout=f32(a.project_out.weight.reshape(m.dim, m.dim)), wout_b=f32(a.project_out.bias),
-                    temp=f32(a.temperature.reshape(-1)),
-                    pin=_hip.pack_gemm_weight(ff.project_in.weight), pin_b=f32(ff.project_in.bias),
-                    ffn_dw=f32(ff.dwconv.weight.reshape(-1, 9)), ffn_dw_b=f32(ff.dwconv.bias),
-                    pout=_hip.pack_gemm_weight(ff.project_out.weight), pout_b=f32(ff.project_out.bias),
-                    n1w=f32(m.norm1.w), n1b=f32(m.norm1.b), n2w=f32(m.norm2.w), n2b=f32(m.norm2.b))
-                if self._split:
-                    # per layer: outside the safe range of the unscaled split (trained checkpoints with large LayerNorm
-                    # gains or tiny / huge weights) the layer stays on the exact f32 MFMA (_hip.split_is_safe)
-                    if _hip.split_is_safe(a.qkv.weight, m.norm1.w, m.norm1.b):
-                        pk[name]["qkv_s"] = _hip.pack_gemm_weight_split(a.qkv.weight)
-                    if _hip.split_is_safe(ff.project_in.weight, m.norm2.w, m.norm2.b):
-                        pk[name]["pin_s"] = _hip.pack_gemm_weight_split(ff.project_in.weight)
-                    if _hip.split_is_safe(ff.project_out.weight):
-                        pk[name]["pout_s"] = _hip.pack_gemm_weight_split(ff.project_out.weight)
-                    pk[name]["mfold_split"] = _hip.split_is_safe(a.project_out.weight)
-                    if m.dim == 192:
-                        # GDFN tail in one kernel (fused_tail.hip): project_in with its halves padded to a multiple of 16
-                        # channels, written tile-major channel-last; taps / project_out packed for irm_gdfn_tail_f16x3_f32
-                        hp = 64 * -(-ff.hidden // 64)
-                        frag, s_w, bp = _hip.pack_pin_padded(ff.project_in.weight, ff.project_in.bias, hp)
-                        s_x = _hip.ln_split_scale(m.norm2.w, m.norm2.b, m.dim, m.norm2.mode == ops.LN_WITHBIAS)
-                        pk[name]["pin_cl"] = (frag, 1.0 / (s_w * s_x), s_x, bp, hp)
-                        pk[name]["tail"] = _hip.pack_gdfn_tail(ff.dwconv.weight, ff.dwconv.bias, ff.project_out.weight)
-                    if m.dim in (192, 384):
-                        # LayerNorm + qkv / project_in with pre-split operands (gemm_ps.hip): (fragments, 1 / (s_w s_x), s_x);
-                        # power-of-two scales on both operands - no range guard needed
-                        for slot, conv, nrm in (("qkv_ps", a.qkv, m.norm1), ("pin_ps", ff.project_in, m.norm2)):
-                            frag, s_w = _hip.pack_gemm_weight_presplit(conv.weight)
-                            s_x = _hip.ln_split_scale(nrm.w, nrm.b, m.dim, nrm.mode == ops.LN_WITHBIAS)
-                            pk[name][slot] = (frag, 1.0 / (s_w * s_x), s_x)
-                    # Gram pass on the fp16 matrix cores where a static bound of |q|, |k| exists (WithBias LayerNorm)
-                    gs = _hip.gram_scales(a.qkv.weight, a.qkv.bias, a.qkv_dwconv.weight, a.qkv_dwconv.bias, m.norm1.w,
-                                          m.norm1.b, m.norm1.mode == ops.LN_WITHBIAS)
-                    if gs is not None:
-                        pk[name]["gram_s"] = gs.to(a.qkv.weight.device)
-                        if m.dim in (192, 384):
-                            # the q, k rows of the depth-wise conv for the Gram pass that runs it itself (dw_gram.hip)
-                            c2, dwb = 2 * m.dim, a.qkv_dwconv.bias
-                            pk[name]["qk_dw"] = (f32(a.qkv_dwconv.weight.reshape(-1, 9)[:c2]), None if dwb is None else f32(dwb[:c2]))
-                if self._split and ops.can_fuse_gdfn(m.dim, 4):
-                    # whole-branch kernels (fused_block.hip): LN + qkv + dwconv, and the complete GDFN
-                    pk[name].update(
-                        qkv_f=_hip.pack_qkv_fused(a.qkv.weight, a.qkv.bias, a.qkv_dwconv.weight, a.qkv_dwconv.bias,
-                                                  m.norm1.w, m.norm1.b),
-                        gdfn_f=_hip.pack_gdfn_fused(ff.project_in.weight, ff.project_in.bias, ff.dwconv.weight,
-                                                    ff.dwconv.bias, ff.project_out.weight, m.norm2.w, m.norm2.b))
-                    if pk[name]["mfold_split"] and m.dim % 16 == 0:
-                        # attention apply inside the GDFN kernel (irm_attn_gdfn_fused_f16x3_f32): project_in's
-                        # input channels in the order its first MFMA leaves x' in the registers
-                        pk[name]["gdfn_fa"] = _hip.pack_gdfn_fused(
-                            ff.project_in.weight, ff.project_in.bias, ff.dwconv.weight, ff.dwconv.bias,
-                            ff.project_out.weight, m.norm2.w, m.norm2.b, kperm=True)
-                if ops.can_fuse_dw(m.dim, 4):
-                    # depth-wise coefficient tables of the fused dw + 1x1 kernel (irm_dwgemm_f32)
-                    c, dw, dwb = m.dim, a.qkv_dwconv.weight.reshape(-1, 9), a.qkv_dwconv.bias
-                    pk[name].update(
-                        v_dwp=_hip.pack_dw_table(dw[2 * c:], None if dwb is None else dwb[2 * c:], c, False),
-                        ffn_dwp=_hip.pack_dw_table(ff.dwconv.weight, ff.dwconv.bias, ff.hidden, True))
-        for name in ("down1_2", "down2_3", "down3_4", "up4_3", "up3_2", "up2_1"):
-            pk[name] = _hip.pack_conv3x3(getattr(self, name).body[0].weight)
-        pk["patch_embed"] = _hip.pack_conv3x3(self.patch_embed.proj.weight)
-        pk["patch_embed_b"] = f32(self.patch_embed.proj.bias)
-        pk["output"] = _hip.pack_conv3x3(self.output.weight)
-        pk["output_b"] = f32(self.output.bias)
-        for name in ("reduce_chan_level3", "reduce_chan_level2") + (("skip_conv",) if self.dual_pixel_task else ()):
-            pk[name] = _hip.pack_gemm_weight(getattr(self, name).weight)
-            pk[name + "_b"] = f32(getattr(self, name).bias)
+        pk = {name: pack_block(m, self._split) for name, m in self.named_modules() if isinstance(m, TransformerBlock)}
+        pk.update(unet.pack_unet(self))
+        for name in ("reduce_chan_level3", "reduce_chan_level2"):
             # (un-normalised input: the emulated GEMM scales it by 2^-4 and saturates, as for project_out)
-            if self._split and name != "skip_conv" and _hip.split_is_safe(getattr(self, name).weight):
+            if self._split and _hip.split_is_safe(getattr(self, name).weight):
                 pk[name + "_s"] = _hip.pack_gemm_weight_split(getattr(self, name).weight)
-        self._packed, self._packed_key = pk, key
         return pk
-
-    # ------------------------------------------------------------------ workspace
-    @property
-    def _ws(self):
-        """Workspace of the current stream (concurrent forwards on different streams must not share)."""
-        return self._ws_by_stream.setdefault(torch.cuda.current_stream().cuda_stream if torch.cuda.is_available()
-                                             else 0, {})
-
-    def _buf(self, name, numel, device):
-        ws = self._ws
-        t = ws.get(name)
-        if t is None or t.numel() < numel or t.device != device:
-            t = torch.empty(int(numel), dtype=torch.float32, device=device)
-            ws[name] = t
-        return t[:numel]
-
-    def _zeros(self, key, numel, device):
-        """A zero-initialised workspace tensor of the current stream, created once per key and device."""
-        ws = self._ws
-        t = ws.get(key)
-        if t is None or t.device != device:
-            t = torch.zeros(numel, dtype=torch.float32, device=device)
-            ws[key] = t
-        return t
-
-    def release_workspace(self):
-        self._ws_by_stream.clear()
 
     # ------------------------------------------------------------------ kernels
     def _block(self, blk: TransformerBlock, w: dict, x: torch.Tensor, have_stats: bool = False,
@@ -449,67 +397,12 @@ class Restormer(nn.Module):
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, inp_img: torch.Tensor) -> torch.Tensor:
-        if not inp_img.is_cuda:
-            raise _hip.HipLibraryError("irm_amd Restormer runs on the GPU only (no CPU fallback); "
-                                       "move the model and input to 'cuda'")
+        self._require_cuda(inp_img)
         x = inp_img.float().contiguous()
-        B, Cin, H, W = x.shape
-        if H % 8 or W % 8:
+        if x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError("Restormer needs H and W to be multiples of 8 (the tiler pads, utils.pad)")
-        dev = x.device
         pk = self._pack()
-        d1, d2, d3, d4 = self.dim, self.dim * 2, self.dim * 4, self.dim * 8
-        H2, W2, H3, W3, H4, W4 = H // 2, W // 2, H // 4, W // 4, H // 8, W // 8
-
-        def buf(name, ch, h, w):
-            return self._buf(name, B * ch * h * w, dev).view(B, ch, h, w)
-
-        cat1 = buf("cat1", 2 * d1, H, W)       # [up2_1 | enc1]   (restormer.py:272)
-        cat2 = buf("cat2", 2 * d2, H2, W2)     # [up3_2 | enc2]   (restormer.py:267)
-        cat3 = buf("cat3", 2 * d3, H3, W3)     # [up4_3 | enc3]   (restormer.py:262)
-        lat = buf("latent", d4, H4, W4)
-        dec3 = buf("dec3", d3, H3, W3)
-        dec2 = buf("dec2", d2, H2, W2)
-
-        e1 = cat1[:, d1:]
-        ops.conv3x3(pk["patch_embed"], x, e1, Cin, d1, bias=pk["patch_embed_b"])
-        if self.dual_pixel_task:
-            e1_in = buf("enc1_in", d1, H, W)
-            e1_in.copy_(e1)
-            if ops.TIMER is not None:
-                ops.TIMER.break_chain()            # a torch kernel sits between two timed launches
-        self._run_stage("encoder_level1", pk, e1)
-        e2 = cat2[:, d2:]
-        ops.conv3x3(pk["down1_2"], e1, e2, d1, d1 // 2, store_mode=1)
-        self._run_stage("encoder_level2", pk, e2)
-        e3 = cat3[:, d3:]
-        ops.conv3x3(pk["down2_3"], e2, e3, d2, d2 // 2, store_mode=1)
-        self._run_stage("encoder_level3", pk, e3)
-        ops.conv3x3(pk["down3_4"], e3, lat, d3, d3 // 2, store_mode=1)
-        self._run_stage("latent", pk, lat)
-
-        ops.conv3x3(pk["up4_3"], lat, cat3[:, :d3], d4, d4 * 2, store_mode=2)
-        rs3 = "reduce_chan_level3_s" in pk and (H3 * W3) % 4 == 0
-        ops.gemm1x1(pk["reduce_chan_level3" + ("_s" if rs3 else "")], cat3, dec3, d3, 2 * d3, bias=pk["reduce_chan_level3_b"],
-                    split=rs3)
-        self._run_stage("decoder_level3", pk, dec3)
-        ops.conv3x3(pk["up3_2"], dec3, cat2[:, :d2], d3, d3 * 2, store_mode=2)
-        rs2 = "reduce_chan_level2_s" in pk and (H2 * W2) % 4 == 0
-        ops.gemm1x1(pk["reduce_chan_level2" + ("_s" if rs2 else "")], cat2, dec2, d2, 2 * d2, bias=pk["reduce_chan_level2_b"],
-                    split=rs2)
-        self._run_stage("decoder_level2", pk, dec2)
-        ops.conv3x3(pk["up2_1"], dec2, cat1[:, :d1], d2, d2 * 2, store_mode=2)
-        # (decoder_level1 and refinement work on the same tensor: one chain, no planar round trip between them)
-        self._run_stage(("decoder_level1", "refinement"), pk, cat1)
-        tap = self.__dict__.get("_tap")
-        if tap is not None:                              # test tap: the trunk output before the `output` conv
-            tap["refinement"] = cat1.clone()
-
-        out = torch.empty(B, self.out_channels, H, W, dtype=torch.float32, device=dev)
-        if self.dual_pixel_task:
-            ops.gemm1x1(pk["skip_conv"], e1_in, cat1, d2, d1, res=cat1, bias=pk["skip_conv_b"])
-            ops.conv3x3(pk["output"], cat1, out, d2, self.out_channels, bias=pk["output_b"])
-        else:
-            ops.conv3x3(pk["output"], cat1, out, d2, self.out_channels, bias=pk["output_b"],
-                        res=x, res_mode=1)
-        return out
+        tap = self.__dict__.get("_tap")                  # test tap: the trunk output before the `output` conv
+        # (decoder_level1 and refinement arrive as one pair of names: one chain, no planar round trip between them)
+        return unet.forward(self, x, pk, lambda names, t, level: self._run_stage(names, pk, t),
+                            None if tap is None else lambda t: tap.__setitem__("refinement", t.clone()))
