@@ -91,6 +91,12 @@ SIGNATURES_GRAM = {
     "irm_dw_gram_cm_f16x3_f32": [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
 }
 
+#: YUV 4:2:0 planes to and from the float32 frame (yuv.hip), mirrors include/irm_hip_yuv.h one to one
+SIGNATURES_YUV = {
+    "irm_yuv420_to_rgb_f32": [_P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "irm_rgb_f32_to_yuv420": [_P, _P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -109,7 +115,8 @@ def load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(make -C image-restoration-models_amd/csrc).  There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM}.items():
+        for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM,
+                               **SIGNATURES_YUV}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

@@ -1,6 +1,7 @@
 """Glue API with the reference's call surface (src/utils.py): model factory,
 patch-config lookup and the tiled-patch inference loop; the metrics (metrics.py),
-the super-resolution resize (resize.py) and NIQE (niqe.py) are re-exported.
+the super-resolution resize (resize.py), NIQE (niqe.py) and the YUV 4:2:0
+conversions (yuv.py) are re-exported.
 
 The hot loop (reference: src/utils.py:353-454, one synchronous forward + D2H +
 numpy blend per tile) runs here as ONE device pipeline per image:
@@ -19,13 +20,15 @@ import numpy as np
 import torch
 from torch.nn import Module
 
-from . import _hip, deblurganv2, dncnn, mair, ops, rednet, restormer
+from . import _hip, deblurganv2, dncnn, mair, ops, rednet, restormer, yuv
 from .frames import device_constant, to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,  # noqa: F401
                       calculate_metrics_device, frame_metrics_basicsr_device, frame_metrics_device, psnr, ssim)
 from .niqe import (calculate_niqe, calculate_niqe_device, load_niqe_params, niqe_feature_distance,  # noqa: F401
                    niqe_features, niqe_features_device, niqe_gamma_table, niqe_plane, niqe_score)
 from .resize import imresize_device, imresize_host, mod_crop, resize_table  # noqa: F401
+from .yuv import (YUV_FORMATS, rgb_to_yuv420_device, rgb_to_yuv420_host, yuv420_to_rgb_device,  # noqa: F401
+                  yuv420_to_rgb_host)
 from .convnet_common import check_precision
 from .configs import PATCH_CONFIG, ROOT_RESULTS_DIR, ROOT_WEIGHTS_DIR
 from .restormer import Restormer
@@ -620,3 +623,57 @@ def run_model_chain(stages, input_img: np.ndarray, device: torch.device, need_de
                                             max_batch=getattr(m, 'max_tiles_per_batch', 8), unit_range=True, out=kind)
         output_img = to_host(frame)
     return output_img, (time.time() - start_time) * 1000
+
+
+def run_model_inference_yuv(model: Module, planes, device: torch.device, *, fmt, matrix="bt709", full_range=False,
+                            siting="left", luma_only=False, patch_size: int | None = None, patch_overlap: int = 32,
+                            need_degradation=False, noise_level=None):
+    """Restore one YUV 4:2:0 video frame: returns (planes, inference_time_ms), the planes in the format they came in
+    and the time from their upload through the download of the result, as run_model_inference's.
+
+    `planes` are numpy arrays, (y, u, v) for fmt "i420" and (y, uv) for "nv12" / "p010" (yuv.py has the layouts).
+    They go up as they are - 1.5 bytes per pixel, 3 for "p010" -, irm_yuv420_to_rgb_f32 makes the float32 RGB frame
+    in [0, 1], the device pipeline of run_model_inference runs on it with the hooks get_model_prediction picks for
+    the model class (unit_range=True, out="float32": the frame is never rounded to 255 RGB levels),
+    irm_rgb_f32_to_yuv420 makes the planes and they come down.  matrix, full_range and siting describe the frame
+    (DESIGN.md section 16).  A super-resolving model returns the planes of an s H x s W frame.
+
+    luma_only=True restores Y alone with a one-channel model (REDNet, the gray DnCNN): the chroma planes are not
+    uploaded and come back as they are, so an up-scaling model raises ValueError (the chroma would need a resize).
+    DeblurGANv2 raises ValueError: its hooks are defined on raw integer values."""
+    if model is None or not callable(model):
+        raise ValueError("run_model_inference_yuv: model must be a model, not None")
+    if isinstance(model, FPNMobileNet) or type(model).__module__.startswith(deblurganv2.__name__ + "."):
+        raise ValueError("run_model_inference_yuv: DeblurGANv2 normalises raw integer values and has no float32 "
+                         "frames; convert with yuv420_to_rgb_host and run it with get_model_prediction")
+    yuv._check_options(fmt, matrix, siting)
+    depth = YUV_FORMATS[fmt][1]
+    yuv._check_planes(planes, fmt, False, np.ndarray, (np.uint16,) if depth == 10 else (np.uint8,))
+    s = _upscale(model, need_degradation)
+    if luma_only and s > 1:
+        raise ValueError(f"luma_only with model.upscale = {s}: the chroma planes would need a resize")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _hip.HipLibraryError("run_model_inference_yuv runs on the GPU only (no CPU fallback); pass a 'cuda' device")
+    opts = dict(matrix=matrix, full_range=full_range, siting=siting, luma_only=luma_only)
+    start_time = time.time()
+    with torch.no_grad():
+        up = tuple(to_device(p, dev) for p in (planes[:1] if luma_only else planes))
+        frame = yuv420_to_rgb_device(up, fmt, **opts)
+        sigma = noise_level if (need_degradation and noise_level is not None) else None
+        frame, _ = tiled_forward_device(model, frame, patch_size, patch_overlap, isinstance(model, _PAD8_MODELS), sigma,
+                                        max_batch=getattr(model, 'max_tiles_per_batch', 8), unit_range=True,
+                                        out="float32")
+        if luma_only:
+            rgb_to_yuv420_device(frame, fmt, out=up, **opts)           # same size: Y is overwritten in place
+            result = (to_host(up[0]),) + tuple(planes[1:])
+        else:
+            # the planes of the result lie behind one another in one buffer, as a decoder lays them out: one download
+            oh, ow = frame.shape[0], frame.shape[1]
+            sizes = [oh * ow] + ([oh * ow // 4] * 2 if fmt == "i420" else [oh * ow // 2])
+            shapes = [(oh, ow)] + ([(oh // 2, ow // 2)] * 2 if fmt == "i420" else [(oh // 2, ow // 2, 2)])
+            buf = torch.empty(sum(sizes), dtype=up[0].dtype, device=dev)
+            rgb_to_yuv420_device(frame, fmt, out=tuple(p.view(s) for p, s in zip(buf.split(sizes), shapes)), **opts)
+            host = to_host(buf)
+            result = tuple(p.reshape(s) for p, s in zip(np.split(host, np.cumsum(sizes)[:-1]), shapes))
+    return result, (time.time() - start_time) * 1000

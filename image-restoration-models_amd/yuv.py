@@ -1,0 +1,247 @@
+"""YUV 4:2:0 video frames: I420, NV12 and P010 planes to the float32 RGB frame in [0, 1] of the
+device pipeline and back, on the GPU (irm_yuv420_to_rgb_f32, irm_rgb_f32_to_yuv420) and restated in numpy float32 on
+the host with the same operation order.  The reference has no YUV path; tests/yuv_model.py states the arithmetic."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _hip
+
+#: format -> (planes, bit depth); "p010" keeps its 10-bit code in the upper bits of a 16-bit word
+YUV_FORMATS = {"i420": (3, 8), "nv12": (2, 8), "p010": (2, 10)}
+#: matrix -> (Kr, Kb)
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+YUV_SITINGS = ("left", "center")
+
+
+def _check_options(fmt, matrix, siting) -> None:
+    if fmt not in YUV_FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(YUV_FORMATS)}, not {fmt!r}")
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix must be one of {sorted(YUV_MATRICES)}, not {matrix!r}")
+    if siting not in YUV_SITINGS:
+        raise ValueError(f"siting must be 'left' or 'center', not {siting!r}")
+
+
+def _check_planes(planes, fmt, luma_only: bool, kind, dtypes) -> tuple:
+    """(H, W) of the planes of one frame: their number, type (`kind`: np.ndarray or torch.Tensor), dtype and shapes.
+    With luma_only the chroma planes are not looked at and may be missing."""
+    n, _ = YUV_FORMATS[fmt]
+    what = "(y, u, v)" if n == 3 else "(y, uv)"
+    if not isinstance(planes, (tuple, list)) or not (len(planes) == n or (luma_only and len(planes) == 1)):
+        raise ValueError(f"{fmt!r} planes are {what}, not {type(planes).__name__}"
+                         + (f" of {len(planes)}" if isinstance(planes, (tuple, list)) else ""))
+    used = planes[:1] if luma_only else planes
+    for p in used:
+        if not isinstance(p, kind):
+            raise ValueError(f"{fmt!r} planes must be {kind.__name__}s, not {type(p).__name__}")
+        if p.dtype not in dtypes:
+            raise ValueError(f"{fmt!r} planes are {' or '.join(str(d) for d in dtypes)}, not {p.dtype}")
+    if len(planes[0].shape) != 2:
+        raise ValueError(f"the Y plane is [H][W], not shape {tuple(planes[0].shape)}")
+    h, w = (int(s) for s in planes[0].shape)
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        raise ValueError(f"4:2:0 frames have even, positive H and W, not {h} x {w}")
+    want = (h // 2, w // 2) if n == 3 else (h // 2, w // 2, 2)
+    for p in used[1:]:
+        if tuple(p.shape) != want:
+            raise ValueError(f"a chroma plane of a {h} x {w} {fmt!r} frame is {list(want)}, not {list(p.shape)}")
+    return h, w
+
+
+def _check_rgb(rgb, luma_only: bool, kind) -> tuple:
+    c = 1 if luma_only else 3
+    if not isinstance(rgb, kind) or len(rgb.shape) != 3 or rgb.shape[2] != c or str(rgb.dtype).split(".")[-1] != "float32":
+        raise ValueError(f"the frame is a float32 [H][W][{c}] {kind.__name__}" + (" with luma_only" if luma_only else ""))
+    h, w = int(rgb.shape[0]), int(rgb.shape[1])
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        raise ValueError(f"4:2:0 frames have even, positive H and W, not {h} x {w}")
+    return h, w
+
+
+def _constants(matrix, full_range, depth) -> dict:
+    """The float32 constants of both directions: the float32 roundings of the float64 expressions."""
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    s, top = float(2 ** (depth - 8)), float(2 ** depth - 1)
+    f = np.float32
+    return dict(y0=f(0.0 if full_range else 16.0 * s), yr=f(top if full_range else 219.0 * s), c0=f(128.0 * s),
+                cr=f(top if full_range else 224.0 * s), kr=f(kr), kg=f(kg), kb=f(kb), r_cr=f(2.0 * (1.0 - kr)),
+                b_cb=f(2.0 * (1.0 - kb)), g_cb=f(2.0 * kb * (1.0 - kb) / kg), g_cr=f(2.0 * kr * (1.0 - kr) / kg),
+                top=f(top))
+
+
+# ---------------------------------------------------------------------------
+# the numpy float32 twins
+
+def _split_planes(planes, fmt, luma_only):
+    """Integer codes (y, u, v) as int64 arrays; u, v None with luma_only."""
+    shift = 6 if fmt == "p010" else 0
+    y = planes[0].astype(np.int64) >> shift
+    if luma_only:
+        return y, None, None
+    if fmt == "i420":
+        return y, planes[1].astype(np.int64), planes[2].astype(np.int64)
+    return y, planes[1][:, :, 0].astype(np.int64) >> shift, planes[1][:, :, 1].astype(np.int64) >> shift
+
+
+def _upsample16(c: np.ndarray, siting: str) -> np.ndarray:
+    """Sixteen times the linearly up-sampled chroma codes, [H/2][W/2] -> [H][W], edges clamped: integers."""
+    p = np.pad(c, 1, mode="edge")
+    rows = np.empty((2 * c.shape[0], p.shape[1]), np.int64)
+    rows[0::2] = 3 * p[1:-1] + p[:-2]                   # a quarter above the sample
+    rows[1::2] = 3 * p[1:-1] + p[2:]                    # a quarter below
+    left, mid, right = rows[:, :-2], rows[:, 1:-1], rows[:, 2:]
+    out = np.empty((rows.shape[0], 2 * c.shape[1]), np.int64)
+    if siting == "center":
+        out[:, 0::2] = 3 * mid + left
+        out[:, 1::2] = 3 * mid + right
+    else:
+        out[:, 0::2] = 4 * mid                          # on the sample
+        out[:, 1::2] = 2 * mid + 2 * right              # midway between two
+    return out
+
+
+def yuv420_to_rgb_host(planes, fmt, matrix="bt709", full_range=False, siting="left", luma_only=False) -> np.ndarray:
+    """The planes of one 4:2:0 frame -> float32 [H][W][3] RGB in [0, 1] ([H][W][1], the luma, with luma_only): the
+    numpy twin of yuv420_to_rgb_device, bit for bit.  `planes` is (y, u, v) for "i420" and (y, uv) for "nv12" /
+    "p010" (uint16, the code in the upper ten bits)."""
+    _check_options(fmt, matrix, siting)
+    depth = YUV_FORMATS[fmt][1]
+    _check_planes(planes, fmt, luma_only, np.ndarray, (np.uint16,) if depth == 10 else (np.uint8,))
+    k = _constants(matrix, full_range, depth)
+    f = np.float32
+    y, u, v = _split_planes(planes, fmt, luma_only)
+    yp = (y.astype(f) - k["y0"]) / k["yr"]
+    if luma_only:
+        return np.clip(yp, f(0), f(1))[:, :, None]
+    cb = (_upsample16(u, siting).astype(f) * f(0.0625) - k["c0"]) / k["cr"]
+    cr = (_upsample16(v, siting).astype(f) * f(0.0625) - k["c0"]) / k["cr"]
+    rgb = np.empty(y.shape + (3,), f)
+    rgb[:, :, 0] = yp + k["r_cr"] * cr
+    rgb[:, :, 1] = (yp - k["g_cb"] * cb) - k["g_cr"] * cr
+    rgb[:, :, 2] = yp + k["b_cb"] * cb
+    return np.clip(rgb, f(0), f(1), out=rgb)
+
+
+def _filter_chroma(c: np.ndarray, siting: str) -> np.ndarray:
+    """Per-pixel chroma [H][W] -> [H/2][W/2] at the chroma site; the order of the additions is the kernel's."""
+    f = np.float32
+    if siting == "center":
+        return ((c[0::2, 0::2] + c[0::2, 1::2]) + (c[1::2, 0::2] + c[1::2, 1::2])) * f(0.25)
+    m, r = c[:, 0::2], c[:, 1::2]
+    left = np.concatenate([m[:, :1], r[:, :-1]], axis=1)            # the column before the even one, clamped
+    h = ((left + (m + m)) + r) * f(0.25)
+    return (h[0::2] + h[1::2]) * f(0.5)
+
+
+def _codes(off, rng, v, top) -> np.ndarray:
+    return np.rint(np.clip(off + rng * v, np.float32(0), top)).astype(np.int64)
+
+
+def rgb_to_yuv420_host(rgb, fmt, matrix="bt709", full_range=False, siting="left", luma_only=False, out=None) -> tuple:
+    """float32 [H][W][3] RGB -> the planes of a 4:2:0 frame in `fmt`, the numpy twin of rgb_to_yuv420_device, bit for
+    bit; values outside [0, 1] are legal (the codes are clipped).  With luma_only the frame is [H][W][1] and only Y is
+    made: `out`, the planes of the frame it belongs to, is required, its Y plane is overwritten and its chroma planes
+    come back as they are.  Without luma_only `out` is optional (planes to write into)."""
+    _check_options(fmt, matrix, siting)
+    n, depth = YUV_FORMATS[fmt]
+    h, w = _check_rgb(rgb, luma_only, np.ndarray)
+    dt = np.uint16 if depth == 10 else np.uint8
+    if out is None and luma_only:
+        raise ValueError("luma_only writes the Y plane alone: pass the frame's planes as out, their chroma is kept")
+    if out is not None and _check_planes(out, fmt, False, np.ndarray, (dt,)) != (h, w):
+        raise ValueError(f"out holds the planes of another frame size than {h} x {w}")
+    k = _constants(matrix, full_range, depth)
+    shift = 6 if fmt == "p010" else 0
+    if out is None:
+        out = ((np.empty((h, w), dt), np.empty((h // 2, w // 2), dt), np.empty((h // 2, w // 2), dt)) if n == 3
+               else (np.empty((h, w), dt), np.empty((h // 2, w // 2, 2), dt)))
+    if luma_only:
+        out[0][...] = _codes(k["y0"], k["yr"], rgb[:, :, 0], k["top"]) << shift
+        return tuple(out)
+    r, g, b = rgb[:, :, 0], rgb[:, :, 1], rgb[:, :, 2]
+    yp = (k["kr"] * r + k["kg"] * g) + k["kb"] * b
+    cb = _filter_chroma((b - yp) / k["b_cb"], siting)
+    cr = _filter_chroma((r - yp) / k["r_cr"], siting)
+    out[0][...] = _codes(k["y0"], k["yr"], yp, k["top"]) << shift
+    u, v = (out[1], out[2]) if n == 3 else (out[1][:, :, 0], out[1][:, :, 1])
+    u[...] = _codes(k["c0"], k["cr"], cb, k["top"]) << shift
+    v[...] = _codes(k["c0"], k["cr"], cr, k["top"]) << shift
+    return tuple(out)
+
+
+# ---------------------------------------------------------------------------
+# the device calls
+
+def _device_planes(planes, fmt, luma_only) -> tuple:
+    """The checks of device planes that need no GPU call and the operands the kernels take: (h, w, y, u, v, step,
+    pitch_y, pitch_c) with u, v views of the chroma plane(s), None with luma_only."""
+    n, depth = YUV_FORMATS[fmt]
+    dtypes = (torch.uint16, torch.int16) if depth == 10 else (torch.uint8,)
+    h, w = _check_planes(planes, fmt, luma_only, torch.Tensor, dtypes)
+    used = planes[:1] if luma_only else planes
+    if any(p.device != planes[0].device or p.dtype != planes[0].dtype for p in used):
+        raise ValueError("the planes of one frame must share device and dtype")
+    y = planes[0]
+    if y.stride(1) != 1 or y.stride(0) < w:
+        raise ValueError(f"the Y plane needs unit stride inside a row and a row stride of at least {w}, not {y.stride()}")
+    if luma_only:
+        return h, w, y, None, None, 1, y.stride(0), 0
+    if n == 3:
+        for p in planes[1:]:
+            if p.stride(1) != 1 or p.stride(0) < w // 2:
+                raise ValueError(f"a planar chroma plane needs unit stride inside a row and a row stride of at least "
+                                 f"{w // 2}, not {p.stride()}")
+        if planes[1].stride(0) != planes[2].stride(0):
+            raise ValueError("the U and the V plane must share their row stride")
+        return h, w, y, planes[1], planes[2], 1, y.stride(0), planes[1].stride(0)
+    uv = planes[1]
+    if uv.stride(2) != 1 or uv.stride(1) != 2 or uv.stride(0) < w:
+        raise ValueError(f"the UV plane needs strides (row >= {w}, 2, 1), not {uv.stride()}")
+    return h, w, y, uv[:, :, 0], uv[:, :, 1], 2, y.stride(0), uv.stride(0)
+
+
+def _kernel_options(fmt, matrix, full_range, siting, luma_only) -> tuple:
+    depth = YUV_FORMATS[fmt][1]
+    return (depth, int(fmt == "p010"), int(matrix == "bt709"), int(bool(full_range)), int(siting == "center"),
+            int(bool(luma_only)))
+
+
+def yuv420_to_rgb_device(planes, fmt, matrix="bt709", full_range=False, siting="left", luma_only=False) -> torch.Tensor:
+    """Device planes of one 4:2:0 frame -> a contiguous float32 [H][W][3] RGB frame in [0, 1] on the same device
+    ([H][W][1], the luma, with luma_only; the chroma planes are then not read and may be left out).  `planes` is
+    (y, u, v) for "i420" and (y, uv) for "nv12" / "p010": uint8 tensors, for "p010" uint16 or its int16 bit pattern.
+    They may be row-pitched views: unit stride inside a row (2 inside UV), any row stride of at least the width.
+    Enqueued on the current stream; ValueError before any GPU call for everything else."""
+    _check_options(fmt, matrix, siting)
+    h, w, y, u, v, step, pitch_y, pitch_c = _device_planes(planes, fmt, luma_only)
+    rgb = torch.empty(h, w, 1 if luma_only else 3, dtype=torch.float32, device=y.device)
+    _hip.call("irm_yuv420_to_rgb_f32", _hip.ptr(y), _hip.ptr(u), _hip.ptr(v), step, pitch_y, pitch_c,
+              *_kernel_options(fmt, matrix, full_range, siting, luma_only), h, w, _hip.ptr(rgb))
+    return rgb
+
+
+def rgb_to_yuv420_device(rgb, fmt, matrix="bt709", full_range=False, siting="left", luma_only=False, out=None) -> tuple:
+    """A float32 [H][W][3] device frame -> the planes of a 4:2:0 frame in `fmt` on the same device: contiguous new
+    tensors (uint8; for "p010" the uint16 bit pattern in int16 tensors), or `out`, planes as yuv420_to_rgb_device
+    takes them (row-pitched views included: nothing outside [H][W] of a plane is written).  Values outside [0, 1] are
+    legal.  With luma_only the frame is [H][W][1] and only the Y plane of `out` - required - is written; its chroma
+    planes come back as they are."""
+    _check_options(fmt, matrix, siting)
+    n, depth = YUV_FORMATS[fmt]
+    h, w = _check_rgb(rgb, luma_only, torch.Tensor)
+    if out is None and luma_only:
+        raise ValueError("luma_only writes the Y plane alone: pass the frame's planes as out, their chroma is kept")
+    if out is None:
+        dt = torch.int16 if depth == 10 else torch.uint8
+        shapes = [(h, w), (h // 2, w // 2), (h // 2, w // 2)] if n == 3 else [(h, w), (h // 2, w // 2, 2)]
+        out = tuple(torch.empty(s, dtype=dt, device=rgb.device) for s in shapes)
+    oh, ow, y, u, v, step, pitch_y, pitch_c = _device_planes(out, fmt, luma_only)
+    if (oh, ow) != (h, w) or y.device != rgb.device:
+        raise ValueError(f"out holds the planes of another device or frame size than {h} x {w}")
+    rgb = rgb.contiguous()
+    _hip.call("irm_rgb_f32_to_yuv420", _hip.ptr(rgb), _hip.ptr(y), _hip.ptr(u), _hip.ptr(v), step, pitch_y,
+              pitch_c, *_kernel_options(fmt, matrix, full_range, siting, luma_only), h, w)
+    return tuple(out)

@@ -535,6 +535,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- the q, k depth-wise conv inside the Gram pass at C = 192 / 384: irm_dw_gram_cm_f16x3_f32 */
 #include "irm_hip_gram.h"
 
+/* ---- YUV 4:2:0 video frames to and from the float32 frame: irm_yuv420_to_rgb_f32, irm_rgb_f32_to_yuv420 */
+#include "irm_hip_yuv.h"
+
 #ifdef __cplusplus
 }
 #endif

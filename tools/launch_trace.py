@@ -54,7 +54,8 @@ def run_case(out, name):
         sizes = np.load(os.path.join(ROOT, "tests", "golden", "fpn_inception.npz"))["fi_sizes_128x160"]
         inputs += [synth.uniform(11, f"trace_enc{i}", (1, c, int(s[0]), int(s[1])), -1.0, 1.0).cuda()
                    for i, (c, s) in enumerate(zip((32, 64, 192, 1088, 2080), sizes))]
-    sigs = {**_hip.SIGNATURES, **_hip.SIGNATURES_HALF, **_hip.SIGNATURES_FRAMES, **_hip.SIGNATURES_GRAM}
+    sigs = {**_hip.SIGNATURES, **_hip.SIGNATURES_HALF, **_hip.SIGNATURES_FRAMES, **_hip.SIGNATURES_GRAM,
+            **_hip.SIGNATURES_YUV}
     trace, call = [], _hip.call
 
     def logged(entry, *args):
