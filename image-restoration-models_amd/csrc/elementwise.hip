@@ -8,7 +8,12 @@
 // pixels (16-byte loads) and runs Welford over its share of the C rows, so x is
 // read exactly once.  A workgroup = PQ pixel quads x G = 256 / PQ channel groups
 // (group g takes channels g, g + G, ...; the partials are merged in group order by
-// Chan's formula).  PQ follows the plane size only (64 / 16 / 4 quads for large /
+// Chan's formula).  The MEAN written out is the plain sum / C, not the merged running
+// mean: a running mean is rounded at every update, and on a nearly flat pixel (all
+// channels within 2^-12 of 1, variance far below eps) one ulp of it is 1.9e-5 of
+// normalised deviation on every channel with the same sign; the sum of such a pixel is
+// exact.  The running means still centre the M2 sums.
+// PQ follows the plane size only (64 / 16 / 4 quads for large /
 // medium / small planes - small planes need the channel axis for parallelism: a
 // 32x32 level has 4 workgroups of 96-deep dependent loops otherwise), never the
 // batch size: an image's statistics do not depend on what it is batched with.
@@ -16,14 +21,15 @@ template <bool VEC, int PQ>
 __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__ x, long x_bs,
                                                        float* __restrict__ stats, int C, int N, float eps) {
     constexpr int G = 256 / PQ;
-    __shared__ float4 pm[G][PQ], pq[G][PQ];
+    __shared__ float4 pm[G][PQ], pq[G][PQ], ps[G][PQ];
     const int b = blockIdx.y;
     const int q = threadIdx.x % PQ, g = threadIdx.x / PQ;
     const int n = (blockIdx.x * PQ + q) * 4;
     const float* p = x + (long)b * x_bs;
-    float4 mean = make_float4(0.f, 0.f, 0.f, 0.f), m2 = mean;
+    float4 mean = make_float4(0.f, 0.f, 0.f, 0.f), m2 = mean, sum = mean;
     int cnt = 0;
     auto push = [&](const float4& v) {
+        sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
         const float rc = 1.0f / (float)(++cnt);
         float d;
         d = v.x - mean.x; mean.x += d * rc; m2.x += d * (v.x - mean.x);
@@ -44,6 +50,7 @@ __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__
     }
     pm[g][q] = mean;
     pq[g][q] = m2;
+    ps[g][q] = sum;
     __syncthreads();
     if (g != 0 || n >= N) return;
     // Chan's merge of (count, mean, M2) partials, fixed order 0, 1, ..., G - 1
@@ -52,7 +59,8 @@ __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__
         const int ck = (C - k + G - 1) / G;          // channels k, k + G, ... < C
         if (ck <= 0) break;
         const float nb = (float)ck, nt = na + nb;
-        const float4 mb = pm[k][q], qb = pq[k][q];
+        const float4 mb = pm[k][q], qb = pq[k][q], sb = ps[k][q];
+        sum.x += sb.x; sum.y += sb.y; sum.z += sb.z; sum.w += sb.w;
         const float f = nb / nt, g2 = na * nb / nt;
         float d;
         d = mb.x - mean.x; mean.x += d * f; m2.x += qb.x + d * d * g2;
@@ -67,8 +75,9 @@ __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__
     rstd.y = 1.0f / sqrtf(m2.y * inv + eps);
     rstd.z = 1.0f / sqrtf(m2.z * inv + eps);
     rstd.w = 1.0f / sqrtf(m2.w * inv + eps);
+    const float fc = (float)C;
     float* s = stats + (long)b * 2 * N;
-    irm_st4<VEC>(s, n, N, mean);
+    irm_st4<VEC>(s, n, N, make_float4(sum.x / fc, sum.y / fc, sum.z / fc, sum.w / fc));
     irm_st4<VEC>(s + N, n, N, rstd);
 }
 

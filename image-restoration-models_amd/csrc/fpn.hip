@@ -10,8 +10,12 @@
 
 // ---------------------------------------------------------------------------
 // per (b, c) plane: mean and 1/sqrt(biased var + eps); two passes (mean, then centred squares; the
-// second pass re-reads the plane from L2), fixed-order block reduction.
-__device__ __forceinline__ float block_sum256(float v, float* sh) {
+// second pass re-reads the plane from L2), fixed-order block reduction.  The sums run in float64: the
+// normalised value (x - mean) rstd sees an error of the mean through rstd, up to 316 on a plane that is
+// constant up to its border (a checkered frame behind the stride-2 stem), and a float32 sum of a few
+// thousand nearly equal values leaves the mean several ulps off - the reference's float32 norm accumulates
+// in float64 too.  The kernel stays bound by its loads.
+__device__ __forceinline__ double block_sum256d(double v, double* sh) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     const int w = threadIdx.x >> 6;
@@ -23,18 +27,18 @@ __device__ __forceinline__ float block_sum256(float v, float* sh) {
 
 __global__ __launch_bounds__(256) void chan_stats_kernel(const float* __restrict__ x, long x_bs, float* __restrict__ st,
                                                          int C, int N, float eps) {
-    __shared__ float sh[4];
+    __shared__ double sh[4];
     const int c = blockIdx.x, b = blockIdx.y;
     const float* p = x + (long)b * x_bs + (long)c * N;
-    float s = 0.0f;
-    for (int i = threadIdx.x; i < N; i += 256) s += p[i];
-    const float mean = block_sum256(s, sh) / (float)N;
-    float q = 0.0f;
-    for (int i = threadIdx.x; i < N; i += 256) { const float d = p[i] - mean; q += d * d; }
-    const float var = block_sum256(q, sh) / (float)N;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < N; i += 256) s += (double)p[i];
+    const double mean = block_sum256d(s, sh) / (double)N;
+    double q = 0.0;
+    for (int i = threadIdx.x; i < N; i += 256) { const double d = (double)p[i] - mean; q += d * d; }
+    const double var = block_sum256d(q, sh) / (double)N;
     if (threadIdx.x == 0) {
-        st[((long)b * C + c) * 2] = mean;
-        st[((long)b * C + c) * 2 + 1] = 1.0f / sqrtf(var + eps);
+        st[((long)b * C + c) * 2] = (float)mean;
+        st[((long)b * C + c) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }
 }
 
@@ -49,15 +53,17 @@ extern "C" int irm_chan_stats_f32(const float* x, long x_bs, float* stats, int B
 // Large planes (a 1280x720 frame is ONE tile for this model): split every plane over several workgroups.
 // Each thread folds 16-element register chunks (exact two-pass mean / M2 per chunk) into a running
 // (n, mean, M2) triple with Chan's merge; lanes, waves and finally the slices are merged in a fixed order,
-// so the result does not depend on scheduling.  ws: [B*C][nsplit][3] floats.
-struct WF { float n, mean, m2; };
+// so the result does not depend on scheduling.  ws: [B*C][nsplit][3] floats.  The triples are float64 inside the
+// kernels, as the sums of chan_stats_kernel and for its reason (a merged mean is rounded at every merge); a slice's
+// triple crosses the workspace as floats, one rounding of a mean over >= 4096 elements.
+struct WF { double n, mean, m2; };
 __device__ __forceinline__ WF wf_merge(WF a, WF b) {
-    const float n = a.n + b.n;
-    if (n == 0.0f) return a;
-    const float d = b.mean - a.mean, f = b.n / n;
+    const double n = a.n + b.n;
+    if (n == 0.0) return a;
+    const double d = b.mean - a.mean, f = b.n / n;
     WF r;
     r.n = n;
-    r.mean = fmaf(d, f, a.mean);
+    r.mean = fma(d, f, a.mean);
     r.m2 = a.m2 + b.m2 + d * d * a.n * f;
     return r;
 }
@@ -70,7 +76,7 @@ __global__ __launch_bounds__(256) void chan_partial_kernel(const float* __restri
     const int nv = N >> 2;                                   // float4 units (N % 4 == 0 on this path)
     const int per = ((nv + nsplit - 1) / nsplit + 3) & ~3;   // units per slice, multiple of 4
     const int beg = sp * per, end = min(beg + per, nv);
-    WF acc{0.f, 0.f, 0.f};
+    WF acc{0.0, 0.0, 0.0};
     for (int i = beg + threadIdx.x * 4; i < end; i += 1024) {
         float v[16];
         int cnt = 0;
@@ -84,15 +90,15 @@ __global__ __launch_bounds__(256) void chan_partial_kernel(const float* __restri
                 v[4 * j] = v[4 * j + 1] = v[4 * j + 2] = v[4 * j + 3] = 0.0f;
             }
         }
-        float s = 0.0f;
+        double s = 0.0;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) s += v[j];
+        for (int j = 0; j < 16; ++j) s += (double)v[j];
         WF ch;
-        ch.n = (float)cnt;
+        ch.n = (double)cnt;
         ch.mean = s / ch.n;
-        float q = 0.0f;
+        double q = 0.0;
 #pragma unroll
-        for (int j = 0; j < 16; ++j) { const float d = v[j] - ch.mean; q += j < cnt ? d * d : 0.0f; }
+        for (int j = 0; j < 16; ++j) { const double d = (double)v[j] - ch.mean; q += j < cnt ? d * d : 0.0; }
         ch.m2 = q;
         acc = wf_merge(acc, ch);
     }
@@ -108,7 +114,7 @@ __global__ __launch_bounds__(256) void chan_partial_kernel(const float* __restri
     if (threadIdx.x == 0) {
         const WF r = wf_merge(wf_merge(sh[0], sh[1]), wf_merge(sh[2], sh[3]));
         float* o = ws + (((long)b * C + c) * nsplit + sp) * 3;
-        o[0] = r.n; o[1] = r.mean; o[2] = r.m2;
+        o[0] = (float)r.n; o[1] = (float)r.mean; o[2] = (float)r.m2;
     }
 }
 
@@ -117,10 +123,10 @@ __global__ __launch_bounds__(64) void chan_finish_kernel(const float* __restrict
     const int pl = blockIdx.x * 64 + threadIdx.x;
     if (pl >= planes) return;
     const float* w = ws + (long)pl * nsplit * 3;
-    WF acc{w[0], w[1], w[2]};
-    for (int i = 1; i < nsplit; ++i) acc = wf_merge(acc, WF{w[3 * i], w[3 * i + 1], w[3 * i + 2]});
-    st[(long)pl * 2] = acc.mean;
-    st[(long)pl * 2 + 1] = 1.0f / sqrtf(acc.m2 / acc.n + eps);
+    WF acc{(double)w[0], (double)w[1], (double)w[2]};
+    for (int i = 1; i < nsplit; ++i) acc = wf_merge(acc, WF{(double)w[3 * i], (double)w[3 * i + 1], (double)w[3 * i + 2]});
+    st[(long)pl * 2] = (float)acc.mean;
+    st[(long)pl * 2 + 1] = (float)(1.0 / sqrt(acc.m2 / acc.n + (double)eps));
 }
 
 extern "C" int irm_chan_stats_ws_f32(const float* x, long x_bs, float* stats, float* ws, long ws_floats, int B, int C,

@@ -377,7 +377,10 @@ __global__ __launch_bounds__(512, 2) void lnpw_dw_fused_kernel(FusedArgs a) {
                     for (int e = 0; e < 8; ++e) { v[ks][e] = xr[j][ks][e]; s += (FULL || e < kl[ks]) ? v[ks][e] : 0.f; }
                 s += __shfl_xor(s, 16);
                 s += __shfl_xor(s, 32);
-                const float mean = s * invC;
+                // ONE rounded product (opaque to the compiler): contracted into d = fma(-s, invC, v), the unrounded s * fl(1 / C)
+                // leaves every channel of a flat pixel a residual of 3e-8 x its value - and this phase normalises to unit RMS
+                float mean = s * invC;
+                asm volatile("" : "+v"(mean));
                 float q = 0.f;
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)

@@ -148,12 +148,14 @@ def _f64(p):
     return {k: (v.double() if v.is_floating_point() else v) for k, v in p.items()}
 
 
-def _oracle(case, p):
+def _oracle(case, p, frame=None, x=None):
     """{row: (y64, e_32)} of a case: 'out', and for Restormer also 'refinement' (the trunk before the output conv,
-    whose gain 0.02 attenuates the trunk's error in the output)."""
-    if case not in _ORACLE:
+    whose gain 0.02 attenuates the trunk's error in the output).  frame, x: another input than the case's seeded noise
+    (tests/test_gpu_degenerate_models.py), cached under (case, frame)."""
+    key = case if frame is None else (case, frame)
+    if key not in _ORACLE:
         fn = CASES[case][3]
-        x, encs = _inputs(case)
+        x, encs = _inputs(case) if frame is None else (x, None)
         res = {}
         with torch.no_grad():
             for dt, pp in ((torch.float32, p), (torch.float64, _f64(p))):
@@ -163,13 +165,13 @@ def _oracle(case, p):
                 else:
                     y = fn(x.to(dt), pp, tap)
                 res[dt] = dict(out=y, **tap)
-        _ORACLE[case] = {r: (res[torch.float64][r], float((res[torch.float32][r].double() - res[torch.float64][r]).abs().max()))
+        _ORACLE[key] = {r: (res[torch.float64][r], float((res[torch.float32][r].double() - res[torch.float64][r]).abs().max()))
                          for r in res[torch.float64]}
-    return _ORACLE[case]
+    return _ORACLE[key]
 
 
-def _run_gpu(case, dev, model, tap):
-    x, encs = _inputs(case)
+def _run_gpu(case, dev, model, tap, x=None):
+    x, encs = _inputs(case) if x is None else (x, None)
     if tap:
         model._tap = {}
     with torch.no_grad():
