@@ -10,7 +10,9 @@ allocations cannot see a read or a store one row, one float4 or one partial bloc
   * an output or workspace lies between sentinels (`sentinel_out`), and `intact` says whether every element outside
     the view, the slack between batch images included, still holds the sentinel.
 
-Plain functions, no fixtures; tests/test_guards_cpu.py is the positive control of every check below.
+`Guards` holds the guarded operands of one launch sequence and `clean` brings a result to the host through the NaN check.
+
+Plain functions and one holder class, no fixtures; tests/test_guards_cpu.py is the positive control of every check below.
 """
 import math
 
@@ -74,6 +76,14 @@ def sentinel_out(shape, dev, dtype=torch.float32, pad=PAD, batch_slack=0):
     return _place(shape, dtype, dev, sentinel(dtype), pad, batch_slack)
 
 
+def channel_slice(dev, B, C, extra, ch, H, W, off, fill):
+    """A [B, C, H, W] channel slice at channel `ch` of a [B, C + extra, H, W] float32 buffer that starts `off` floats into
+    its allocation, everything holding `fill`.  Returns (flat allocation, view)."""
+    N = H * W
+    flat = torch.full((B * (C + extra) * N + 4,), fill, dtype=torch.float32, device=dev)
+    return flat, flat.as_strided((B, C, H, W), ((C + extra) * N, N, W, 1), off + ch * N)
+
+
 def outside(buf, view):
     """Boolean mask over `buf`: True where an element does not belong to `view`."""
     mask = torch.ones(buf.shape, dtype=torch.bool, device=buf.device)
@@ -90,6 +100,58 @@ def intact(buf, view):
 
 def has_nan(t):
     return bool(torch.isnan(t).any())
+
+
+#: elements between the images of a strided operand (a multiple of 4: rows stay 16-byte aligned)
+SLACK = 8
+
+
+class Guards:
+    """The guarded operands of one launch sequence: inp() bands an input, out() places an output or a workspace and
+    remembers it, check() asserts that every remembered surrounding is intact.  Every buffer stays alive as long as
+    the object does: a raw pointer taken from a temporary view would otherwise outlive its allocation."""
+
+    def __init__(self, dev):
+        self.dev, self.outs, self.ins = dev, [], []
+
+    def inp(self, t, slack=0, fill=None):
+        if t is None:
+            return None
+        buf, view = banded(t, self.dev, fill, batch_slack=slack)
+        self.ins.append(buf)
+        return view
+
+    def out(self, name, shape, dtype=torch.float32, slack=0):
+        buf, view = sentinel_out(shape, self.dev, dtype, batch_slack=slack)
+        self.outs.append((name, buf, view))
+        return view
+
+    def check(self):
+        torch.cuda.synchronize()
+        bad = [name for name, buf, view in self.outs if not intact(buf, view)]
+        assert not bad, f"writes outside: {bad}"
+
+
+def clean(t):
+    """The result on the host, after the check that no NaN (a guard element of an input) reached it."""
+    t = t.cpu().contiguous()
+    assert not has_nan(t), "a NaN from outside an input reached the result"
+    return t
+
+
+def guarded_fold(g, qkv, B, C, heads, N, temp, wout, part=None, nready=None, **kw):
+    """ops.mdta_fold with part / gsum at exactly their record sizes and the folded matrix between sentinels of the Guards
+    `g`; returns (attention, folded matrix)."""
+    from irm_amd import ops
+    _, nchunk, rec = ops.mdta_plan(B, C, heads, N)
+    c = C // heads
+    if part is None:
+        part = g.out("part", (B * heads * nchunk * rec,))
+    gsum, attn = g.out("gsum", (B * heads * rec,)), g.out("attn", (B, heads, c, c))
+    mfold = g.out("mfold", (B * (ops.mfold_frag_numel(C) if kw.get("frag") else ops.mfold_numel(C)),))
+    mfold.zero_()
+    ops.mdta_fold(qkv, part, gsum, temp, wout, mfold, C, heads, attn=attn, nchunk_ready=nready, **kw)
+    return attn, mfold
 
 
 def two_fills(run):

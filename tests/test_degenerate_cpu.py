@@ -8,7 +8,7 @@ import torch
 import degenerate as dg
 from irm_amd import synth
 from oracle import restormer_ref
-from test_gpu_precision import CASES, _cpu_params, _f64
+from ledger import CASES, cpu_params, f64
 
 KS = (48, 96, 192, 384)
 
@@ -105,12 +105,12 @@ def test_oracles_are_finite_on_frames(case, kind):
     K e_32 + F max|y64| of the GPU ledger has a yardstick on every frame.  The one exception is exact: a bias-free network
     maps a black tile to zeros at every layer, in both precisions."""
     factory, shape, (lo, hi), fn, _ = CASES[case]
-    p = _cpu_params(factory().load_synthetic(42))
+    p = cpu_params(factory().load_synthetic(42))
     x = dg.frame(kind, shape, lo, hi)
     t32, t64 = {}, {}
     with torch.no_grad():
         y32 = dict(out=fn(x, p, t32), **t32)
-        y64 = dict(out=fn(x.double(), _f64(p), t64), **t64)
+        y64 = dict(out=fn(x.double(), f64(p), t64), **t64)
     assert set(y32) == set(y64) and ("refinement" in y64) == case.startswith("restormer")
     for row in y64:
         assert bool(torch.isfinite(y32[row]).all()) and bool(torch.isfinite(y64[row]).all()), row

@@ -1,13 +1,9 @@
 """Every fp32 instantiation behind the dense 3x3-conv entry points, at its edges, against float64.
 
 irm_conv3x3_ep_f32 (csrc/conv3x3.hip), irm_conv3x3_f16x3_ep_f32 (csrc/conv3x3_f16.hip) and irm_conv3x3_thin_f32
-(csrc/conv3x3_thin.hip) pick one of 24 kernel instantiations.  CONV_VARIANTS lists them, expected_conv_variant() restates
-the three dispatches in Python, passes_per_group() restates how the output-channel passes are dealt to the workgroup
-groups, and CASES places cases on each instantiation's edges: several passes in one workgroup, groups with unequal pass
-counts, a ragged last pass, a last tile with Co % 16 != 0, a half-full last input stage, partial row and column tiles,
-channel slices of larger buffers, the scalar and the 16-byte store path of the generic kernel, and every epilogue.  The
-launch planner shrinks ct on images this small, so every case passes ct and ygroups explicitly (ops.plan_conv3x3 keeps
-explicit values).
+(csrc/conv3x3_thin.hip) pick one of 24 kernel instantiations.  tests/variant_model.py lists them (CONV_VARIANTS), restates
+the three dispatches and the dealing of the output-channel passes in Python, and holds the cases (CONV_CASES) placed on
+each instantiation's edges; this file checks that table and runs every case.
 
 For each case, on the same seeded inputs:
   e    = max|y_gpu - y64|   (y64: F.conv2d + the epilogue in float64 on the CPU)
@@ -26,218 +22,17 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+from block_model import F, K, conv_epilogue
+from guards import channel_slice as _slice
 from irm_amd import _hip, ops, synth
-from test_gpu_precision import F, K
+from variant_model import CONV_CASE_IDS as CASE_IDS
+from variant_model import CONV_CASES as CASES
+from variant_model import (CONV_VARIANTS, EXACT_CTS, SPLIT_CTS, case_passes, case_plan, case_variant, expected_conv_variant,
+                           layout, out_shape, pass_structure, passes_per_group, split, thin_in, thin_out)
+from variant_model import conv_generic as generic
+from variant_model import conv_ring as ring
 
 SENTINEL = 7.0
-EXACT_CTS = (1, 2, 3, 4, 6)             # the two ct switches of irm_conv3x3_ep_f32 (conv3x3.hip)
-SPLIT_CTS = (1, 2, 3, 4, 8, 12)         # output tiles per pass: the ct switch of irm_conv3x3_f16x3_ep_f32
-
-
-# --------------------------------------------------------------------------- the variant table and its dispatch mirror
-def ring(ct):
-    return f"conv3x3_ring_kernel<{ct}, 3>"              # launch_conv_ring (conv3x3.hip): NS = 3
-
-
-def generic(ct):
-    return f"conv3x3_kernel<{ct}>"
-
-
-def split(ct):
-    """ct 1 ... 4: one weight chunk of ct tiles; 8 / 12: 2 / 3 chunks of 4 (the ct switch of irm_conv3x3_f16x3_ep_f32)."""
-    return f"conv3x3_f16x3_kernel<{min(ct, 4)}, {max(1, ct // 4)}>"
-
-
-def thin_in(ci):
-    return f"conv3x3_thin_in_kernel<{ci}, 2>"
-
-
-def thin_out(co):
-    return f"conv3x3_thin_out_kernel<{co}, 4>"
-
-
-CONV_VARIANTS = sorted([ring(ct) for ct in EXACT_CTS] + [generic(ct) for ct in EXACT_CTS]
-                       + [split(ct) for ct in SPLIT_CTS]
-                       + [thin_in(c) for c in (1, 2, 3, 4)] + [thin_out(c) for c in (1, 2, 3, 4)])
-assert len(CONV_VARIANTS) == len(set(CONV_VARIANTS)) == 24
-
-
-def expected_conv_variant(kind, ci, co, W, ct, x_bs, y_bs, r_bs, x_al, y_al, r_al, wp_al):
-    """(instantiation, vec) the entry point of `kind` ("exact", "split", "thin") launches, None = IRM_EINVAL.  *_bs:
-    batch strides in floats (0 without a residual), *_al: the pointer is 16-byte aligned (a null residual is).  vec is
-    ConvArgs.vec, the 16-byte store path of the generic kernel; the split and the thin kernels always store 16 bytes."""
-    all_vec = W % 4 == 0 and x_bs % 4 == 0 and y_bs % 4 == 0 and r_bs % 4 == 0 and x_al and y_al and r_al
-    if kind == "exact":                                             # irm_conv3x3_ep_f32 (conv3x3.hip)
-        if ct not in EXACT_CTS:
-            return None
-        vec = W % 4 == 0 and y_bs % 4 == 0 and r_bs % 4 == 0 and y_al and r_al      # a.vec
-        fast = vec and x_bs % 4 == 0 and x_al and wp_al                             # fast
-        return (ring(ct) if fast else generic(ct)), vec
-    if kind == "split":                                             # irm_conv3x3_f16x3_ep_f32: alignment, ct switch
-        if not (all_vec and wp_al) or ct not in SPLIT_CTS:
-            return None
-        return split(ct), True
-    if kind == "thin":                                              # irm_conv3x3_thin_f32: checks, Co / Ci dispatch
-        if not all_vec or (co > 4 and ci > 4):
-            return None
-        return (thin_out(co) if co <= 4 and ci > 4 else thin_in(ci)), True
-    raise ValueError(kind)
-
-
-def passes_per_group(mtiles, ct, ygroups):
-    """Output-channel passes each workgroup group runs: ygroups is clamped to [1, nchunks] (irm_conv_common,
-    conv_epilogue.h) and group y takes passes y, y + ygroups, ... (my_chunks in conv3x3_ring_kernel)."""
-    nchunks = -(-mtiles // ct)
-    yg = min(max(ygroups, 1), nchunks)
-    return [(nchunks - y + yg - 1) // yg for y in range(yg)]
-
-
-def pass_structure(passes):
-    """"single": no workgroup runs a second pass; else "even" or "uneven" pass counts over the groups."""
-    return "single" if max(passes) == 1 else "even" if min(passes) == max(passes) else "uneven"
-
-
-# --------------------------------------------------------------------------- cases
-def _case(kind, path, name, co, ci, H, W, *, B=2, ct=None, yg=None, bias=False, relu1=False, res_mode=0, relu2=False,
-          store_mode=0, shuffle=2, leaky=None, x_off=0, y_off=0, r_off=0):
-    """One launch.  path: "ring" / "scalar" / "vec" (exact), "split", "thin"; *_off: floats the buffer starts past a
-    16-byte boundary."""
-    return dict(kind=kind, path=path, name=name, co=co, ci=ci, H=H, W=W, B=B, ct=ct, yg=yg, bias=bias, relu1=relu1,
-                res_mode=res_mode, relu2=relu2, store_mode=store_mode, shuffle=shuffle, leaky=leaky, x_off=x_off,
-                y_off=y_off, r_off=r_off)
-
-
-def _exact_cases(ct, path):
-    """Cases A - D of one exact CT on one path: the ring (all aligned, W = 36), the generic kernel with scalar stores
-    (W = 35; once W = 36 with every buffer one float past alignment) or with 16-byte stores (W = 36, only x one float
-    past alignment).  The PixelUnshuffle case takes W = 40 instead of 36 (its output planes, 5 x 18 floats at W = 36,
-    would put the output slice off 16-byte alignment and the launch on the scalar path) and W = 38 on the scalar path."""
-    W = 35 if path == "scalar" else 36
-    off = dict(x_off=1) if path == "vec" else {}
-    kw = dict(ct=ct, **off)
-    cases = [
-        _case("exact", path, "A uneven-groups ragged-last-pass relu res1 relu2", 16 * (2 * ct + 1) - 1, 20, 9, W, yg=2,
-              bias=True, relu1=True, res_mode=1, relu2=True, **kw),
-        _case("exact", path, "B one-pass m%16=1 res2", 16 * (ct - 1) + 1, 5, 5, W, yg=1, res_mode=2, **kw),
-        _case("exact", path, "C three-passes one-stage shuffle2", 48 * ct, 3, 5, W, yg=1, store_mode=2, shuffle=2, **kw),
-        _case("exact", path, "C three-passes one-stage shuffle4", 48 * ct, 3, 5, W, yg=1, store_mode=2, shuffle=4, **kw),
-        _case("exact", path, "D two-passes ragged unshuffle", 16 * ct + 8, 12, 10, 38 if path == "scalar" else 40, yg=1,
-              store_mode=1, **kw),
-    ]
-    if path == "scalar":
-        cases.append(_case("exact", path, "A all-buffers-offset", 16 * (2 * ct + 1) - 1, 20, 9, 36, yg=2, bias=True,
-                           relu1=True, res_mode=1, relu2=True, ct=ct, x_off=1, y_off=1, r_off=1))
-    if ct == 3:
-        cases.append(_case("exact", path, "B ygroups-100-clamped", 16 * (ct - 1) + 1, 5, 5, W, yg=100, res_mode=2, **kw))
-    return cases
-
-
-def _exact_epilogue_cases(path):
-    """Once per path: the tanh + clamp residual (res_mode 3) and LeakyReLU."""
-    W = 35 if path == "scalar" else 36
-    off = dict(x_off=1) if path == "vec" else {}
-    return [
-        _case("exact", path, "E tanh-clamp two-groups", 40, 9, 9, W, ct=2, yg=2, bias=True, res_mode=3, **off),
-        _case("exact", path, "F leaky two-passes", 50, 9, 9, W, ct=3, yg=1, bias=True, leaky=0.1, **off),
-    ]
-
-
-def _split_cases(ct):
-    """A, C, D with CT = the output tiles per pass, W = 36 and aligned slices (the kernel accepts nothing else), and B
-    for the single-pass launch production issues most."""
-    return [
-        _case("split", "split", "A uneven-groups ragged-last-pass relu res1 relu2", 16 * (2 * ct + 1) - 1, 40, 9, 36,
-              ct=ct, yg=2, bias=True, relu1=True, res_mode=1, relu2=True),
-        _case("split", "split", "B one-pass m%16=1 res2", 16 * (ct - 1) + 1, 5, 5, 36, ct=ct, yg=1, res_mode=2),
-        _case("split", "split", "C three-passes one-stage shuffle2", 48 * ct, 3, 5, 36, ct=ct, yg=1, store_mode=2),
-        _case("split", "split", "C three-passes one-stage shuffle4", 48 * ct, 3, 5, 36, ct=ct, yg=1, store_mode=2,
-              shuffle=4),
-        _case("split", "split", "D two-passes ragged unshuffle", 16 * ct + 8, 70, 10, 40, ct=ct, yg=1, store_mode=1),
-    ]
-
-
-def _thin_cases():
-    cases = [
-        _case("thin", "thin", "ragged co group 13+13+13+11", 50, 3, 9, 12, B=1, bias=True, relu1=True),
-        _case("thin", "thin", "ragged co group 10+9 B3", 19, 2, 5, 8, B=3, res_mode=1, relu2=True),
-        _case("thin", "thin", "gray first layer odd H", 17, 1, 7, 8, bias=True, relu1=True),
-        _case("thin", "thin", "ci4 ragged co group 9+9+9+6", 33, 4, 9, 12, B=1, bias=True, res_mode=2),
-    ]
-    for co in (1, 2, 3, 4):     # H = 6: the second 4-row strip holds 2 rows; Ci = 9: the four waves sum 3, 2, 2, 2 channels
-        cases.append(_case("thin", "thin", f"co{co} partial strip", co, 9, 6, 12, bias=co % 2 == 1,
-                           res_mode=(0, 1, 2, 3)[co - 1], relu1=co == 2, relu2=co == 4))
-    return cases
-
-
-CASES = []
-for _ct in EXACT_CTS:
-    for _path in ("ring", "scalar", "vec"):
-        CASES += _exact_cases(_ct, _path)
-for _path in ("ring", "scalar", "vec"):
-    CASES += _exact_epilogue_cases(_path)
-for _ct in SPLIT_CTS:
-    CASES += _split_cases(_ct)
-CASES += _thin_cases()
-
-
-# --------------------------------------------------------------------------- layouts
-def out_shape(c):
-    """(channels, H, W) of the output tensor."""
-    co, H, W, r = c["co"], c["H"], c["W"], c["shuffle"]
-    if c["store_mode"] == 1:
-        return co * 4, H // 2, W // 2
-    if c["store_mode"] == 2:
-        return co // (r * r), H * r, W * r
-    return co, H, W
-
-
-def layout(c):
-    """Batch strides (floats) and 16-byte alignment of x, y, res of a case: x is channels [2, 2 + Ci) of a Ci + 3
-    channel buffer, y channels [1, 1 + C_out) of C_out + 2, res channels [1, 1 + Co) of Co + 3 (allocations are 16-byte
-    aligned; *_off floats are skipped in front)."""
-    N = c["H"] * c["W"]
-    oc, oh, ow = out_shape(c)
-    lay = dict(x_bs=(c["ci"] + 3) * N, x_al=(c["x_off"] + 2 * N) % 4 == 0,
-               y_bs=(oc + 2) * oh * ow, y_al=(c["y_off"] + oh * ow) % 4 == 0, r_bs=0, r_al=True)
-    if c["res_mode"]:
-        lay.update(r_bs=(c["co"] + 3) * N, r_al=(c["r_off"] + N) % 4 == 0)
-    return lay
-
-
-def case_plan(c):
-    """(ct, ygroups) the launch gets from ops.conv3x3 (the thin kernel has no plan)."""
-    if c["kind"] == "thin":
-        return None, None
-    return ops.plan_conv3x3(c["co"], c["H"], c["W"], c["B"], split=c["kind"] == "split", ct=c["ct"], ygroups=c["yg"])
-
-
-def case_variant(c):
-    ct, _ = case_plan(c)
-    return expected_conv_variant(c["kind"], c["ci"], c["co"], c["W"], ct, wp_al=True, **layout(c))
-
-
-def case_passes(c):
-    ct, yg = case_plan(c)
-    return passes_per_group((c["co"] + 15) // 16, ct, yg)
-
-
-def _variant_name(c):
-    v = case_variant(c)
-    if v is None:
-        return "rejected"
-    return v[0] + (" vec" if c["path"] == "vec" else " scalar" if c["path"] == "scalar" else "")
-
-
-CASE_IDS = [f"{_variant_name(c)} | {c['name']}".replace(" ", "_") for c in CASES]
-assert len(set(CASE_IDS)) == len(CASE_IDS)
-
-#: variant -> the pass structures ("single" / "even" / "uneven") its cases run; tests/test_planner_cpu.py and
-#: tests/test_gpu_launch_replay.py hold the planner's and production's launches against it
-CASE_STRUCTURES = {}
-for _c in CASES:
-    _v = case_variant(_c)
-    if _v is not None:
-        CASE_STRUCTURES.setdefault(_v[0], set()).add("single" if _c["kind"] == "thin" else pass_structure(case_passes(_c)))
 
 
 # --------------------------------------------------------------------------- CPU tests of the table and the cases
@@ -318,15 +113,6 @@ def test_expected_conv_variant_spot_checks():
 
 
 # --------------------------------------------------------------------------- buffers and references
-def _slice(dev, B, C, extra, ch, H, W, off, fill):
-    """A [B, C, H, W] channel slice at channel `ch` of a [B, C + extra, H, W] buffer that starts `off` floats into its
-    allocation.  Returns (flat allocation, view)."""
-    N = H * W
-    flat = torch.full((B * (C + extra) * N + 4,), fill, dtype=torch.float32, device=dev)
-    view = flat.as_strided((B, C, H, W), ((C + extra) * N, N, W, 1), off + ch * N)
-    return flat, view
-
-
 def inputs(c, idx):
     B, ci, co, H, W = c["B"], c["ci"], c["co"], c["H"], c["W"]
     g = f"cv{idx}_{co}_{ci}_{H}x{W}_{B}"
@@ -339,20 +125,7 @@ def inputs(c, idx):
 def reference(c, t, dt):
     """F.conv2d and the epilogue chain of the kernels (bias, relu1 / leaky, res_mode, relu2, store) in dtype dt."""
     y = TF.conv2d(t["x"].to(dt), t["w"].to(dt), t["bias"].to(dt) if c["bias"] else None, padding=1)
-    if c["relu1"]:
-        y = torch.relu(y)
-    if c["leaky"] is not None:
-        y = torch.where(y > 0, y, y * torch.tensor(c["leaky"], dtype=torch.float32).to(dt))
-    if c["res_mode"]:
-        r = t["r"].to(dt)
-        y = y + r if c["res_mode"] == 1 else r - y if c["res_mode"] == 2 else (torch.tanh(y) + r).clamp(-1, 1)
-    if c["relu2"]:
-        y = torch.relu(y)
-    if c["store_mode"] == 1:
-        y = TF.pixel_unshuffle(y, 2)
-    elif c["store_mode"] == 2:
-        y = TF.pixel_shuffle(y, c["shuffle"])
-    return y
+    return conv_epilogue(y, t["r"], c["relu1"], c["res_mode"], c["relu2"], c["store_mode"], c["shuffle"], c["leaky"])
 
 
 _REFS = {}      # case index -> (y64, e_32, max|y64|): computed once, shared, left unchanged

@@ -5,11 +5,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from block_model import FPN_TOL as TOL
 from irm_amd import _hip, deblurganv2, ops, synth, utils
 from oracle import deblurgan_ref, tiler_ref
 
 pytestmark = pytest.mark.gpu
-TOL = 2e-4
 
 
 def rnd(name, shape, lo=-1.0, hi=1.0):

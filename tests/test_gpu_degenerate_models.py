@@ -1,9 +1,9 @@
 """The precision ledger (tests/test_gpu_precision.py) on frames instead of noise: black, flat, letterboxed, checkered.
 
-Machinery and bar are the ledger's, by import: the cases, the model builds, the CPU oracles and the one pass function
+Machinery and bar are the ledger's (tests/ledger.py): the cases, the model builds, the CPU oracles and the one pass function
 e_gpu <= K * e_32 + F * max|y64|, where e_32 and y64 come from the CPU oracle ON THE SAME FRAME - the oracle's own fp32
 error moves by two orders of magnitude with the frame content, and the bar moves with it.  Restormer is held on both
-rows, `out` and the `refinement` tap.  The oracle runs are cached in the ledger's module cache under (case, frame); the
+rows, `out` and the `refinement` tap.  The oracle runs are cached in ledger.py's cache under (case, frame); the
 WithBias variants that share weights, oracle and size (fused, unfused, IRM_GEMM_EXACT=1) share one run.
 
 test_frame_table prints the table of DESIGN.md, section "Degenerate inputs"."""
@@ -12,7 +12,7 @@ import torch
 
 import degenerate as dg
 import half_model as hm
-import test_gpu_precision as ledger
+import ledger
 from irm_amd import dncnn
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +40,7 @@ def frame_of(case, kind):
 
 def oracle(case, p, kind, x):
     """{row: (y64, e_32)}: the ledger's oracle on a frame, finite in both precisions."""
-    ref = ledger._oracle(ORACLE_OF.get(case, case), p, frame=kind, x=x)
+    ref = ledger.oracle(ORACLE_OF.get(case, case), p, frame=kind, x=x)
     for row, (y64, e32) in ref.items():
         assert bool(torch.isfinite(y64).all()) and e32 == e32 and e32 != float("inf"), (case, kind, row)
     return ref
@@ -65,10 +65,10 @@ def test_ledger_on_frames(dev, monkeypatch, case, kind):
     when these frames were first run, each a defect since fixed: MaIRUNet on black / letterbox at 15.8 / 12.1 x e_32 (out_proj
     on the fp16-emulated GEMM; now on the exact kernel, 1.4 / 1.5) and FPN-MobileNet on checker at 9.5 (float32 sums in the
     InstanceNorm statistics; now float64, 1.9 - and black 3.6 -> 2.1)."""
-    model, p = ledger._build(case, dev, monkeypatch)
+    model, p = ledger.build(case, dev, monkeypatch)
     x = frame_of(case, kind)
     ref = oracle(case, p, kind, x)
-    got = ledger._run_gpu(case, dev, model, "refinement" in ref, x=x)
+    got = ledger.run_gpu(case, dev, model, "refinement" in ref, x=x)
     exact_zero = case == "restormer_bf_64x64_b1" and kind == "black"
     for row, (y64, e32) in ref.items():
         assert bool(torch.isfinite(got[row]).all()), row
@@ -87,13 +87,13 @@ def test_positive_control_letterbox(dev, monkeypatch):
     (no GPU involved) puts a rounded latent layer at 2 ... 3 x e_32, under the bar, while a layer of the first block,
     which every later layer amplifies, stands at 50 x e_32 (Degenerate inputs)."""
     case, kind = "restormer_wb_64x64_b1", "letterbox"
-    model, p = ledger._build(case, dev, monkeypatch)
+    model, p = ledger.build(case, dev, monkeypatch)
     x = frame_of(case, kind)
     ref = oracle(case, p, kind, x)
     w = model.encoder_level1[0].ffn.project_out.weight
     with torch.no_grad():
         w.copy_(w.half().float())
-    got = ledger._run_gpu(case, dev, model, True, x=x)
+    got = ledger.run_gpu(case, dev, model, True, x=x)
     for row, (y64, e32) in ref.items():
         e_gpu = float((got[row] - y64).abs().max())
         print(f"control {kind} {row}: e_gpu {e_gpu:.3e}  e_32 {e32:.3e}  ratio {e_gpu / e32:.1f}")

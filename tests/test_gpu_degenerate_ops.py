@@ -2,8 +2,9 @@
 
 Every other GPU test draws its activations from independent uniform noise, on which a normalising kernel cannot reach its
 special cases (no pixel with zero variance over the channels, no zero q / k row, no constant plane).  Here the inputs come
-from tests/degenerate.py; shapes, float64 references and tolerances are those of each kernel's own existing test (imported,
-not restated), the tolerance taken over the whole float64 output where it scales with max|ref|.
+from tests/degenerate.py; shapes and tolerances are those of each kernel's own existing test, the float64 references and the
+fixed bars the shared ones of tests/block_model.py and tests/scan_model.py, the tolerance taken over the whole float64 output
+where it scales with max|ref|.
 
 One tolerance needed mending.  test_gemm1x1_f16x3, test_gemm_presplit and test_ln_gemm_presplit_fused carry an ABSOLUTE
 clause (e < 2e-5) written for outputs of magnitude ~10.  A BiasFree LayerNorm does not remove the mean, so a C(a) or A(a)
@@ -29,14 +30,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import block_model as bm
 import degenerate as dg
-import test_gpu_deblurgan as t_fpn
-import test_gpu_fused as t_fused
-import test_gpu_mair as t_mair
-import test_gpu_ops as t_ops
+import scan_model
+from block_model import FPN_TOL, FUSED_TOL, OPS_TOL, qk_from_tm, qk_to_tm, unpack_mfold, unpack_presplit
+from block_model import run_mdta_fold as _fold
 from irm_amd import _hip, ops, synth
 from oracle import mair_ref
-from test_gpu_dw_gram import unpack_mfold
 
 pytestmark = pytest.mark.gpu
 
@@ -58,15 +58,7 @@ LISTED = {
 
 @pytest.fixture(scope="module", autouse=True)
 def _record_entry_points():
-    mp = pytest.MonkeyPatch()
-    real = _hip.call
-
-    def call(name, *args):
-        _REACHED.add(name)
-        return real(name, *args)
-    mp.setattr(_hip, "call", call)
-    yield
-    mp.undo()
+    yield from bm.record_calls(_REACHED)
 
 
 def rnd(name, shape, lo=-1.0, hi=1.0):
@@ -82,9 +74,9 @@ def image(kind, tag, B, K, H, W, tile, lo=-1.5, hi=2.0):
 
 
 def ln64(xd, lnw, lnb, ln, labels=None, clamp=None):
-    """The float64 LayerNorm of the existing tests (t_ops._ln_ref).  labels: the output at the Z / C(a) pixels REPLACED by
+    """The float64 LayerNorm of the existing tests (block_model.layer_norm).  labels: the output at the Z / C(a) pixels REPLACED by
     the bias (WithBias: what the LayerNorm of a pixel without deviations is); clamp: BiasFree output limited to +-clamp."""
-    y = t_ops._ln_ref(xd, lnw, lnb, ln)
+    y = bm.layer_norm(xd, lnw, lnb, ln)
     if labels is not None:
         assert ln == 1
         m = dg.flat_mask(labels)
@@ -112,8 +104,7 @@ def test_ln_stats(dev, kind):
     stats = torch.empty(B, 2, H * W, device=dev)
     ops.ln_stats(big.to(dev)[:, 2:2 + C], stats, 1e-5)
     xr = x.double()
-    mean = xr.mean(1).reshape(B, -1)
-    rstd = 1.0 / torch.sqrt(xr.var(1, unbiased=False) + 1e-5).reshape(B, -1)
+    mean, rstd = (s.reshape(B, -1) for s in bm.ln_stats(xr))
     s = stats.cpu().double()
     e_m, e_r = float((s[:, 0] - mean).abs().max()), float(((s[:, 1] - rstd).abs() / rstd).max())
     print(f"ln_stats {kind}: mean abs {e_m:.3e}  rstd rel {e_r:.3e}")
@@ -155,7 +146,7 @@ def test_gemm1x1_ln(dev, M, K, H, W, B, ln, res, bias, kind):
     ops.gemm1x1(_hip.pack_gemm_weight(w).to(dev), xg, ybig[:, 1:1 + M], M, K, res=r.to(dev) if res else None,
                 bias=bv.to(dev) if bias else None, stats=stats, lnw=lnw.to(dev), lnb=lnb.to(dev) if ln == 1 else None, ln_mode=ln)
     got = ybig.cpu().double()
-    tol = t_ops.TOL * max(1.0, float(ref.abs().max()))
+    tol = OPS_TOL * max(1.0, float(ref.abs().max()))
     err = float((got[:, 1:1 + M] - ref).abs().max())
     print(f"gemm1x1 {tag}: {err:.3e} (bar {tol:.3e})")
     assert err < tol
@@ -231,8 +222,7 @@ def test_gemm1x1_output_statistics(dev, kind):
     B, H, W = 2, 12, 20
     x, _ = image(kind, f"so{kind}", B, K, H, W, 64)
     ref = x.double()
-    mean = ref.mean(1).reshape(B, -1)
-    rstd = 1.0 / torch.sqrt(ref.var(1, unbiased=False) + 1e-5).reshape(B, -1)
+    mean, rstd = (s.reshape(B, -1) for s in bm.ln_stats(ref))
     y = torch.empty(B, M, H, W, device=dev)
     st = torch.full((B, 2, H * W), float("nan"), device=dev)
     assert ops.can_fuse_stats(M)
@@ -240,7 +230,7 @@ def test_gemm1x1_output_statistics(dev, kind):
     s_ = st.cpu().double()
     e_y, e_m, e_r = float((y.cpu().double() - ref).abs().max()), float((s_[:, 0] - mean).abs().max()), float(((s_[:, 1] - rstd).abs() / rstd).max())
     print(f"gemm1x1 stats_out {kind}: y {e_y:.3e}  mean {e_m:.3e}  rstd rel {e_r:.3e}")
-    assert e_y < t_ops.TOL * max(1.0, float(ref.abs().max()))
+    assert e_y < OPS_TOL * max(1.0, float(ref.abs().max()))
     assert e_m < 1e-5 * max(1.0, float(mean.abs().max())) and e_r < 1e-5
     st2 = torch.empty(B, 2, H * W, device=dev)
     ops.ln_stats(y, st2)
@@ -260,7 +250,7 @@ def test_fpn_convs_on_flat_planes(dev, kind):
     """The convolutions of FPN-MobileNet (stride-2 stem, stride-2 and stride-1 depth-wise, plain 1x1, dense 3x3 with bias) on the
     planes a black or checkered frame gives them, with the shapes, float64 references and TOL of test_stride2_convs, test_dwconv3x3,
     test_gemm1x1 and test_conv3x3; the stride-2 outputs of a checker are constant up to the border, exactly as in float64."""
-    TOL = t_fpn.TOL
+    TOL = FPN_TOL
     x = flat_frame(kind, 2, 3, 32, 48)
     w = rnd("s2w", (32, 3, 3, 3), -0.3, 0.3)
     ref = F.conv2d(x.double(), w.double(), None, 2, 1)
@@ -278,17 +268,17 @@ def test_fpn_convs_on_flat_planes(dev, kind):
     ref1 = F.conv2d(xd.double(), wd.double(), None, 1, 1, groups=96)
     y1 = torch.empty(2, 96, 32, 48, device=dev)
     ops.dwconv3x3(xd.to(dev), wd.reshape(96, 9).to(dev), y1)
-    assert float((y1.cpu().double() - ref1).abs().max()) < t_ops.TOL
+    assert float((y1.cpu().double() - ref1).abs().max()) < OPS_TOL
     wp = rnd("fpw", (40, 96), -0.3, 0.3)
     refp = torch.einsum("mk,bkhw->bmhw", wp.double(), xd.double())
     yp = torch.empty(2, 40, 32, 48, device=dev)
     ops.gemm1x1(_hip.pack_gemm_weight(wp).to(dev), xd.to(dev), yp, 40, 96)
-    assert float((yp.cpu().double() - refp).abs().max()) < t_ops.TOL * max(1.0, float(refp.abs().max()))
+    assert float((yp.cpu().double() - refp).abs().max()) < OPS_TOL * max(1.0, float(refp.abs().max()))
     wc, bc = rnd("fcw", (64, 96, 3, 3), -0.2, 0.2), rnd("fcb", (64,))
     refc = F.conv2d(xd.double(), wc.double(), bc.double(), padding=1)
     yc = torch.empty(2, 64, 32, 48, device=dev)
     ops.conv3x3(_hip.pack_conv3x3_weight(wc).to(dev), xd.to(dev), yc, 96, 64, bias=bc.to(dev))
-    assert float((yc.cpu().double() - refc).abs().max()) < t_ops.TOL * max(1.0, float(refc.abs().max()))
+    assert float((yc.cpu().double() - refc).abs().max()) < OPS_TOL * max(1.0, float(refc.abs().max()))
 
 
 # =========================================================================== LN split + pre-split GEMM
@@ -313,7 +303,7 @@ def test_ln_split(dev, K, H, W, B, ln, kind):
     xs = torch.full((B * K * N + 64,), float("nan"), device=dev)
     ops.ln_split(big.to(dev)[:, 2:2 + K], xs, lnw.to(dev), lnb.to(dev) if ln == 1 else None, ln, s_x)
     assert torch.isnan(xs[B * K * N:]).all()
-    got = t_ops._unpack_presplit(xs[:B * K * N].cpu(), B * N, K).view(B, N, K).permute(0, 2, 1).reshape(B, K, H, W) / s_x
+    got = unpack_presplit(xs[:B * K * N].cpu(), B * N, K).view(B, N, K).permute(0, 2, 1).reshape(B, K, H, W) / s_x
     ref = ln64(x.double(), lnw, lnb, ln)
     beyond = ref.abs() * s_x > SAT if ln == 2 else torch.zeros_like(ref, dtype=torch.bool)
     assert ln == 2 or not bool(beyond.any())
@@ -444,7 +434,7 @@ def test_ln_gemm_presplit_cl(dev, ln, kind):
     def href(labels):
         return F.conv2d(ln64(x.double(), lnw, lnb, ln, labels=labels), pin_w.double()[:, :, None, None], pin_b.double())
     ref = href(None)
-    tol = t_fused.TOL * max(1.0, float(ref.abs().max()))
+    tol = FUSED_TOL * max(1.0, float(ref.abs().max()))
     err = float((got - ref).abs().max())
     print(f"LN-fused cl {tag}: {err:.3e} (bar {tol:.3e})")
     assert err <= tol
@@ -492,7 +482,7 @@ def test_biasfree_clamp_is_pinned(dev, K, M, H, W, B):
         y16, y32, frag, s_w, _ = _presplit_pair(dev, w, x, lnw, None, 2, bv, *((6, 2, 42) if K == 192 else (8, 2, 81)))
         xs = torch.empty(B * K * N, device=dev)
         ops.ln_split(x.to(dev), xs, lnw.to(dev), None, 2, s_x)
-        got = t_ops._unpack_presplit(xs.cpu(), B * N, K).view(B, N, K).permute(0, 2, 1).reshape(B, K, H, W) / s_x
+        got = unpack_presplit(xs.cpu(), B * N, K).view(B, N, K).permute(0, 2, 1).reshape(B, K, H, W) / s_x
         e_ln, e16, e32 = float((got - lnr).abs().max()), float((y16 - ref).abs().max()), float((y32 - ref).abs().max())
         print(f"  a {a:g}: ln_split {e_ln:.3e} (|ref|max {float(lnr.abs().max()):.4g})  gemm f16x3 {e16:.3e}  f32 pair {e32:.3e}  "
               f"|ref|max {float(ref.abs().max()):.4g}")
@@ -512,27 +502,12 @@ def test_biasfree_clamp_is_pinned(dev, K, M, H, W, B):
 GATE_SAT = 16.0 * SAT      # the gated activations are split to fp16 behind a fixed 2^-4 and limited at +-65000 there (irm_gate_split2)
 
 
-def gdfn64(x1, xn, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b, gate_sat=None):
-    """t_fused.gdfn_ref from the LayerNorm output xn on (float64): the chain behind a LayerNorm whose output at the flat
-    pixels is forced to the bias, or (gate_sat) with the gate limited where the kernels limit it.  Returns (y, [B][H][W] mask of
-    the pixels with a gate value beyond the limit)."""
-    hid = pout_w.shape[1]
-    h = F.conv2d(xn, pin_w.double()[:, :, None, None], None if pin_b is None else pin_b.double())
-    h = F.conv2d(h, dw_w.double().view(2 * hid, 1, 3, 3), None if dw_b is None else dw_b.double(), padding=1, groups=2 * hid)
-    g = F.gelu(h[:, :hid]) * h[:, hid:]
-    beyond = torch.zeros(g.shape[0], g.shape[2], g.shape[3], dtype=torch.bool)
-    if gate_sat is not None:
-        beyond = (g.abs() > gate_sat).any(1)
-        g = g.clamp(-gate_sat, gate_sat)
-    return x1 + F.conv2d(g, pout_w.double()[:, :, None, None], None if pout_b is None else pout_b.double()), beyond
-
-
 def gdfn_reference(x1, o, ln):
-    """(t_fused.gdfn_ref as it stands, [B][H][W] mask of the pixels with a gate value beyond the kernels' limit).  WithBias: no
+    """(block_model.gdfn as it stands, [B][H][W] mask of the pixels with a gate value beyond the kernels' limit).  WithBias: no
     such pixel.  BiasFree: a C(a) pixel enters project_in as a / sqrt(eps) w = 316 a w, its gate gelu(h1) h2 reaches 1e6 and
     passes |gate| <= 16 x 65000 (test_gate_out_of_range_saturates_instead_of_nan; test_gdfn_gate_limit_is_pinned)."""
-    plain = t_fused.gdfn_ref(x1, o["lnw"], o["lnb"], ln, o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"], o["pout_w"], o["pout_b"])
-    _, beyond = gdfn64(x1.double(), ln64(x1.double(), o["lnw"], o["lnb"], ln), o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"],
+    plain = bm.gdfn(x1.double(), o["lnw"], o["lnb"], ln, o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"], o["pout_w"], o["pout_b"])
+    _, beyond = bm.gdfn_from_ln(x1.double(), ln64(x1.double(), o["lnw"], o["lnb"], ln), o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"],
                        o["pout_w"], o["pout_b"], gate_sat=GATE_SAT)
     assert ln == 2 or not bool(beyond.any())
     return plain, beyond
@@ -543,18 +518,8 @@ def held(got, ref, beyond):
     return float(torch.where(beyond[:, None], torch.zeros_like(ref), got - ref).abs().max())
 
 
-def qkv64(xn, w, b, dw_w, dw_b):
-    M = w.shape[0]
-    h = F.conv2d(xn, w.double()[:, :, None, None], None if b is None else b.double())
-    return F.conv2d(h, dw_w.double().view(M, 1, 3, 3), None if dw_b is None else dw_b.double(), padding=1, groups=M)
-
-
 def _gdfn_operands(tag, C, hid, ln):
-    ws = 0.3
-    return dict(lnw=rnd(tag + "lw", (C,), 0.5, 1.5), lnb=rnd(tag + "lb", (C,), -0.2, 0.2) if ln == 1 else None,
-                pin_w=rnd(tag + "pi", (2 * hid, C), -ws, ws), pout_w=rnd(tag + "po", (C, hid), -ws, ws),
-                dw_w=rnd(tag + "dw", (2 * hid, 9), -0.4, 0.4), pin_b=rnd(tag + "pib", (2 * hid,), -0.3, 0.3),
-                dw_b=rnd(tag + "dwb", (2 * hid,), -0.3, 0.3), pout_b=rnd(tag + "pob", (C,), -0.3, 0.3))
+    return dict(zip(("lnw", "lnb", "pin_w", "pin_b", "dw_w", "dw_b", "pout_w", "pout_b"), bm.gdfn_operands(rnd, tag, C, hid, ln)))
 
 
 # C, hid, H, W, B: test_gdfn_fused's (48, 127, 20, 36) = 3 x 2 tiles of 8 x 32, partial in both directions, and (96, 255, 24, 40)
@@ -576,14 +541,14 @@ def test_gdfn_fused(dev, C, hid, H, W, B, ln, kind):
     ops.gdfn_fused(pk, xb[:, 1:1 + C], yb[:, 2:2 + C], C, hid, ln_mode=ln, bias=o["pout_b"].to(dev))
     y = yb.cpu()
     got = y[:, 2:2 + C].double()
-    tol = t_fused.TOL * max(1.0, float(ref.abs().max()))
+    tol = FUSED_TOL * max(1.0, float(ref.abs().max()))
     err = held(got, ref, beyond)
     print(f"gdfn_fused {tag}: {err:.3e} (bar {tol:.3e}){f'  pixels beyond the gate limit, not held: {int(beyond.sum())} of {beyond.numel()}' if bool(beyond.any()) else ''}")
     assert err <= tol and bool(torch.isfinite(got).all())
     assert torch.all(y[:, :2] == 7.0) and torch.equal(xb.cpu(), big)
     if ln == 1:
         m = dg.flat_neighbourhood_mask(lab)
-        ref_b, _ = gdfn64(x.double(), ln64(x.double(), o["lnw"], o["lnb"], 1, labels=lab), o["pin_w"], o["pin_b"], o["dw_w"],
+        ref_b, _ = bm.gdfn_from_ln(x.double(), ln64(x.double(), o["lnw"], o["lnb"], 1, labels=lab), o["pin_w"], o["pin_b"], o["dw_w"],
                           o["dw_b"], o["pout_w"], o["pout_b"])
         assert bool(m.any()) and float((got - ref_b)[:, :, m].abs().max()) <= tol
 
@@ -611,14 +576,14 @@ def test_attn_gdfn_fused(dev, C, hid, H, W, B, ln, kind):
     ops.attn_gdfn_fused(pk, xb[:, 1:1 + C], vb[:, 2 * C:], frag, yb[:, 2:2 + C], C, hid, ln_mode=ln, bias=o["pout_b"].to(dev))
     y = yb.cpu()
     got = y[:, 2:2 + C].double()
-    tol = t_fused.TOL * max(1.0, float(ref.abs().max()))
+    tol = FUSED_TOL * max(1.0, float(ref.abs().max()))
     err = held(got, ref, beyond)
     print(f"attn_gdfn_fused {tag}: {err:.3e} (bar {tol:.3e}){f'  pixels beyond the gate limit, not held: {int(beyond.sum())} of {beyond.numel()}' if bool(beyond.any()) else ''}")
     assert err <= tol and bool(torch.isfinite(got).all())
     assert torch.all(y[:, :2] == 7.0) and torch.equal(xb.cpu(), big) and torch.equal(vb.cpu(), vbig)
     if ln == 1:
         m = dg.flat_neighbourhood_mask(lab)
-        ref_b, _ = gdfn64(x1, ln64(x1, o["lnw"], o["lnb"], 1, labels=lab), o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"], o["pout_w"],
+        ref_b, _ = bm.gdfn_from_ln(x1, ln64(x1, o["lnw"], o["lnb"], 1, labels=lab), o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"], o["pout_w"],
                           o["pout_b"])
         assert float((got - ref_b)[:, :, m].abs().max()) <= tol
 
@@ -628,7 +593,7 @@ def test_attn_gdfn_fused(dev, C, hid, H, W, B, ln, kind):
 def test_gdfn_gate_limit_is_pinned(dev, C, hid, H, W, B, attn):
     """Where the gate limit of the fused GDFN kernels starts for a BiasFree C(a) pixel: one row of tiles
     of C(a) inside a noise image, a the largest power of two for which no gate value of the float64 chain passes 16 x 65000, and
-    the next one.  Below: the ordinary bar against the plain float64 t_fused.gdfn_ref at every pixel.  Above: finite, and the
+    the next one.  Below: the ordinary bar against the plain float64 block_model.gdfn at every pixel.  Above: finite, and the
     ordinary bar against the float64 chain whose gate is limited at the same value.  The threshold comes from the float64 chain
     and the constants of irm_gate_split2, not from a run of the kernel."""
     tag = f"gate{C}{int(attn)}"
@@ -642,7 +607,7 @@ def test_gdfn_gate_limit_is_pinned(dev, C, hid, H, W, B, attn):
         x = noise.clone()
         x[:, :, 8:16] = a
         x1 = x.double() + torch.einsum("bij,bjhw->bihw", mf.double(), vbig[:, 2 * C:].double()) if attn else x.double()
-        y, beyond = gdfn64(x1, ln64(x1, o["lnw"], None, 2), o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"], o["pout_w"], o["pout_b"],
+        y, beyond = bm.gdfn_from_ln(x1, ln64(x1, o["lnw"], None, 2), o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"], o["pout_w"], o["pout_b"],
                            gate_sat=sat)
         return x, x1, y, beyond
     below = max(a for a in (2.0 ** k for k in range(-8, 4)) if not bool(chain(a, GATE_SAT)[3].any()))
@@ -656,7 +621,7 @@ def test_gdfn_gate_limit_is_pinned(dev, C, hid, H, W, B, attn):
     for a, limited in ((below, False), (above, True)):
         x, x1, ref, beyond = chain(a, GATE_SAT if limited else None)
         if not limited:
-            plain = t_fused.gdfn_ref(x1, o["lnw"], None, 2, o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"], o["pout_w"], o["pout_b"])
+            plain = bm.gdfn(x1, o["lnw"], None, 2, o["pin_w"], o["pin_b"], o["dw_w"], o["dw_b"], o["pout_w"], o["pout_b"])
             assert float((ref - plain).abs().max()) <= 1e-12 * float(plain.abs().max())
             ref = plain
         y = torch.empty(B, C, H, W, device=dev)
@@ -665,7 +630,7 @@ def test_gdfn_gate_limit_is_pinned(dev, C, hid, H, W, B, attn):
         else:
             ops.gdfn_fused(pk, x.to(dev), y, C, hid, ln_mode=2, bias=o["pout_b"].to(dev))
         got = y.cpu().double()
-        tol = t_fused.TOL * max(1.0, float(ref.abs().max()))
+        tol = FUSED_TOL * max(1.0, float(ref.abs().max()))
         err = float((got - ref).abs().max())
         print(f"gate limit {tag}: a {a:g} ({'limited' if limited else 'plain'} reference, {int(beyond.sum())} pixels beyond): {err:.3e} (bar {tol:.3e})")
         assert bool(torch.isfinite(got).all()) and err <= tol and bool(beyond.any()) == limited
@@ -687,54 +652,21 @@ def test_qkv_dw_fused(dev, C, H, W, B, ln, kind):
     o = _qkv_operands(tag, C, ln)
     x, lab = image(kind, tag, B, C, H, W, (8, 32))
     big = in_slice(x, 3, 1, tag)
-    ref = t_fused.qkv_ref(x, o["lnw"], o["lnb"], ln, o["w"], o["wb"], o["dw_w"], o["dw_b"])
+    ref = bm.qkv(x.double(), o["lnw"], o["lnb"], ln, o["w"], o["wb"], o["dw_w"], o["dw_b"])
     pk = _hip.pack_qkv_fused(o["w"].to(dev), o["wb"], o["dw_w"], o["dw_b"], o["lnw"], o["lnb"])
     yb = torch.full((B, M + 2, H, W), 7.0, device=dev)
     ops.qkv_dw_fused(pk, big.to(dev)[:, 1:1 + C], yb[:, 1:1 + M], C, M, ln_mode=ln)
     y = yb.cpu()
     got = y[:, 1:1 + M].double()
-    tol = t_fused.TOL * max(1.0, float(ref.abs().max()))
+    tol = FUSED_TOL * max(1.0, float(ref.abs().max()))
     err = float((got - ref).abs().max())
     print(f"qkv_dw_fused {tag}: {err:.3e} (bar {tol:.3e})")
     assert err <= tol
     assert torch.all(y[:, 0] == 7.0) and torch.all(y[:, M + 1] == 7.0)
     if ln == 1:
         m = dg.flat_neighbourhood_mask(lab)
-        ref_b = qkv64(ln64(x.double(), o["lnw"], o["lnb"], 1, labels=lab), o["w"], o["wb"], o["dw_w"], o["dw_b"])
+        ref_b = bm.qkv_from_ln(ln64(x.double(), o["lnw"], o["lnb"], 1, labels=lab), o["w"], o["wb"], o["dw_w"], o["dw_b"])
         assert bool(m.any()) and float((got - ref_b)[:, :, m].abs().max()) <= tol
-
-
-def qk_from_tm(t):
-    """q, k tile-major [tile][channels][8 x 32] inside a planar container -> planar (test_qk_tile_major_chain)."""
-    B, C2, H, W = t.shape
-    return t.reshape(B, H // 8, W // 32, C2, 8, 32).permute(0, 3, 1, 4, 2, 5).reshape(B, C2, H, W)
-
-
-def qk_to_tm(t):
-    B, C2, H, W = t.shape
-    return t.reshape(B, C2, H // 8, 8, W // 32, 32).permute(0, 2, 4, 1, 3, 5).reshape(B, C2, H, W).contiguous()
-
-
-def attn64(q, k, temp, heads):
-    """float64 attention matrix [B][heads][c][c] of planar q, k [B][C][H][W] (test_mdta_fold)."""
-    B, C = q.shape[:2]
-    q, k = q.double().reshape(B, heads, C // heads, -1), k.double().reshape(B, heads, C // heads, -1)
-    return torch.softmax(F.normalize(q, dim=-1) @ F.normalize(k, dim=-1).transpose(-1, -2) * temp.double().view(1, heads, 1, 1), -1)
-
-
-def _fold(dev, qkv, temp, wout, C, heads, **kw):
-    """(attention, packed folded matrix) of ops.mdta_fold on a device qkv."""
-    B, _, H, W = qkv.shape
-    ready = kw.get("nchunk_ready")
-    _, nchunk, rec = ops.mdta_plan(B, C, heads, H * W)
-    part = kw.pop("part", None)
-    if part is None:
-        part = torch.full((B * heads * (ready or nchunk) * rec,), float("nan"), device=dev)
-    gsum = torch.empty(B * heads * rec, device=dev)
-    mfold = torch.zeros(B * ops.mfold_numel(C), device=dev)
-    attn = torch.empty(B, heads, C // heads, C // heads, device=dev)
-    ops.mdta_fold(qkv, part, gsum, temp.to(dev), wout.to(dev), mfold, C, heads, attn=attn, **kw)
-    return attn.cpu(), mfold.cpu(), gsum.cpu()
 
 
 @pytest.mark.parametrize("kind", IMAGES)
@@ -749,7 +681,7 @@ def test_qkv_tile_major_chain(dev, C, heads, ln, kind):
     tag = f"tm{C}_{ln}{kind}"
     o = _qkv_operands(tag, C, ln, bias=False)
     x, lab = image(kind, tag, B, C, H, W, (8, 32))
-    ref = t_fused.qkv_ref(x, o["lnw"], o["lnb"], ln, o["w"], None, o["dw_w"], None)
+    ref = bm.qkv(x.double(), o["lnw"], o["lnb"], ln, o["w"], None, o["dw_w"], None)
     pk = _hip.pack_qkv_fused(o["w"].to(dev), None, o["dw_w"], None, o["lnw"], o["lnb"])
     gs = _hip.gram_scales(o["w"].view(M, C, 1, 1), None, o["dw_w"].view(M, 1, 3, 3), None, o["lnw"], o["lnb"], ln == 1)
     assert (gs is not None) == (ln == 1)
@@ -766,16 +698,16 @@ def test_qkv_tile_major_chain(dev, C, heads, ln, kind):
     assert torch.equal(q0[:, 2 * C:], q1[:, 2 * C:])
     back = qk_from_tm(q1[:, :2 * C])
     assert torch.equal(back, q0[:, :2 * C])
-    tol = t_fused.TOL * max(1.0, float(ref.abs().max()))
+    tol = FUSED_TOL * max(1.0, float(ref.abs().max()))
     err = float((torch.cat([back, q1[:, 2 * C:]], 1).double() - ref).abs().max())
-    aref = attn64(ref[:, :C], ref[:, C:2 * C], temp, heads)
+    aref = bm.attention(ref[:, :C], ref[:, C:2 * C], temp, heads)
     ea = float((a1.double() - aref).abs().max())
     print(f"qkv tm chain {tag}: qkv {err:.3e} (bar {tol:.3e})  attn vs float64 {ea:.3e}  tm vs planar {float((a0 - a1).abs().max()):.3e}")
     assert err <= tol and ea < 2e-5
     assert float((a0 - a1).abs().max()) <= 2e-6 and float((m0 - m1).abs().max()) <= 2e-6
     if ln == 1:
         m = dg.flat_neighbourhood_mask(lab)
-        ref_b = qkv64(ln64(x.double(), o["lnw"], o["lnb"], 1, labels=lab), o["w"], None, o["dw_w"], None)
+        ref_b = bm.qkv_from_ln(ln64(x.double(), o["lnw"], o["lnb"], 1, labels=lab), o["w"], None, o["dw_w"], None)
         assert float((q0.double() - ref_b)[:, :, m].abs().max()) <= tol
 
 
@@ -803,8 +735,8 @@ def test_qkv_gram_cm(dev, kind):
     assert torch.all(q1[:, :2 * C] == 7.0)
     a1, m1, _ = _fold(dev, q1, temp, wout, C, heads, gram_scale=gs, tm=True, nchunk_ready=nchunk, part=part)
     assert torch.equal(q0[:, 2 * C:], q1[:, 2 * C:])
-    ref = t_fused.qkv_ref(x, o["lnw"], o["lnb"], 1, o["w"], None, o["dw_w"], None)
-    ea = float((a1.double() - attn64(ref[:, :C], ref[:, C:2 * C], temp, heads)).abs().max())
+    ref = bm.qkv(x.double(), o["lnw"], o["lnb"], 1, o["w"], None, o["dw_w"], None)
+    ea = float((a1.double() - bm.attention(ref[:, :C], ref[:, C:2 * C], temp, heads)).abs().max())
     da, dm = float((a0 - a1).abs().max()), float((m0 - m1).abs().max())
     print(f"qkv_gram_cm {tag}: attn vs float64 {ea:.3e}  vs chain: attn {da:.3e} mfold {dm:.3e}")
     assert da <= 2e-6 and dm <= 2e-6 and ea < 2e-5
@@ -862,7 +794,7 @@ def test_mdta_fold(dev, B, C, heads, H, W, case):
     qkv = rnd(tag, (B, 3 * C, H, W))
     mdta_degenerate(case, qkv[:, :C], qkv[:, C:2 * C], heads)
     temp, wout = rnd(tag + "t", (heads,), 2.0, 6.0), rnd(tag + "w", (C, C), -0.3, 0.3)
-    aref = attn64(qkv[:, :C], qkv[:, C:2 * C], temp, heads)
+    aref = bm.attention(qkv[:, :C].double(), qkv[:, C:2 * C].double(), temp, heads)
     v = qkv[:, 2 * C:].double().reshape(B, heads, c, N)
     ref = torch.einsum("oc,bcn->bon", wout.double(), (aref @ v).reshape(B, C, N)).reshape(B, C, H, W)
     qg = qkv.to(dev)
@@ -872,11 +804,11 @@ def test_mdta_fold(dev, B, C, heads, H, W, case):
     ops.gemm1x1(mfold.to(dev), qg[:, 2 * C:], y, C, C, w_bs=ops.mfold_numel(C))
     e_y = float((y.cpu().double() - ref).abs().max())
     print(f"mdta {tag}: attn {err:.3e}  folded + applied {e_y:.3e}")
-    assert e_y < t_ops.TOL
+    assert e_y < OPS_TOL
     a2, mf2, _ = _fold(dev, qg, temp, wout, C, heads, split=True)
     y2 = torch.empty(B, C, H, W, device=dev)
     ops.gemm1x1(mf2.to(dev), qg[:, 2 * C:], y2, C, C, w_bs=ops.mfold_numel(C), split=True)
-    assert torch.equal(a2, a) and float((y2.cpu().double() - ref).abs().max()) < t_ops.TOL and float((y2 - y).abs().max()) < 2e-5
+    assert torch.equal(a2, a) and float((y2.cpu().double() - ref).abs().max()) < OPS_TOL and float((y2 - y).abs().max()) < 2e-5
     part = torch.full((B * heads * ops.mdta_plan(B, C, heads, N)[1] * (c * c + 2 * c),), float("nan"), device=dev)
     gsum = torch.empty(B * heads * (c * c + 2 * c), device=dev)
     mfrag = torch.zeros(B * ops.mfold_frag_numel(C), device=dev)
@@ -906,7 +838,7 @@ def test_mdta_gram_f16x3(dev, tm, case):
     temp, wout = rnd(tag + "t", (heads,), 2.0, 6.0), rnd(tag + "w", (C, C), -0.3, 0.3)
     q, k = qkv[:, :C].double().reshape(B, heads, c, N), qkv[:, C:2 * C].double().reshape(B, heads, c, N)
     gref = torch.cat([(q @ k.transpose(-1, -2)).reshape(B, heads, c * c), (q * q).sum(-1), (k * k).sum(-1)], -1)
-    aref = attn64(qkv[:, :C], qkv[:, C:2 * C], temp, heads)
+    aref = bm.attention(qkv[:, :C].double(), qkv[:, C:2 * C].double(), temp, heads)
     dev_qkv = qkv.clone()
     if tm:
         dev_qkv[:, :2 * C] = qk_to_tm(qkv[:, :2 * C])
@@ -934,7 +866,7 @@ def _dw_gram_operands(case):
     gs = torch.pow(2.0, torch.floor(torch.log2(2.0 ** 14.8 / bound))).float()
     temp, wout = rnd(tag + "t", (heads,), 2.0, 6.0), rnd(tag + "wo", (C, C), -0.3, 0.3)
     qk = F.conv2d(raw.double()[:, :2 * C], dw_w.double()[:2 * C].view(2 * C, 1, 3, 3), None, padding=1, groups=2 * C)
-    attn = attn64(qk[:, :C], qk[:, C:], temp, heads)
+    attn = bm.attention(qk[:, :C], qk[:, C:], temp, heads)
     mfold = torch.stack([wout.double() @ torch.block_diag(*attn[i]) for i in range(B)])
     return C, heads, H, W, B, raw, dw_w, gs, temp, wout, attn, mfold
 
@@ -1011,7 +943,7 @@ def test_chan_norm(dev, affine, res, kind):
                       res=r.to(dev) if res else None)
     err = float((xg.cpu().double() - ref).abs().max())
     print(f"chan_norm {kind} affine{int(affine)} res{int(res)}: {err:.3e}")
-    assert err < t_fpn.TOL
+    assert err < FPN_TOL
 
 
 @pytest.mark.parametrize("kind", PLANES)
@@ -1046,8 +978,8 @@ SCAN_CASES = ("u_zero", "proj_zero", "constant", "dt_pm30")
 
 
 def scan_degenerate(case, tag, B, D, N, R, L):
-    """The synthetic regime of t_mair.scan_inputs with one degenerate edit."""
-    x, proj, dtw, dtb, A, Ds = t_mair.scan_inputs(tag, "synthetic", B, D, N, R, L)
+    """The synthetic regime of scan_model.scan_inputs with one degenerate edit."""
+    x, proj, dtw, dtb, A, Ds = scan_model.scan_inputs(tag, "synthetic", B, D, N, R, L)
     if case == "u_zero":
         x = torch.zeros_like(x)
     elif case == "proj_zero":
@@ -1072,7 +1004,7 @@ def test_selective_scan(dev, B, D, N, R, H, W, chunk, case):
     ids, inv = mair_ref.scan_ids(H, W, 4)
     tag = f"dz{D}{N}{case}"
     x, proj, dtw, dtb, A, Ds = scan_degenerate(case, tag, B, D, N, R, L)
-    yT, ysum, nchunk = t_mair.run_scan(dev, x, proj, dtw, dtb, A, Ds, ids, B, L, D, N, R, chunk)
+    yT, ysum, nchunk = scan_model.run_scan(dev, x, proj, dtw, dtb, A, Ds, ids, B, L, D, N, R, chunk)
     got = yT.cpu().permute(0, 1, 3, 2)                      # (B, 4, D, L) pixel order
     assert torch.isfinite(got).all()
     sums = ysum.cpu().sum(3).reshape(B, 4, -1)[:, :, :D]
@@ -1082,7 +1014,7 @@ def test_selective_scan(dev, B, D, N, R, H, W, chunk, case):
         want = Ds.view(1, 4, D, 1) * x.view(B, 1, D, L)
         assert torch.equal(got, want), "a zero projection must give y = D u exactly"
     if case != "u_zero":                                     # (0 = 0 there: the bar's e_32 is 0 too)
-        t_mair.check_scan_f64(f"{case} D{D} N{N} L{L} chunk{chunk}", x, proj, dtw, dtb.reshape(4, D), A, Ds, ids, inv, got,
+        scan_model.check_scan_f64(f"{case} D{D} N{N} L{L} chunk{chunk}", x, proj, dtw, dtb.reshape(4, D), A, Ds, ids, inv, got,
                               ysum.cpu(), B, L, D, N, R, chunk)
 
 

@@ -13,6 +13,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import block_model as bm
+from block_model import unpack_mfold
+from guards import SLACK, Guards, clean, guarded_fold, has_nan
 from irm_amd import _hip, ops, restormer, synth
 from oracle import restormer_ref
 
@@ -26,12 +29,6 @@ SENTINEL = 7.0
 
 def rnd(name, shape, lo=-1.0, hi=1.0):
     return synth.uniform(321, name, shape, lo, hi)
-
-
-def unpack_mfold(mf, nb, C):
-    """packed [mtile][kstep][lane] (lane = 16 g + r holds M[16 mtile + r][4 kstep + g]) -> [nb][C][C]"""
-    mt = C // 16
-    return mf.view(nb, mt, 4 * mt, 4, 16).permute(0, 1, 4, 2, 3).reshape(nb, C, C)
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,8 +47,7 @@ def inputs(C, heads, H, W, bias):
     raw = F.conv2d(xn, w.double()[:, :, None, None]).float()
     qk = F.conv2d(raw.double()[:, :2 * C], dw_w.double()[:2 * C].view(2 * C, 1, 3, 3), None if dw_b is None else dw_b.double()[:2 * C],
                   padding=1, groups=2 * C)
-    q, k = qk.reshape(B, 2, heads, C // heads, H * W).unbind(1)
-    attn = torch.softmax(F.normalize(q, dim=-1) @ F.normalize(k, dim=-1).transpose(-1, -2) * temp.double().view(1, heads, 1, 1), -1)
+    attn = bm.attention_qk(qk, temp, heads)
     mfold = torch.stack([wout.double() @ torch.block_diag(*attn[i]) for i in range(B)])
     return dict(raw=raw, dw_w=dw_w, dw_b=dw_b, gs=gs, temp=temp, wout=wout, attn=attn, mfold=mfold)
 
@@ -187,8 +183,6 @@ def test_dw_gram_guard_bands(dev):
     borders), B = 2 with batch slack.  qkv holds the q, k planes ONLY, between NaN bands: a halo read one pixel before a
     plane's row, past its end or past the k planes poisons a record.  part at exactly B heads nchunk 2400 floats between
     sentinels.  The attention matrix of the records against float64 (bar of test_mdta_fold, 2e-5)."""
-    from guards import has_nan
-    from test_gpu_guard_bands import SLACK, Guards, _attn_ref, _fold, clean
     nb, C, heads, H, W = 2, 192, 4, 32, 32
     assert ops.can_dw_gram(C, heads, H, W)
     raw, dw_w, dw_b = rnd("dgq", (nb, 2 * C, H, W), -1.0, 1.0), rnd("dgw", (2 * C, 9), -0.4, 0.4), rnd("dgb", (2 * C,), -0.3, 0.3)
@@ -202,6 +196,6 @@ def test_dw_gram_guard_bands(dev):
     assert ops.dw_gram(qkv, g.inp(dw_w), gsc, part, C, heads, bias=g.inp(dw_b)) == nchunk
     g.check()
     assert not has_nan(part.cpu())
-    attn, _ = _fold(g, dev, qkv, nb, C, heads, H * W, g.inp(temp), g.inp(wout), part=part, nready=nchunk, gram_scale=gsc)
+    attn, _ = guarded_fold(g, qkv, nb, C, heads, H * W, g.inp(temp), g.inp(wout), part=part, nready=nchunk, gram_scale=gsc)
     g.check()
-    assert float((clean(attn).double() - _attn_ref(ref, heads, temp)).abs().max()) < 2e-5
+    assert float((clean(attn).double() - bm.attention_qk(ref, temp, heads)).abs().max()) < 2e-5

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from frame_checks import merge_float64, packed_blocks
 from irm_amd import _hip, dncnn, ensemble, mair, ops, restormer, synth, utils
 
 pytestmark = pytest.mark.gpu
@@ -35,15 +36,6 @@ def plus_golden(plus_meta):
                 name, r = key.split("@")
                 bands.setdefault(name, []).append((int(r), z[key]))
     return {name: np.concatenate([a for _, a in sorted(b, key=lambda t: t[0])], axis=-2) for name, b in bands.items()}
-
-
-def packed_blocks(buf, geo, B, C, s=1):
-    """packed buffer -> blocks[variant][partition] = [B, C, s ph, s pw] views, grid order."""
-    out = [[] for _ in range(8)]
-    for row in geo.table[8:]:
-        e, _, _, ph, pw, off = (int(v) for v in row[:6])
-        out[e].append(buf[off * C * s * s:(off + B * ph * pw) * C * s * s].view(B, C, s * ph, s * pw))
-    return out
 
 
 class Identity(torch.nn.Module):
@@ -105,30 +97,6 @@ def test_kernels_reject_bad_arguments(dev):
 
 
 # --------------------------------------------------------------------------- 2. merge kernel vs float64
-def merge_float64(blocks, H, W, s, chop):
-    """numpy float64 restatement of one_img_test's stitch (:65-77, x s), the crop (:103) and gather (:107-117)."""
-    total = 0.0
-    for v in range(8):
-        p = ensemble.plan(H, W, v, chop)
-        (ha, wa), (nh, nw) = p.size, p.grid
-        B, Co = blocks[v][0].shape[:2]
-        img = np.zeros((B, Co, s * (ha + p.pad[0]), s * (wa + p.pad[1])))
-        for i in range(nh):
-            for j in range(nw):
-                top, left = (0 if i == 0 else p.shave[0] * s), (0 if j == 0 else p.shave[1] * s)
-                img[:, :, i * p.split[0] * s:(i + 1) * p.split[0] * s, j * p.split[1] * s:(j + 1) * p.split[1] * s] = \
-                    blocks[v][i * nw + j][:, :, top:top + p.split[0] * s, left:left + p.split[1] * s]
-        img = img[:, :, :s * ha, :s * wa]
-        if v >= 4:
-            img = img.transpose(0, 1, 3, 2)
-        if v & 2:
-            img = img[:, :, :, ::-1]
-        if v & 1:
-            img = img[:, :, ::-1, :]
-        total = total + img
-    return total / 8.0
-
-
 @pytest.mark.parametrize("B,Co,H,W,s,chop", [(2, 3, 230, 410, 1, True), (1, 3, 230, 410, 2, True), (2, 2, 64, 210, 3, True),
                                              (1, 3, 64, 210, 4, True), (1, 1, 401, 33, 2, True), (2, 3, 37, 53, 3, False),
                                              (1, 3, 203, 467, 1, True)])

@@ -7,31 +7,16 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import block_model as bm
+from block_model import FUSED_TOL as TOL
+from block_model import from_tm, to_tm
 from irm_amd import _hip, ops, synth
 
 pytestmark = pytest.mark.gpu
-TOL = 2e-5
 
 
 def rnd(name, shape, lo=-1.0, hi=1.0):
     return synth.uniform(321, name, shape, lo, hi)
-
-
-def gdfn_ref(x, lnw, lnb, ln_mode, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b, eps=1e-5):
-    """float64: x + project_out(gelu(dw(h)[:hid]) * dw(h)[hid:]), h = project_in(LN(x))."""
-    xd = x.double()
-    mu = xd.mean(1, keepdim=True)
-    var = xd.var(1, unbiased=False, keepdim=True)
-    if ln_mode == _hip.LN_WITHBIAS:
-        xn = (xd - mu) / torch.sqrt(var + eps) * lnw.double()[None, :, None, None] + lnb.double()[None, :, None, None]
-    else:
-        xn = xd / torch.sqrt(var + eps) * lnw.double()[None, :, None, None]
-    hid = pout_w.shape[1]
-    h = F.conv2d(xn, pin_w.double()[:, :, None, None], None if pin_b is None else pin_b.double())
-    h = F.conv2d(h, dw_w.double().view(2 * hid, 1, 3, 3), None if dw_b is None else dw_b.double(), padding=1,
-                 groups=2 * hid)
-    g = F.gelu(h[:, :hid]) * h[:, hid:]
-    return xd + F.conv2d(g, pout_w.double()[:, :, None, None], None if pout_b is None else pout_b.double())
 
 
 GDFN_CASES = [
@@ -52,16 +37,9 @@ GDFN_CASES = [
 def test_gdfn_fused(dev, C, hid, H, W, B, ln, bias, ws):
     tag = f"f{C}_{hid}_{H}_{W}_{B}_{ln}"
     big = rnd(tag + "x", (B, C + 3, H, W), -1.5, 2.0)
-    lnw = rnd(tag + "lw", (C,), 0.5, 1.5)
-    lnb = rnd(tag + "lb", (C,), -0.2, 0.2) if ln == 1 else None
-    pin_w = rnd(tag + "pi", (2 * hid, C), -ws, ws)
-    pout_w = rnd(tag + "po", (C, hid), -ws, ws)
-    dw_w = rnd(tag + "dw", (2 * hid, 9), -0.4, 0.4)
-    pin_b = rnd(tag + "pib", (2 * hid,), -0.3, 0.3) if bias else None
-    dw_b = rnd(tag + "dwb", (2 * hid,), -0.3, 0.3) if bias else None
-    pout_b = rnd(tag + "pob", (C,), -0.3, 0.3) if bias else None
+    lnw, lnb, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b = bm.gdfn_operands(rnd, tag, C, hid, ln, bias, ws)
     x = big[:, 1:1 + C]
-    ref = gdfn_ref(x, lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
+    ref = bm.gdfn(x.double(), lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
     pk = _hip.pack_gdfn_fused(pin_w.to(dev), pin_b, dw_w, dw_b, pout_w, lnw, lnb)
     xb = big.to(dev)
     yb = torch.full((B, C + 2, H, W), 7.0, device=dev)
@@ -96,20 +74,13 @@ def test_attn_gdfn_fused(dev, C, hid, H, W, B, ln, bias):
     big = rnd(tag + "x", (B, C + 3, H, W), -1.5, 2.0)
     vbig = rnd(tag + "v", (B, 3 * C, H, W), -2.0, 2.0)          # v = the last C channels of a qkv buffer
     mf = rnd(tag + "m", (B, C, C), -0.2, 0.2)                     # per-image folded matrix
-    lnw = rnd(tag + "lw", (C,), 0.5, 1.5)
-    lnb = rnd(tag + "lb", (C,), -0.2, 0.2) if ln == 1 else None
-    pin_w = rnd(tag + "pi", (2 * hid, C), -ws, ws)
-    pout_w = rnd(tag + "po", (C, hid), -ws, ws)
-    dw_w = rnd(tag + "dw", (2 * hid, 9), -0.4, 0.4)
-    pin_b = rnd(tag + "pib", (2 * hid,), -0.3, 0.3) if bias else None
-    dw_b = rnd(tag + "dwb", (2 * hid,), -0.3, 0.3) if bias else None
-    pout_b = rnd(tag + "pob", (C,), -0.3, 0.3) if bias else None
+    lnw, lnb, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b = bm.gdfn_operands(rnd, tag, C, hid, ln, bias, ws)
     bo = rnd(tag + "bo", (C,), -0.3, 0.3) if bias else None
     x, v = big[:, 1:1 + C], vbig[:, 2 * C:]
     x1 = x.double() + torch.einsum("bij,bjhw->bihw", mf.double(), v.double())
     if bo is not None:
         x1 = x1 + bo.double()[None, :, None, None]
-    ref = gdfn_ref(x1, lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
+    ref = bm.gdfn(x1, lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
     pk = _hip.pack_gdfn_fused(pin_w.to(dev), pin_b, dw_w, dw_b, pout_w, lnw, lnb, kperm=True)
     frag = _hip.pack_mfold_frag(mf).to(dev)
     assert torch.equal(_hip.unpack_mfold_frag(frag, B, C), (mf.half().float() + (mf - mf.half().float()).half().float()))
@@ -127,18 +98,6 @@ def test_attn_gdfn_fused(dev, C, hid, H, W, B, ln, bias):
     ops.attn_gdfn_fused(pk, xb[:, 1:1 + C], vb[:, 2 * C:], frag, y2, C, hid, ln_mode=ln,
                         bias_o=None if bo is None else bo.to(dev), bias=None if pout_b is None else pout_b.to(dev))
     assert torch.equal(y2.cpu(), y[:, 2:2 + C]), "not deterministic"
-
-
-def to_tm(t):
-    """[B][C][H][W] planar -> the same container holding the tile-major channel-last order of include/irm_hip.h
-    ([tile][8 x 32 pixels][C])."""
-    B, C, H, W = t.shape
-    return t.reshape(B, C, H // 8, 8, W // 32, 32).permute(0, 2, 4, 3, 5, 1).reshape(B, C, H, W).contiguous()
-
-
-def from_tm(t):
-    B, C, H, W = t.shape
-    return t.reshape(B, H // 8, W // 32, 8, 32, C).permute(0, 5, 1, 3, 2, 4).reshape(B, C, H, W).contiguous()
 
 
 @pytest.mark.parametrize("C,hid,H,W,B,lay", [(96, 255, 16, 64, 2, 7), (96, 255, 24, 32, 1, 1), (48, 127, 8, 96, 3, 2),
@@ -177,15 +136,9 @@ def test_gdfn_tail_c192(dev, H, W, B, ln, bias):
     tag = f"gt{H}_{W}_{B}_{ln}"
     ws = 0.2
     big = rnd(tag + "x", (B, C + 3, H, W), -1.5, 2.0)
-    lnw = rnd(tag + "lw", (C,), 0.5, 1.5)
-    lnb = rnd(tag + "lb", (C,), -0.2, 0.2) if ln == 1 else None
-    pin_w, pout_w = rnd(tag + "pi", (2 * hid, C), -ws, ws), rnd(tag + "po", (C, hid), -ws, ws)
-    dw_w = rnd(tag + "dw", (2 * hid, 9), -0.4, 0.4)
-    pin_b = rnd(tag + "pib", (2 * hid,), -0.3, 0.3) if bias else None
-    dw_b = rnd(tag + "dwb", (2 * hid,), -0.3, 0.3) if bias else None
-    pout_b = rnd(tag + "pob", (C,), -0.3, 0.3) if bias else None
+    lnw, lnb, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b = bm.gdfn_operands(rnd, tag, C, hid, ln, bias, ws)
     x = big[:, 1:1 + C]
-    ref = gdfn_ref(x, lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
+    ref = bm.gdfn(x.double(), lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
     frag, s_w, bp = _hip.pack_pin_padded(pin_w.to(dev), None if pin_b is None else pin_b.to(dev), hp)
     s_x = _hip.ln_split_scale(lnw, lnb, C, ln == 1)
     pk = _hip.pack_gdfn_tail(dw_w, dw_b, pout_w.to(dev))
@@ -195,12 +148,7 @@ def test_gdfn_tail_c192(dev, H, W, B, ln, bias):
                             out_scale=1.0 / (s_w * s_x), bias=bp)
     assert torch.all(h_cl[-64:] == 7.0), "wrote past h"
     # h itself: un-permute [B][tile][chunk of 64 channels][256][64] and compare with float64 project_in(LN(x))
-    xd = x.double()
-    mu, var = xd.mean(1, keepdim=True), xd.var(1, unbiased=False, keepdim=True)
-    xn = ((xd - mu) if ln == 1 else xd) / torch.sqrt(var + 1e-5) * lnw.double()[None, :, None, None]
-    if ln == 1:
-        xn = xn + lnb.double()[None, :, None, None]
-    href = F.conv2d(xn, pin_w.double()[:, :, None, None], None if pin_b is None else pin_b.double())
+    href = F.conv2d(bm.layer_norm(x.double(), lnw, lnb, ln), pin_w.double()[:, :, None, None], None if pin_b is None else pin_b.double())
     hc = (h_cl[:-64].cpu().view(B, H // 8, W // 32, 2 * hp // 64, 8, 32, 64).permute(0, 3, 6, 1, 4, 2, 5)
           .reshape(B, 2 * hp, H, W))                     # [B][ty][tx][chunk][8][32][64] -> planar
     assert float((hc[:, :hid].double() - href[:, :hid]).abs().max()) <= TOL * max(1.0, float(href.abs().max()))
@@ -223,19 +171,6 @@ def test_gdfn_fused_deterministic(dev):
     ops.gdfn_fused(pk, x, y1, C, hid, ln_mode=1)
     ops.gdfn_fused(pk, x, y2, C, hid, ln_mode=1)
     assert torch.equal(y1, y2)
-
-
-def qkv_ref(x, lnw, lnb, ln_mode, w, b, dw_w, dw_b, eps=1e-5):
-    xd = x.double()
-    mu = xd.mean(1, keepdim=True)
-    var = xd.var(1, unbiased=False, keepdim=True)
-    if ln_mode == _hip.LN_WITHBIAS:
-        xn = (xd - mu) / torch.sqrt(var + eps) * lnw.double()[None, :, None, None] + lnb.double()[None, :, None, None]
-    else:
-        xn = xd / torch.sqrt(var + eps) * lnw.double()[None, :, None, None]
-    M = w.shape[0]
-    h = F.conv2d(xn, w.double()[:, :, None, None], None if b is None else b.double())
-    return F.conv2d(h, dw_w.double().view(M, 1, 3, 3), None if dw_b is None else dw_b.double(), padding=1, groups=M)
 
 
 QKV_CASES = [
@@ -262,7 +197,7 @@ def test_qkv_dw_fused(dev, C, H, W, B, ln, bias):
     wb = rnd(tag + "wb", (M,), -0.3, 0.3) if bias else None
     dw_b = rnd(tag + "dwb", (M,), -0.3, 0.3) if bias else None
     x = big[:, 1:1 + C]
-    ref = qkv_ref(x, lnw, lnb, ln, w, wb, dw_w, dw_b)
+    ref = bm.qkv(x.double(), lnw, lnb, ln, w, wb, dw_w, dw_b)
     pk = _hip.pack_qkv_fused(w.to(dev), wb, dw_w, dw_b, lnw, lnb)
     xb = big.to(dev)
     yb = torch.full((B, M + 2, H, W), 7.0, device=dev)
@@ -297,17 +232,11 @@ def test_qk_tile_major_chain(dev, C, heads, H, W, B, f16):
             assert torch.equal(v_back, res[0][0][:, 2 * C:]) and torch.equal(qkv[:, :2 * C].cpu(), res[1][0][:, :2 * C])
             continue
         ops.qkv_dw_fused(pk, x, qkv, C, M, ln_mode=1, tm=tm)
-        _, nchunk, rec = ops.mdta_plan(B, C, heads, N)
-        part = torch.full((B * heads * nchunk * rec,), float("nan"), device=dev)
-        gsum = torch.empty(B * heads * rec, device=dev)
-        mfold = torch.zeros(B * ops.mfold_numel(C), device=dev)
-        attn = torch.empty(B, heads, C // heads, C // heads, device=dev)
-        ops.mdta_fold(qkv, part, gsum, temp, wout, mfold, C, heads, attn=attn, gram_scale=gs, tm=tm)
-        res.append((qkv.cpu(), attn.cpu(), mfold.cpu()))
+        res.append((qkv.cpu(),) + bm.run_mdta_fold(dev, qkv, temp, wout, C, heads, gram_scale=gs, tm=tm)[:2])
     (q0, a0, m0), (q1, a1, m1) = res
     assert torch.equal(q0[:, 2 * C:], q1[:, 2 * C:]), "v must not depend on the q, k layout"
     # the tile-major block of tile (ty, tx) holds channel ch of pixels (8 ty + r, 32 tx + c) at [ch][32 r + c]
-    back = q1[:, :2 * C].reshape(B, H // 8, W // 32, 2 * C, 8, 32).permute(0, 3, 1, 4, 2, 5).reshape(B, 2 * C, H, W)
+    back = bm.qk_from_tm(q1[:, :2 * C])
     assert torch.equal(back, q0[:, :2 * C]), "tile-major q, k are not a permutation of the planar ones"
     assert float((a0 - a1).abs().max()) <= 2e-6 and float((m0 - m1).abs().max()) <= 2e-6
 
@@ -341,11 +270,8 @@ def test_qkv_gram_cm_c48(dev, H, W, B, x_tm):
         else:
             part = torch.full((nb * nchunk * rec,), float("nan"), device=dev)
             ops.qkv_dw_fused(pk, xi, qkv, C, M, ln_mode=1, tm=True, x_tm=x_tm, v_tm=True)
-        gsum = torch.empty(nb * rec, device=dev)
-        mfold = torch.zeros(nb * ops.mfold_numel(C), device=dev)
-        attn = torch.empty(nb, heads, C, C, device=dev)
-        ops.mdta_fold(qkv, part, gsum, temp, wout, mfold, C, heads, attn=attn, gram_scale=gs, tm=True, nchunk_ready=nready)
-        return qkv[:, 2 * C:].cpu(), attn.cpu(), mfold.cpu()
+        attn, mfold, _ = bm.run_mdta_fold(dev, qkv, temp, wout, C, heads, part=part, gram_scale=gs, tm=True, nchunk_ready=nready)
+        return qkv[:, 2 * C:].cpu(), attn, mfold
 
     v0, a0, m0 = fold(False, xin, B)
     v1, a1, m1 = fold(True, xin, B)
@@ -380,16 +306,11 @@ def test_fused_trained_like_statistics(dev, act_scale, ln):
     lnb = rnd(tag + "lb", (C,), -2.0, 2.0) if ln == 1 else None
     pin_w, pout_w = _logu(tag + "pi", (2 * hid, C), 1e-5, 10.0), _logu(tag + "po", (C, hid), 1e-5, 3.0) / hid ** 0.5
     dw_w = _logu(tag + "dw", (2 * hid, 9), 1e-4, 1.0)
-    ref = gdfn_ref(x, lnw, lnb, ln, pin_w, None, dw_w, None, pout_w, None)
+    ref = bm.gdfn(x.double(), lnw, lnb, ln, pin_w, None, dw_w, None, pout_w, None)
     xd = x.to(dev)
     # plain fp32 chain on the same device (torch kernels) as the yardstick
-    mu = xd.mean(1, keepdim=True)
-    var = xd.var(1, unbiased=False, keepdim=True)
-    xn = ((xd - mu) if ln == 1 else xd) / torch.sqrt(var + 1e-5) * lnw.to(dev)[None, :, None, None]
-    if ln == 1:
-        xn = xn + lnb.to(dev)[None, :, None, None]
-    h = F.conv2d(F.conv2d(xn, pin_w.to(dev)[:, :, None, None]), dw_w.to(dev).view(-1, 1, 3, 3), padding=1, groups=2 * hid)
-    y32 = xd + F.conv2d(F.gelu(h[:, :hid]) * h[:, hid:], pout_w.to(dev)[:, :, None, None])
+    xn = bm.layer_norm(xd, lnw.to(dev), None if lnb is None else lnb.to(dev), ln)
+    y32 = bm.gdfn_from_ln(xd, xn, pin_w.to(dev), None, dw_w.to(dev), None, pout_w.to(dev), None)[0]
     y = torch.empty_like(xd)
     ops.gdfn_fused(_hip.pack_gdfn_fused(pin_w.to(dev), None, dw_w, None, pout_w, lnw, lnb), xd, y, C, hid, ln_mode=ln)
     scale = float(ref.abs().max())
@@ -399,8 +320,8 @@ def test_fused_trained_like_statistics(dev, act_scale, ln):
     # the qkv branch with the same statistics
     M = 3 * C
     w, dq = _logu(tag + "qw", (M, C), 1e-5, 10.0), _logu(tag + "qd", (M, 9), 1e-4, 1.0)
-    refq = qkv_ref(x, lnw, lnb, ln, w, None, dq, None)
-    q32 = F.conv2d(F.conv2d(xn, w.to(dev)[:, :, None, None]), dq.to(dev).view(-1, 1, 3, 3), padding=1, groups=M)
+    refq = bm.qkv(x.double(), lnw, lnb, ln, w, None, dq, None)
+    q32 = bm.qkv_from_ln(xn, w.to(dev), None, dq.to(dev), None)
     yq = torch.empty(B, M, H, W, device=dev)
     ops.qkv_dw_fused(_hip.pack_qkv_fused(w.to(dev), None, dq, None, lnw, lnb), xd, yq, C, M, ln_mode=ln)
     scale = float(refq.abs().max())
@@ -419,7 +340,7 @@ def test_gate_out_of_range_saturates_instead_of_nan(dev):
     pin_w = rnd("satpi", (2 * hid, C), -600.0, 600.0)
     dw_w, pout_w = rnd("satdw", (2 * hid, 9), -0.4, 0.4), rnd("satpo", (C, hid), -0.1, 0.1)
     lnw, lnb = rnd("satlw", (C,), 0.5, 1.5), rnd("satlb", (C,), -0.2, 0.2)
-    ref = gdfn_ref(x.cpu(), lnw, lnb, 1, pin_w, None, dw_w, None, pout_w, None)
+    ref = bm.gdfn(x.cpu().double(), lnw, lnb, 1, pin_w, None, dw_w, None, pout_w, None)
     gate_max = float((ref - x.cpu().double()).abs().max())
     y = torch.empty_like(x)
     ops.gdfn_fused(_hip.pack_gdfn_fused(pin_w.to(dev), None, dw_w, None, pout_w, lnw, lnb), x, y, C, hid, ln_mode=1)

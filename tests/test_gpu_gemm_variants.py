@@ -1,15 +1,15 @@
 """Every kernel instantiation behind the two 1x1-GEMM entry points, at its edges, against float64.
 
 irm_gemm1x1_f32 and irm_gemm1x1_f16x3_f32 both go through gemm_entry (csrc/gemm_pw.hip), which picks one of 78
-instantiations of gemm_ring_kernel, gemm_pw_kernel and gemm_xres_kernel.  VARIANTS lists them, expected_variant()
-restates the dispatch in Python, and CASES places cases on each variant's edges: M tails, a partly filled last pass,
-M <= 48, uneven ygroups, K tails, N not a multiple of 256, channel slices of larger buffers, and every option the
-variant accepts.
+instantiations of gemm_ring_kernel, gemm_pw_kernel and gemm_xres_kernel.  tests/variant_model.py lists them (VARIANTS)
+and restates the dispatch in Python (expected_variant); CASES places cases on each variant's edges: M tails, a partly
+filled last pass, M <= 48, uneven ygroups, K tails, N not a multiple of 256, channel slices of larger buffers, and every
+option the variant accepts.
 
 For each case, on the same seeded inputs:
   e    = max|y_gpu - y64|   (y64: the same op in float64 on the CPU)
   e_32 = max|y32 - y64|     (y32: the same op in float32 on the CPU)
-and the case passes when e <= K * e_32 + F * max|y64|, the bar of tests/test_gpu_precision.py.  The written slice of
+and the case passes when e <= K * e_32 + F * max|y64|, the ledger's bar (block_model.passes).  The written slice of
 the output starts as NaN and the rest of its buffer as a sentinel: an unwritten element fails, so does a stray write.
 Two committed positive controls (lo halves of the split weight zeroed; one weight of the last, partial output tile
 perturbed by 2^-10) must fail the same bar."""
@@ -17,85 +17,16 @@ import math
 
 import pytest
 import torch
-import torch.nn.functional as TF
 
+import block_model as bm
+from block_model import F, K, passes
+from guards import channel_slice as _slice
 from irm_amd import _hip, ops, synth
-from test_gpu_precision import F, K
+from variant_model import CTS, LN_NONE, LN_WB, VARIANTS, expected_variant, res_depths, xres
+from variant_model import gemm_generic as generic
+from variant_model import gemm_ring as ring
 
 SENTINEL = 7.0
-LN_NONE, LN_WB, LN_BF = 0, 1, 2
-CTS = (3, 4, 6, 8, 9)                   # the ct switches of gemm_entry (gemm_pw.hip:656-662, 669-675, 678-684)
-
-
-# --------------------------------------------------------------------------- the variant table and its dispatch mirror
-def ring(pt, ct, ns, ln, res, f16):
-    return f"gemm_ring_kernel<{pt}, {ct}, {ns}, {ln}, {'true' if res else 'false'}, {'true' if f16 else 'false'}>"
-
-
-def generic(ct, vec):
-    return f"gemm_pw_kernel<2, {ct}, {'true' if vec else 'false'}>"
-
-
-def xres(kt, ct):
-    # xres_launch<KT, CT, NS = 3, NPT = 16, WP = 2>, KT 12: <12, CT, 3, 8, 2> (gemm_xres.hip:229-236, 248-253);
-    # the kernel's own template order is <KT, CT, NS, WP, NPT>
-    return f"gemm_xres_kernel<{kt}, {ct}, 3, 2, {8 if kt == 12 else 16}>"
-
-
-def ring_ns(ct, k, f16):
-    """Ring depth of a residual launch (PT 2): 3 for ct <= 6 and K <= 512 (the split kernel not at ct 4), else 4
-    (launch_ring, gemm_pw.hip:560-577)."""
-    return 3 if ct <= 6 and k <= 512 and not (f16 and ct == 4) else 4
-
-
-def _res_depths(ct, f16):
-    return (3, 4) if ct <= 6 and not (f16 and ct == 4) else (4,)
-
-
-VARIANTS = sorted(
-    # exact f32 ring, residual: PT 2, no LN (launch_ring_any, gemm_pw.hip:584-587)
-    [ring(2, ct, ns, LN_NONE, True, False) for ct in CTS for ns in _res_depths(ct, False)]
-    # exact f32 ring, no residual: PT 4 (3-deep ring) or PT 2 (4-deep), any LN (gemm_pw.hip:588-595)
-    + [ring(pt, ct, 3 if pt == 4 else 4, ln, False, False) for pt in (2, 4) for ct in CTS for ln in (0, 1, 2)]
-    # split ring, residual: PT 2, no LN (launch_ring_split, gemm_pw.hip:601-604)
-    + [ring(2, ct, ns, LN_NONE, True, True) for ct in CTS for ns in _res_depths(ct, True)]
-    # split ring, no residual: PT 4 (gemm_pw.hip:605-607)
-    + [ring(4, ct, 3, ln, False, True) for ct in CTS for ln in (0, 1, 2)]
-    # generic streaming kernel (gemm_pw.hip:678-685 -> launch_gemm 610-617)
-    + [generic(ct, vec) for ct in CTS for vec in (False, True)]
-    # input-resident split kernel (gemm_xres.hip:246-253)
-    + [xres(kt, ct) for kt in (2, 4, 6, 12) for ct in (8, 9)])
-assert len(VARIANTS) == len(set(VARIANTS)) == 78
-
-
-def expected_variant(*, split, M, K, N, B, ct, ygroups, ln, res, stats_out, w_bs, vec):
-    """The instantiation gemm_entry launches (None = IRM_EINVAL).
-    Mirrors gemm_pw.hip:626-686 and gemm_xres.hip:246-257."""
-    mt = (M + 15) // 16
-    if stats_out and mt > ct:                                       # gemm_pw.hip:644
-        return None
-    nchunks = -(-mt // ct)
-    yg = min(max(ygroups, 1), nchunks)                              # gemm_pw.hip:645-647
-    if split:
-        if not vec or N < 4 or (res and ln):                        # gemm_pw.hip:651
-            return None
-        if K <= 192 and ln and not stats_out and not res and not w_bs:    # gemm_pw.hip:652
-            st, kt_ct = (K + 15) // 16, 9 if mt % 9 == 0 else 8    # gemm_xres.hip:246
-            if st in (2, 4, 6) or (st == 12 and M >= 512):          # gemm_xres.hip:247-256
-                return xres(st, kt_ct)
-        if ct not in CTS:
-            return None
-        if res:                                                     # gemm_pw.hip:601-604
-            return ring(2, ct, ring_ns(ct, K, True), LN_NONE, True, True)
-        return ring(4, ct, 3, ln, False, True)                      # gemm_pw.hip:605-607
-    if ct not in CTS:
-        return None
-    if vec and N >= 4 and not (res and ln):                         # gemm_pw.hip:665
-        if res:
-            return ring(2, ct, ring_ns(ct, K, False), LN_NONE, True, False)
-        pt = 4 if B * -(-N // 256) * yg >= 512 else 2               # gemm_pw.hip:668
-        return ring(pt, ct, 3 if pt == 4 else 4, ln, False, False)
-    return generic(ct, vec)                                         # gemm_pw.hip:678-685
 
 
 # --------------------------------------------------------------------------- cases
@@ -111,7 +42,7 @@ def _case(variant, name, M, K, H, W, B, *, ct, yg=None, ln=0, res=None, scale=Fa
 def _ring_res_cases(ct, ns, f16):
     v = ring(2, ct, ns, LN_NONE, True, f16)
     # NS 4 where NS 3 exists: K > 512
-    k_lo, k_hi = (530, 601) if ns == 4 and 3 in _res_depths(ct, f16) else (37, 90)
+    k_lo, k_hi = (530, 601) if ns == 4 and 3 in res_depths(ct, f16) else (37, 90)
     return [
         _case(v, "m%16=1 partial-last-pass inplace scale", 16 * ct + 1, k_lo, 12, 20, 2, ct=ct, yg=1, res="inplace",
               scale=True, bias=True),
@@ -195,7 +126,7 @@ def _xres_cases(kt, ct):
 CASES = []
 for _ct in CTS:
     for _f16 in (False, True):
-        for _ns in _res_depths(_ct, _f16):
+        for _ns in res_depths(_ct, _f16):
             CASES += _ring_res_cases(_ct, _ns, _f16)
     for _ln in (0, 1, 2):
         CASES += _ring_plain_cases(2, _ct, _ln, False) + _ring_plain_cases(4, _ct, _ln, False)
@@ -227,47 +158,19 @@ def case_variant(c):
                             ln=c["ln"], res=c["res"] is not None, stats_out=c["stats_out"], w_bs=c["w_bs"], vec=_vec(c))
 
 
-def _slice(dev, B, C, extra, off, H, W, misalign, fill):
-    """A [B, C, H, W] channel slice at channel `off` of a [B, C + extra, H, W] buffer (as a flat buffer: one more float
-    in front when misaligned).  Returns (flat buffer, view)."""
-    N = H * W
-    flat = torch.full((B * (C + extra) * N + 4,), fill, dtype=torch.float32, device=dev)
-    o = 1 if misalign else 0
-    view = flat.as_strided((B, C, H, W), ((C + extra) * N, N, W, 1), o + off * N)
-    return flat, view
-
-
-def _ln64(x, lnw, lnb, ln):
-    if not ln:
-        return x
-    mu, var = x.mean(1, keepdim=True), x.var(1, unbiased=False, keepdim=True)
-    k = x.shape[1]
-    xn = ((x - mu) if ln == LN_WB else x) / torch.sqrt(var + 1e-5) * lnw.view(1, k, 1, 1)
-    return xn + lnb.view(1, k, 1, 1) if ln == LN_WB else xn
-
-
-def _act(y, act):
-    return {0: lambda t: t, 1: torch.relu, 2: TF.gelu, 3: TF.silu}[act](y)
-
-
-def _stats(y):
-    mean = y.mean(1)
-    return mean, 1.0 / torch.sqrt(y.var(1, unbiased=False) + 1e-5)
-
-
 def reference(c, t, dt):
     """y (and its LayerNorm statistics) of a case in dtype dt on the CPU."""
     B, M, Kc, H, W = c["B"], c["M"], c["K"], c["H"], c["W"]
-    x = _ln64(t["x"].to(dt), t["lnw"].to(dt), t["lnb"].to(dt), c["ln"])
+    x = bm.layer_norm(t["x"].to(dt), t["lnw"], t["lnb"], c["ln"])
     w = t["w"].to(dt)
     y = torch.einsum("bmk,bkhw->bmhw", w, x) if w.dim() == 3 else torch.einsum("mk,bkhw->bmhw", w, x)
     if c["bias"]:
         y = y + t["bias"].to(dt).view(1, M, 1, 1)
-    y = _act(y, c["act"])
+    y = bm.act(y, c["act"])
     if c["res"] is not None:
         r = t["r"].to(dt)
         y = y + (r * t["scale"].to(dt).view(1, M, 1, 1) if c["scale"] else r)
-    return y, (_stats(y) if c["stats_out"] else None)
+    return y, (bm.ln_stats(y) if c["stats_out"] else None)
 
 
 def inputs(c, idx):
@@ -292,7 +195,7 @@ def run_case(c, t, dev, wp=None):
     """Launch a case through ops.gemm1x1; returns (y slice, whole y buffer, written mask, stats_out or None)."""
     B, M, Kc, H, W = c["B"], c["M"], c["K"], c["H"], c["W"]
     N = H * W
-    mis = c["misalign"]
+    mis = int(c["misalign"])          # x, y, res start one float past a 16-byte boundary
     _, xv = _slice(dev, B, Kc, 3, 2, H, W, mis, 0.0)
     xv.copy_(t["x"].to(dev))
     ybuf, yv = _slice(dev, B, M, 2, 1, H, W, mis, SENTINEL)
@@ -320,10 +223,6 @@ def run_case(c, t, dev, wp=None):
                 stats_out=st_out, res_scale=t["scale"].to(dev) if c["scale"] else None, split=c["split"])
     torch.cuda.synchronize()
     return yv.cpu().double(), ybuf.cpu(), mask.cpu(), (None if st_out is None else st_out.cpu().double())
-
-
-def passes(e, e32, ymax):
-    return e <= K * e32 + F * ymax
 
 
 def measure(c, t, got, stats_got):

@@ -18,55 +18,18 @@ import torch.nn.functional as F
 from irm_amd import _hip, ensemble, ops, resize, synth, utils
 from oracle import mair_ref, tiler_ref
 
-from guards import banded, has_nan, intact, sentinel_out, two_fills
-from test_gpu_ensemble import merge_float64, packed_blocks
-from test_gpu_fused import gdfn_ref, qkv_ref
-from test_gpu_mair import check_scan_f64, scan_inputs, ysum_floor
-from test_gpu_niqe import check_against_host
-from test_gpu_ops import _ln_ref
-from test_gpu_sr_protocol import check_quantised
+import block_model as bm
+from frame_checks import check_against_host, check_quantised, down, merge_float64, packed_blocks, up
+from guards import SLACK, Guards, clean, guarded_fold, has_nan, two_fills
+from scan_model import check_scan_f64, scan_inputs, ysum_floor
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SLACK = 8          # elements between the images of a strided operand (a multiple of 4: rows stay 16-byte aligned)
 
 
 def rnd(name, shape, lo=-1.0, hi=1.0):
     return synth.uniform(909, name, shape, lo, hi)
-
-
-class Guards:
-    """The guarded operands of one launch sequence: inp() bands an input, out() places an output or a workspace and
-    remembers it, check() asserts that every remembered surrounding is intact.  Every buffer stays alive as long as
-    the object does: a raw pointer taken from a temporary view would otherwise outlive its allocation."""
-
-    def __init__(self, dev):
-        self.dev, self.outs, self.ins = dev, [], []
-
-    def inp(self, t, slack=0, fill=None):
-        if t is None:
-            return None
-        buf, view = banded(t, self.dev, fill, batch_slack=slack)
-        self.ins.append(buf)
-        return view
-
-    def out(self, name, shape, dtype=torch.float32, slack=0):
-        buf, view = sentinel_out(shape, self.dev, dtype, batch_slack=slack)
-        self.outs.append((name, buf, view))
-        return view
-
-    def check(self):
-        torch.cuda.synchronize()
-        bad = [name for name, buf, view in self.outs if not intact(buf, view)]
-        assert not bad, f"writes outside: {bad}"
-
-
-def clean(t):
-    """The result on the host, after the check that no NaN (a guard element of an input) reached it."""
-    t = t.cpu().contiguous()
-    assert not has_nan(t), "a NaN from outside an input reached the result"
-    return t
 
 
 # --------------------------------------------------------------------------- mamba.hip
@@ -86,7 +49,7 @@ def test_selective_scan_and_combine(dev, D, N, R):
     """Block path (4, 3) with D = 96 = one full + one partial 64-channel block; flat path (1, 4) with D = 66 and
     (16, 4) with D = 90 (4 D is no multiple of 64).  B = 2, 5 x 7 pixels, chunk 32: the last chunk has 3 steps.
     state, sdt, ysum at exactly the header's sizes; gate at exactly [B][4][D]; z and out with batch slack.
-    Bars: SCAN_K / SCAN_F / ysum_floor (test_gpu_mair.check_scan_f64) and test_losh_combine_production_vs_float64."""
+    Bars: SCAN_K / SCAN_F / ysum_floor (scan_model.check_scan_f64) and test_losh_combine_production_vs_float64."""
     B, H, W, chunk = 2, 5, 7, 32
     L, J = H * W, R + 2 * N
     nchunk, DB = -(-L // chunk), -(-D // 64)
@@ -178,14 +141,9 @@ def test_ensemble_merge(dev, s, B, Co):
 
 
 # --------------------------------------------------------------------------- fpn.hip
-def _stats_ref(x):
-    xd = x.double().reshape(x.shape[0], x.shape[1], -1)
-    return xd.mean(-1), 1.0 / torch.sqrt(xd.var(-1, unbiased=False) + 1e-5)
-
-
 def _check_stats(st, x, hi):
     got = clean(st).double()
-    mean, rstd = _stats_ref(x)
+    mean, rstd = bm.ln_stats(x.double().flatten(2), dim=-1)      # per plane
     assert float((got[..., 0] - mean).abs().max()) < 1e-5 * max(1.0, abs(hi))
     assert float(((got[..., 1] - rstd).abs() / rstd).max()) < 1e-4
 
@@ -215,7 +173,7 @@ def test_chan_norm_act_in_place_with_residual(dev):
     B, C, H, W = 2, 5, 23, 41
     x, r = rnd("cn", (B, C, H, W), -2, 3), rnd("cnr", (B, C, H, W))
     w, b = rnd("cnw", (C,), 0.5, 1.5), rnd("cnb", (C,))
-    mean, rstd = _stats_ref(x)
+    mean, rstd = bm.ln_stats(x.double().flatten(2), dim=-1)      # per plane
     ref = F.relu(F.instance_norm(x.double(), None, None, w.double(), b.double(), True, 0.1, 1e-5)) + r.double()
     g = Guards(dev)
     y = g.out("y", (B, C, H, W), slack=SLACK)
@@ -262,16 +220,6 @@ def _frame(rng, shape, dtype):
     return rng.integers(0, (255 if dtype == np.uint8 else 65535) + 1, size=shape).astype(dtype)
 
 
-def _bits(a):
-    """A uint8 / uint16 host frame as the tensor the kernels take (uint16 as its int16 bit pattern)."""
-    return torch.from_numpy(np.ascontiguousarray(a.view(np.int16) if a.dtype == np.uint16 else a))
-
-
-def _unbits(t, dtype):
-    a = t.cpu().numpy()
-    return a.view(np.uint16) if dtype == np.uint16 else a
-
-
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
 @pytest.mark.parametrize("pad_zero", [0, 1])
 @pytest.mark.parametrize("sigma", [None, 25])
@@ -297,7 +245,7 @@ def test_tile_extract(dev, dtype, pad_zero, sigma):
     def run(fill):
         g = Guards(dev)
         tiles = g.out("tiles", (T, T_C, T_PAD, T_PAD))
-        _hip.call("irm_tile_extract", _hip.ptr(g.inp(_bits(img), fill=fill)), int(dtype == np.uint16),
+        _hip.call("irm_tile_extract", _hip.ptr(g.inp(up(img, "cpu"), fill=fill)), int(dtype == np.uint16),
                   _hip.ptr(g.inp(torch.tensor(origins, dtype=torch.int32), fill=fill)), _hip.ptr(g.inp(noise)), _hip.ptr(tiles),
                   T_H, T_W, T_C, T_PS, T_PS, T_PAD, T_PAD, T, 0.0, 1.0, pad_zero)
         g.check()
@@ -334,7 +282,7 @@ def test_window_blend(dev, dtype, s):
         out, sse = g.out("out", (s * T_H, s * T_W, Co), tdt), g.out("sse", (1,), torch.int64)
         sse.zero_()
         args = (_hip.ptr(g.inp(pred)), _hip.ptr(g.inp(torch.tensor(origins, dtype=torch.int32), fill=fill)), _hip.ptr(g.inp(window)),
-                _hip.ptr(out), int(dtype == np.uint16), _hip.ptr(g.inp(_bits(target), fill=fill)), _hip.ptr(sse), T_H, T_W, Co, Cp,
+                _hip.ptr(out), int(dtype == np.uint16), _hip.ptr(g.inp(up(target, "cpu"), fill=fill)), _hip.ptr(sse), T_H, T_W, Co, Cp,
                 T_PS, T_PS, T_PAD, T_PAD, T_PS, T)
         if s == 1:
             _hip.call("irm_window_blend", *args, 1.0, 0.0)
@@ -344,7 +292,7 @@ def test_window_blend(dev, dtype, s):
         return out.cpu(), sse.cpu()
 
     out, sse = two_fills(run)
-    got = _unbits(out, dtype)
+    got = down(out, dtype)
     assert np.array_equal(got, ref), f"{int((got != ref).sum())} of {ref.size} output values differ"
     assert int(sse[0]) == int(((ref.astype(np.int64) - target.astype(np.int64)) ** 2).sum())
 
@@ -357,7 +305,7 @@ FRAME_KINDS = [(np.uint8, 3), (np.uint8, 1), (np.uint16, 3), (np.uint16, 1)]
 @pytest.mark.parametrize("scale,H,W", [(2, 6, 7), (0.5, 10, 11), (0.25, 18, 19)])
 def test_imresize_bicubic(dev, dtype, C, scale, H, W):
     """The shortest legal sides (H = P taps: 6 enlarging, 4 s + 2 shrinking) and an odd W = P + 1; K = 2.  The tap tables
-    between NaN (weights) and two fills (indices).  Bars of test_gpu_sr_protocol.check_resize."""
+    between NaN (weights) and two fills (indices).  Bars of frame_checks.check_resize."""
     K = 2
     rng = np.random.default_rng(17)
     frames = _frame(rng, (K, H, W, C), dtype)
@@ -372,7 +320,7 @@ def test_imresize_bicubic(dev, dtype, C, scale, H, W):
         for out_float in (1, 0):
             g = Guards(dev)
             out = g.out("out", (K, OH, OW, C), torch.float32 if out_float else tdt)
-            _hip.call("irm_imresize_bicubic", _hip.ptr(g.inp(_bits(frames), fill=fill)), int(dtype == np.uint16), _hip.ptr(out),
+            _hip.call("irm_imresize_bicubic", _hip.ptr(g.inp(up(frames, "cpu"), fill=fill)), int(dtype == np.uint16), _hip.ptr(out),
                       out_float, _hip.ptr(g.inp(torch.from_numpy(wh.astype(np.float32)))),
                       _hip.ptr(g.inp(torch.from_numpy(ih.astype(np.int32)), fill=fill)),
                       _hip.ptr(g.inp(torch.from_numpy(ww.astype(np.float32)))),
@@ -385,7 +333,7 @@ def test_imresize_bicubic(dev, dtype, C, scale, H, W):
     assert not has_nan(f32)
     want = np.stack([utils.imresize_host(f, scale) for f in frames])
     assert float(np.abs(f32.numpy().astype(np.float64) - want).max()) <= 1e-6
-    check_quantised(_unbits(q, dtype), np.stack([utils.imresize_host(f, scale, out="same") for f in frames]),
+    check_quantised(down(q, dtype), np.stack([utils.imresize_host(f, scale, out="same") for f in frames]),
                     f"guarded resize {scale} {dtype.__name__} C{C}")
 
 
@@ -393,7 +341,7 @@ def test_imresize_bicubic(dev, dtype, C, scale, H, W):
 @pytest.mark.parametrize("H,W", [(7, 7), (13, 23)])
 def test_frame_metrics(dev, dtype, C, H, W):
     """7 x 7 (one interior pixel) and 13 x 23 (odd sides); K = 2; ws_words exactly the header's minimum.  The squared
-    error is exact, SSIM within 1e-9 of the host (test_gpu_metrics._parity)."""
+    error is exact, SSIM within 1e-9 of the host (frame_checks.metric_parity)."""
     K = 2
     rng = np.random.default_rng(19)
     tgt = _frame(rng, (K, H, W, C), dtype)
@@ -404,7 +352,7 @@ def test_frame_metrics(dev, dtype, C, H, W):
     def run(fill):
         g = Guards(dev)
         sse, ssim, ws = g.out("sse", (K,), torch.int64), g.out("ssim", (K,), torch.float64), g.out("ws", (words,), torch.float64)
-        _hip.call("irm_frame_metrics", _hip.ptr(g.inp(_bits(pred), fill=fill)), _hip.ptr(g.inp(_bits(tgt), fill=fill)),
+        _hip.call("irm_frame_metrics", _hip.ptr(g.inp(up(pred, "cpu"), fill=fill)), _hip.ptr(g.inp(up(tgt, "cpu"), fill=fill)),
                   int(dtype == np.uint16), K, H, W, C, float(peak), _hip.ptr(sse), _hip.ptr(ssim), _hip.ptr(ws), words)
         g.check()
         return sse.cpu(), ssim.cpu()
@@ -433,7 +381,7 @@ def test_frame_metrics_basicsr(dev, dtype, C, H, W, crop, y):
         g = Guards(dev)
         sse = g.out("sse", (K,), torch.float64 if y else torch.int64)
         ssim, ws = g.out("ssim", (K,), torch.float64), g.out("ws", (words,), torch.float64)
-        _hip.call("irm_frame_metrics_basicsr", _hip.ptr(g.inp(_bits(pred), fill=fill)), _hip.ptr(g.inp(_bits(tgt), fill=fill)),
+        _hip.call("irm_frame_metrics_basicsr", _hip.ptr(g.inp(up(pred, "cpu"), fill=fill)), _hip.ptr(g.inp(up(tgt, "cpu"), fill=fill)),
                   int(dtype == np.uint16), K, H, W, C, crop, y, 0, _hip.ptr(sse), _hip.ptr(ssim), _hip.ptr(ws), words)
         g.check()
         return sse.cpu(), ssim.cpu()
@@ -465,7 +413,7 @@ def test_niqe_features(dev, dtype, C):
     def run(fill):
         g = Guards(dev)
         feat = g.out("feat", (K, nblk, 36), torch.float64)
-        _hip.call("irm_niqe_features", _hip.ptr(g.inp(_bits(frames), fill=fill)), int(dtype == np.uint16), K, H, W, C, crop, 1,
+        _hip.call("irm_niqe_features", _hip.ptr(g.inp(up(frames, "cpu"), fill=fill)), int(dtype == np.uint16), K, H, W, C, crop, 1,
                   _hip.ptr(g.inp(window)), _hip.ptr(g.inp(table)), _hip.ptr(feat), 36 * K * nblk)
         g.check()
         return (feat.cpu(),)
@@ -601,7 +549,7 @@ def test_presplit_gemms(dev, ln):
     assert ops.can_presplit(K, N)
     w, lnw, lnb, bv = _ps_operands(f"ps{ln}", M, K, ln)
     x = rnd(f"psx{ln}", (B, K, H, W), -2, 3)
-    ref = torch.einsum("mk,bkhw->bmhw", w.double(), _ln_ref(x.double(), lnw, lnb, ln)) + bv.double().view(1, M, 1, 1)
+    ref = torch.einsum("mk,bkhw->bmhw", w.double(), bm.layer_norm(x.double(), lnw, lnb, ln)) + bv.double().view(1, M, 1, 1)
     frag, s_w = _hip.pack_gemm_weight_presplit(w)
     s_x = _hip.ln_split_scale(lnw, lnb, K, ln == 1)
     g = Guards(dev)
@@ -627,12 +575,8 @@ def test_gdfn_tail_c192(dev, ln):
     assert ops.can_gdfn_tail(C, H, W)
     tag = f"gt{ln}"
     x = rnd(tag + "x", (B, C, H, W), -1.5, 2.0)
-    lnw = rnd(tag + "lw", (C,), 0.5, 1.5)
-    lnb = rnd(tag + "lb", (C,), -0.2, 0.2) if ln == 1 else None
-    pin_w, pout_w = rnd(tag + "pi", (2 * hid, C), -0.2, 0.2), rnd(tag + "po", (C, hid), -0.2, 0.2)
-    dw_w = rnd(tag + "dw", (2 * hid, 9), -0.4, 0.4)
-    pin_b, dw_b, pout_b = rnd(tag + "pib", (2 * hid,), -0.3, 0.3), rnd(tag + "dwb", (2 * hid,), -0.3, 0.3), rnd(tag + "pob", (C,), -0.3, 0.3)
-    ref = gdfn_ref(x, lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
+    lnw, lnb, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b = bm.gdfn_operands(rnd, tag, C, hid, ln, ws=0.2)
+    ref = bm.gdfn(x.double(), lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
     frag, s_w, bp = _hip.pack_pin_padded(pin_w, pin_b, hp)
     s_x = _hip.ln_split_scale(lnw, lnb, C, ln == 1)
     rec, w2, inv_s2 = _hip.pack_gdfn_tail(dw_w, dw_b, pout_w)
@@ -655,13 +599,10 @@ def test_attn_gdfn_fused(dev):
     assert ops.can_fuse_gdfn(C, W)
     tag = "ag"
     x, v, mf = rnd(tag + "x", (B, C, H, W), -1.5, 2.0), rnd(tag + "v", (B, C, H, W), -2.0, 2.0), rnd(tag + "m", (B, C, C), -0.2, 0.2)
-    lnw, lnb = rnd(tag + "lw", (C,), 0.5, 1.5), rnd(tag + "lb", (C,), -0.2, 0.2)
-    pin_w, pout_w = rnd(tag + "pi", (2 * hid, C), -0.3, 0.3), rnd(tag + "po", (C, hid), -0.3, 0.3)
-    dw_w = rnd(tag + "dw", (2 * hid, 9), -0.4, 0.4)
-    pin_b, dw_b = rnd(tag + "pib", (2 * hid,), -0.3, 0.3), rnd(tag + "dwb", (2 * hid,), -0.3, 0.3)
-    pout_b, bo = rnd(tag + "pob", (C,), -0.3, 0.3), rnd(tag + "bo", (C,), -0.3, 0.3)
+    lnw, lnb, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b = bm.gdfn_operands(rnd, tag, C, hid, ln)
+    bo = rnd(tag + "bo", (C,), -0.3, 0.3)
     x1 = x.double() + torch.einsum("bij,bjhw->bihw", mf.double(), v.double()) + bo.double()[None, :, None, None]
-    ref = gdfn_ref(x1, lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
+    ref = bm.gdfn(x1, lnw, lnb, ln, pin_w, pin_b, dw_w, dw_b, pout_w, pout_b)
     rec, w2, inv_s1, inv_s2 = _hip.pack_gdfn_fused(pin_w, pin_b, dw_w, dw_b, pout_w, lnw, lnb, kperm=True)
     g = Guards(dev)
     y = g.out("y", (B, C, H, W), slack=SLACK)
@@ -679,25 +620,6 @@ def _qkv_operands(tag, C):
     return lnw, lnb, w, dw_w, gs
 
 
-def _attn_ref(qk, heads, temp):
-    """float64 attention matrix of q, k = the first 2C channels of a float64 [B][2C or 3C][H][W] tensor."""
-    B, C = qk.shape[0], qk.shape[1]
-    q, k = qk.reshape(B, 2, heads, (C // 2) // heads, -1).unbind(1)
-    return torch.softmax(F.normalize(q, dim=-1) @ F.normalize(k, dim=-1).transpose(-1, -2) * temp.double().view(1, heads, 1, 1), dim=-1)
-
-
-def _fold(g, dev, qkv, B, C, heads, N, temp, wout, part=None, nready=None, **kw):
-    """mdta_fold with part / gsum at exactly their record sizes and the folded matrix between sentinels."""
-    _, nchunk, rec = ops.mdta_plan(B, C, heads, N)
-    c = C // heads
-    if part is None:
-        part = g.out("part", (B * heads * nchunk * rec,))
-    gsum, attn = g.out("gsum", (B * heads * rec,)), g.out("attn", (B, heads, c, c))
-    mfold = g.out("mfold", (B * (ops.mfold_frag_numel(C) if kw.get("frag") else ops.mfold_numel(C)),))
-    mfold.zero_()
-    ops.mdta_fold(qkv, part, gsum, temp, wout, mfold, C, heads, attn=attn, nchunk_ready=nready, **kw)
-    return attn, mfold
-
 
 @pytest.mark.parametrize("C", [48, 96])
 def test_qkv_tile_major_and_gram_tm(dev, C):
@@ -712,23 +634,22 @@ def test_qkv_tile_major_and_gram_tm(dev, C):
     lnw, lnb, w, dw_w, gs = _qkv_operands(tag, C)
     x = rnd(tag + "x", (B, C, H, W), -1.5, 2.0)
     temp, wout = rnd(tag + "t", (heads,), 2.0, 6.0), rnd(tag + "wo", (C, C), -0.3, 0.3)
-    ref = qkv_ref(x, lnw, lnb, 1, w, None, dw_w, None)
+    ref = bm.qkv(x.double(), lnw, lnb, 1, w, None, dw_w, None)
     rec, inv_s1 = _hip.pack_qkv_fused(w, None, dw_w, None, lnw, lnb)
     g = Guards(dev)
     qkv = g.out("qkv", (B, M, H, W), slack=SLACK)
     ops.qkv_dw_fused((g.inp(rec), inv_s1), g.inp(x, SLACK), qkv, C, M, ln_mode=1, tm=True)
     g.check()
     got = clean(qkv)
-    planar = torch.cat([got[:, :2 * C].reshape(B, H // 8, W // 32, 2 * C, 8, 32).permute(0, 3, 1, 4, 2, 5).reshape(B, 2 * C, H, W),
-                        got[:, 2 * C:]], 1)
+    planar = torch.cat([bm.qk_from_tm(got[:, :2 * C]), got[:, 2 * C:]], 1)
     assert float((planar.double() - ref).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
-    aref = _attn_ref(ref[:, :2 * C], heads, temp)
+    aref = bm.attention_qk(ref[:, :2 * C], temp, heads)
     tg, wg = g.inp(temp), g.inp(wout)
     for scale in (g.inp(gs), None):
-        attn, _ = _fold(g, dev, qkv, B, C, heads, N, tg, wg, gram_scale=scale, tm=True)
+        attn, _ = guarded_fold(g, qkv, B, C, heads, N, tg, wg, gram_scale=scale, tm=True)
         g.check()
         assert float((clean(attn).double() - aref).abs().max()) < 2e-5
-    attn, mfrag = _fold(g, dev, qkv, B, C, heads, N, tg, wg, gram_scale=g.inp(gs), tm=True, frag=True)
+    attn, mfrag = guarded_fold(g, qkv, B, C, heads, N, tg, wg, gram_scale=g.inp(gs), tm=True, frag=True)
     g.check()
     a = clean(attn).double()
     mref = torch.stack([wout.double() @ torch.block_diag(*a[i]) for i in range(B)])
@@ -745,7 +666,7 @@ def test_qkv_gram_cm(dev):
     lnw, lnb, w, dw_w, gs = _qkv_operands("qg", C)
     x = rnd("qgx", (B, C, H, W), -1.5, 2.0)
     temp, wout = rnd("qgt", (heads,), 2.0, 6.0), rnd("qgwo", (C, C), -0.3, 0.3)
-    ref = qkv_ref(x, lnw, lnb, 1, w, None, dw_w, None)
+    ref = bm.qkv(x.double(), lnw, lnb, 1, w, None, dw_w, None)
     rec, inv_s1 = _hip.pack_qkv_fused(w, None, dw_w, None, lnw, lnb)
     nchunk = (H // 8) * (W // 32) // ops.QKV_GRAM_NCH
     g = Guards(dev)
@@ -756,6 +677,6 @@ def test_qkv_gram_cm(dev):
     assert bool((qkv[:, :2 * C] == 12345.0).all()), "q, k must not be written"
     v = clean(qkv[:, 2 * C:])
     assert float((v.double() - ref[:, 2 * C:]).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
-    attn, _ = _fold(g, dev, qkv, B, C, heads, N, g.inp(temp), g.inp(wout), part=part, nready=nchunk, gram_scale=gsc, tm=True)
+    attn, _ = guarded_fold(g, qkv, B, C, heads, N, g.inp(temp), g.inp(wout), part=part, nready=nchunk, gram_scale=gsc, tm=True)
     g.check()
-    assert float((clean(attn).double() - _attn_ref(ref[:, :2 * C], heads, temp)).abs().max()) < 2e-5
+    assert float((clean(attn).double() - bm.attention_qk(ref[:, :2 * C], temp, heads)).abs().max()) < 2e-5

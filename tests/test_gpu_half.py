@@ -38,11 +38,6 @@ def from_cl(t):
     return t.detach().cpu().permute(0, 3, 1, 2).double()
 
 
-def intact(buf, view):
-    guard = buf[guards.outside(buf, view)]
-    return bool((guard == buf.new_tensor(guards.SENTINEL)).all())
-
-
 def bits(t):
     return t.detach().cpu().contiguous().view(torch.int16 if t.dtype == torch.float16 else torch.int32)
 
@@ -73,7 +68,7 @@ def run_mid(dev, x, w, bias, res, relu1, res_mode, relu2):
     ops.conv3x3_h((packed.to(dev), inv), xv, yv, ci, co, bias=bias.to(dev), relu1=relu1, res=rv, res_mode=res_mode,
                   relu2=relu2)
     torch.cuda.synchronize()
-    return from_cl(yv), bits(yv), intact(ybuf, yv)
+    return from_cl(yv), bits(yv), guards.intact(ybuf, yv)
 
 
 EPILOGUES = {"bias": (False, 0, False), "relu1": (True, 0, False), "res_relu2": (True, 1, True)}
@@ -179,7 +174,7 @@ def test_in_kernel_vs_model(dev, ci, co, H, W, relu1):
         ybuf, yv = guards.sentinel_out((2, H, W, co), dev, dtype=torch.float16, batch_slack=SLACK)
         ops.conv3x3_h_in(w.to(dev), xv, yv, ci, co, bias=bias.to(dev), relu1=relu1)
         torch.cuda.synchronize()
-        return from_cl(yv), bits(yv), intact(ybuf, yv)
+        return from_cl(yv), bits(yv), guards.intact(ybuf, yv)
     y, b0, ok = run()
     assert ok, "a store outside the output"
     assert not guards.has_nan(y), "a read outside the input reached the output"

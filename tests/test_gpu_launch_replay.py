@@ -17,10 +17,11 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+import block_model as bm
+from block_model import F, K
 from irm_amd import _hip, deblurganv2, dncnn, mair, ops, rednet, restormer
-from test_gpu_conv_variants import CASE_STRUCTURES, CONV_VARIANTS, expected_conv_variant, pass_structure, passes_per_group
-from test_gpu_gemm_variants import VARIANTS, expected_variant
-from test_gpu_precision import F, K
+from variant_model import (CASE_STRUCTURES, CONV_VARIANTS, VARIANTS, expected_conv_variant, expected_variant, pass_structure,
+                           passes_per_group)
 
 pytestmark = pytest.mark.gpu
 
@@ -183,18 +184,6 @@ def _buffers(ds, dev, seed):
     return out
 
 
-def _ln(x, lnw, lnb, ln):
-    if not ln:
-        return x
-    mu, var = x.mean(0, keepdim=True), x.var(0, unbiased=False, keepdim=True)
-    xn = ((x - mu) if ln == 1 else x) / torch.sqrt(var + 1e-5) * lnw.view(-1, 1)
-    return xn + lnb.view(-1, 1) if ln == 1 else xn
-
-
-def _act(y, act):
-    return {0: lambda t: t, 1: torch.relu, 2: TF.gelu, 3: TF.silu}[act](y)
-
-
 def _row(name, got, y64, y32):
     """(row, e, e_32, bar): the ledger bar e <= K * e_32 + F * max|y64|; NaN (unwritten) counts as infinite."""
     e = float((got.double() - y64).abs().nan_to_num(float("inf")).max())
@@ -240,12 +229,11 @@ def replay_gemm(r, dev, seed):
     for b in range(B):
         ys = {}
         for dt in (torch.float64, torch.float32):
-            xb = _ln(x[b, :Kc].reshape(Kc, N).to(dt), *(None if t[n] is None else t[n].to(dt) for n in ("lnw", "lnb")), ln) \
-                if ln else x[b, :Kc].reshape(Kc, N).to(dt)
+            xb = bm.layer_norm(x[b, :Kc].reshape(Kc, N).to(dt), t["lnw"], t["lnb"], ln, dim=0)
             yb = (wd[b] if w_bs else wd).to(dt) @ xb
             if t["bias"] is not None:
                 yb = yb + t["bias"].to(dt).view(-1, 1)
-            yb = _act(yb, kw.get("act", 0))
+            yb = bm.act(yb, kw.get("act", 0))
             if res0 is not None:
                 rb = res0[b].reshape(-1, N)[:M].to(dt)
                 yb = yb + (rb * t["res_scale"].to(dt).view(-1, 1) if t["res_scale"] is not None else rb)
@@ -271,20 +259,8 @@ def _conv_ref(x, w, bias, res, kw, dt):
             y = y + torch.einsum("oc,chw->ohw", w[:, :, dy, dx].to(dt), xp[:, dy:dy + H, dx:dx + W])
     if bias is not None:
         y = y + bias.to(dt).view(-1, 1, 1)
-    if kw.get("relu1"):
-        y = torch.relu(y)
-    rm = kw.get("res_mode", 0)
-    if rm:
-        r = res.to(dt)
-        y = y + r if rm == 1 else r - y if rm == 2 else (torch.tanh(y) + r).clamp(-1, 1)
-    if kw.get("relu2"):
-        y = torch.relu(y)
-    sm = kw.get("store_mode", 0)
-    if sm == 1:
-        y = TF.pixel_unshuffle(y[None], 2)[0]
-    elif sm == 2:
-        y = TF.pixel_shuffle(y[None], 2)[0]
-    return y
+    return bm.conv_epilogue(y[None], None if res is None else res[None], kw.get("relu1"), kw.get("res_mode", 0), kw.get("relu2"),
+                            kw.get("store_mode", 0))[0]
 
 
 def replay_conv(r, dev, seed):

@@ -9,13 +9,11 @@ import torch.nn.functional as F
 
 from irm_amd import _hip, mair, ops, synth
 from irm_amd.mair import mairunet_arch as arch
+from ledger import FLAT_CFG, NET_G
 from oracle import mair_ref
+from scan_model import check_scan_f64, run_scan, scan_inputs, ysum_floor
 
 pytestmark = pytest.mark.gpu
-
-NET_G = dict(inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], num_refinement_blocks=4, ssm_ratio=2.0,
-             flp_ratio=4.0, mlp_ratio=1.5, bias=False, dual_pixel_task=False, img_size=128, scan_len=4, batch_size=8,
-             dynamic_ids=False)
 
 
 def rnd(name, shape, lo=-1.0, hi=1.0):
@@ -33,116 +31,6 @@ def test_transpose(dev, B, R, C):
     out = torch.empty(B, C, R, device=dev)
     ops.transpose(xg[:, 1:1 + R], out, R, C)
     assert torch.equal(out.cpu(), x[:, 1:1 + R].transpose(1, 2).contiguous())
-
-
-#: float64 bar of the scan / combine tests: e_dev <= SCAN_K * e_32 + SCAN_F * max|y64|, e_32 the fp32 oracle's own error
-SCAN_K = 4.0
-SCAN_F = 2.0 ** -22
-
-
-def scan_lanes(D):
-    """Channels a float64 check covers: the first and last lane of every 64-channel block, and all of a partial block."""
-    ch = set()
-    for db in range(-(-D // 64)):
-        lo, hi = 64 * db, min(64 * db + 64, D)
-        ch.update(range(lo, hi) if hi - lo < 64 else (lo, hi - 1))
-    return torch.tensor(sorted(ch))
-
-
-def selective_scan_f64(u, dt_raw, dtb, A, Bs, Cs, Ds):
-    """Float64 restatement of the recurrence, vectorised over (batch, direction, channel, state), looped over time,
-    y formed on the fly (no [L]-long state history).  u, dt_raw (B, 4, d, L) in scan order; dtb, Ds (4, d);
-    A (4, d, N); Bs, Cs (B, 4, N, L).  dt = softplus(dt_raw + dtb); h_t = exp(dt A) h + dt B_t u_t;
-    y_t = <h_t, C_t> + Ds u_t."""
-    u, A, Bs, Cs = u.double(), A.double(), Bs.double(), Cs.double()
-    dt = F.softplus(dt_raw.double() + dtb.double().unsqueeze(-1))
-    h = torch.zeros(u.shape[:3] + (A.shape[-1],), dtype=torch.float64)
-    y = torch.empty(u.shape, dtype=torch.float64)
-    for t in range(u.shape[-1]):
-        d_t = dt[..., t].unsqueeze(-1)
-        h = torch.exp(d_t * A) * h + (d_t * u[..., t].unsqueeze(-1)) * Bs[:, :, None, :, t]
-        y[..., t] = (h * Cs[:, :, None, :, t]).sum(-1)
-    return y + Ds.double().unsqueeze(-1) * u
-
-
-def scan_inputs(tag, regime, B, D, N, R, L):
-    """(x planar u (B, D, L), proj [dt_raw | B | C] per direction in pixel order (B, 4, J, L), dtw, dtb, A, Ds).
-    synthetic: dt bias in [-4, -2], A in [-4.5, -1] (the original op test);
-    trained: A = -(1..N) as Mamba initialises it, dt bias = softplus^-1(dt), dt log-uniform in [1e-3, 1e-1];
-    memory: dt ~ 1e-3 and |A| <= 1 (a chunk keeps most of its incoming state), with raw dt spikes beyond -20 and +20 on
-    1 % of the steps so both softplus tails run."""
-    J = R + 2 * N
-    x = rnd(f"su{tag}", (B, D, L))
-    proj = rnd(f"sp{tag}", (B, 4, J, L))
-    Ds = rnd(f"sd{tag}", (4 * D,), 0.5, 1.5)
-    if regime == "synthetic":
-        dtw = rnd(f"sw{tag}", (4, D, R), -0.5, 0.5)
-        dtb = rnd(f"sb{tag}", (4, D), -4, -2)
-        A = -torch.exp(rnd(f"sa{tag}", (4 * D, N), 0, 1.5))
-    elif regime == "trained":
-        dtw = rnd(f"sw{tag}", (4, D, R), -0.1, 0.1)
-        dt = torch.exp(rnd(f"sb{tag}", (4, D), float(np.log(1e-3)), float(np.log(1e-1))).double())
-        dtb = torch.log(torch.expm1(dt)).float()
-        A = -torch.arange(1, N + 1, dtype=torch.float32).repeat(4 * D, 1)
-    else:
-        dtw = rnd(f"sw{tag}", (4, D, R), 0.5, 1.5) / R
-        dtb = torch.full((4, D), float(np.log(np.expm1(1e-3))))
-        A = -rnd(f"sa{tag}", (4 * D, N), 0.05, 1.0)
-        spike = rnd(f"sx{tag}", (B, 4, 1, L), 0, 1)
-        amp = torch.where(rnd(f"sy{tag}", (B, 4, 1, L)) > 0, 40.0, -40.0)
-        proj[:, :, :R] = torch.where(spike < 0.01, amp, proj[:, :, :R] * 0.5)
-    return x, proj, dtw, dtb, A, Ds
-
-
-def run_scan(dev, x, proj, dtw, dtb, A, Ds, ids, B, L, D, N, R, chunk):
-    """The device scan on planar inputs: (y (B, 4, L, D) in pixel order, ysum (B, 4, DB, nchunk, 64), nchunk)."""
-    J = R + 2 * N
-    xT = x.transpose(1, 2).contiguous().to(dev)                                             # (B,L,D)
-    pT = proj.reshape(B, 4 * J, L).transpose(1, 2).contiguous().to(dev)                     # (B,L,4J)
-    nchunk, DB = -(-L // chunk), -(-D // 64)
-    yT = torch.full((B, 4, L, D), float("nan"), device=dev)
-    state = torch.empty(2 * B * 4 * DB * nchunk * N * 64, device=dev)
-    sdt = torch.empty(B * 4 * DB * nchunk * 64, device=dev)
-    ysum = torch.empty(B * 4 * DB * nchunk * 64, device=dev)
-    ops.selective_scan(xT, pT, ids.int().to(dev), dtw.to(dev), dtb.to(dev), A.to(dev), Ds.to(dev), yT, state, sdt, ysum,
-                       B, L, D, N, R, chunk)
-    return yT, ysum.view(B, 4, DB, nchunk, 64), nchunk
-
-
-def ysum_floor(chunk, nchunk, mabs):
-    """Worst-case rounding of the device's chunk sums of y divided by L (sequential fp32 sums of `chunk` steps, then
-    16 interleaved partial sums over the chunks), given mabs = max over channels of mean|y|: inherent to an fp32 sum,
-    about 1e-5 relative at chunk 176 - a chunk missing from the sum moves the mean by 1 / nchunk."""
-    return (chunk + nchunk // 16 + 16) * 2.0 ** -24 * mabs
-
-
-def check_scan_f64(tag, x, proj, dtw, dtb, A, Ds, ids, inv, got, ysum, B, L, D, N, R, chunk):
-    """got (B, 4, D, L) pixel order, ysum (B, 4, DB, nchunk, 64) from the device, against the float64 restatement on
-    the scan_lanes(D) channels; yardstick: the fp32 oracle (mair_ref.selective_scan) on the same channels."""
-    ch = scan_lanes(D)
-    d = len(ch)
-    xs = torch.stack([x[:, ch].index_select(-1, ids[k]) for k in range(4)], 1)              # (B,4,d,L) scan order
-    pg = torch.stack([proj[:, k].index_select(-1, ids[k]) for k in range(4)], 1)            # (B,4,J,L)
-    w_c, b_c, A_c, D_c = dtw[:, ch], dtb[:, ch], A.view(4, D, N)[:, ch], Ds.view(4, D)[:, ch]
-    y64 = selective_scan_f64(xs, torch.einsum("bkrl,kdr->bkdl", pg[:, :, :R].double(), w_c.double()), b_c, A_c,
-                             pg[:, :, R:R + N], pg[:, :, R + N:], D_c)
-    dts = torch.einsum("bkrl,kdr->bkdl", pg[:, :, :R], w_c)
-    y32 = mair_ref.selective_scan(xs.reshape(B, -1, L), dts.reshape(B, -1, L), A_c.reshape(-1, N), pg[:, :, R:R + N],
-                                  pg[:, :, R + N:], D_c.reshape(-1), delta_bias=b_c.reshape(-1),
-                                  delta_softplus=True).view(B, 4, d, L)
-    y64 = torch.stack([y64[:, k].index_select(-1, inv[k]) for k in range(4)], 1)            # pixel order
-    y32 = torch.stack([y32[:, k].index_select(-1, inv[k]) for k in range(4)], 1)
-    g = got[:, :, ch].double()
-    ymax = float(y64.abs().max())
-    e_dev, e_32 = float((g - y64).abs().max()), float((y32.double() - y64).abs().max())
-    m64 = y64.mean(-1)
-    s = ysum.cpu().double().sum(3).reshape(B, 4, -1)[:, :, ch] / L
-    m_dev, m_32 = float((s - m64).abs().max()), float((y32.double().mean(-1) - m64).abs().max())
-    floor = ysum_floor(chunk, ysum.shape[3], float(y64.abs().mean(-1).max()))
-    print(f"scan {tag}: y e_dev {e_dev:.3e} e_32 {e_32:.3e} ratio {e_dev / e_32:.2f} (|y64| {ymax:.3g}); "
-          f"mean e_dev {m_dev:.3e} e_32 {m_32:.3e} fp32-sum floor {floor:.3e}")
-    assert e_dev <= SCAN_K * e_32 + SCAN_F * ymax, "scan output vs float64"
-    assert m_dev <= SCAN_K * m_32 + floor, "chunk-summed ysum / L vs float64 mean"
 
 
 @pytest.mark.parametrize("B,D,N,R,H,W,chunk", [(1, 96, 4, 3, 16, 24, 64), (2, 192, 8, 6, 8, 16, 32), (1, 384, 16, 12, 8, 8, 32),
@@ -163,25 +51,16 @@ def test_selective_scan_vs_oracle(dev, B, D, N, R, H, W, chunk):
     y = mair_ref.selective_scan(xs.reshape(B, -1, L), dts.reshape(B, -1, L), A, pg[:, :, R:R + N], pg[:, :, R + N:],
                                 Ds, delta_bias=dtb.reshape(-1), delta_softplus=True).view(B, 4, D, L)
     y_img = torch.stack([y[:, k].index_select(-1, inv[k]) for k in range(4)], 1)            # (B,4,D,L) pixel order
-    # device
-    xT = x.transpose(1, 2).contiguous().to(dev)                                             # (B,L,D)
-    pT = proj.reshape(B, 4 * J, L).transpose(1, 2).contiguous().to(dev)                     # (B,L,4J)
-    nchunk, DB = -(-L // chunk), -(-D // 64)
-    yT = torch.full((B, 4, L, D), float("nan"), device=dev)
-    state = torch.empty(2 * B * 4 * DB * nchunk * N * 64, device=dev)
-    sdt = torch.empty(B * 4 * DB * nchunk * 64, device=dev)
-    ysum = torch.empty(B * 4 * DB * nchunk * 64, device=dev)
-    ops.selective_scan(xT, pT, ids.int().to(dev), dtw.to(dev), dtb.to(dev), A.to(dev), Ds.to(dev), yT, state, sdt, ysum,
-                       B, L, D, N, R, chunk)
+    yT, ysum, _ = run_scan(dev, x, proj, dtw, dtb, A, Ds, ids, B, L, D, N, R, chunk)
     got = yT.cpu().permute(0, 1, 3, 2)                                                       # (B,4,D,L)
     err = float((got - y_img).abs().max())
     print(f"scan D{D} N{N} L{L} chunk{chunk}: max-abs vs oracle {err:.3e} (|y| max {float(y_img.abs().max()):.2f})")
     assert err <= 2e-4 * max(1.0, float(y_img.abs().max()))
     # per-chunk sums of y feed the ShuffleAttn mean
-    s = ysum.cpu().view(B, 4, DB, nchunk, 64).sum(3).reshape(B, 4, DB * 64)[:, :, :D]
+    s = ysum.cpu().sum(3).reshape(B, 4, -1)[:, :, :D]
     assert (s / L - y_img.mean(-1)).abs().max() <= 1e-4 * max(1.0, float(y_img.abs().max()))
     check_scan_f64(f"D{D} N{N} L{L} chunk{chunk}", x, proj, dtw, dtb.reshape(4, D), A, Ds, ids, inv, got,
-                   ysum.cpu().view(B, 4, DB, nchunk, 64), B, L, D, N, R, chunk)
+                   ysum.cpu(), B, L, D, N, R, chunk)
 
 
 @pytest.mark.parametrize("regime", ["synthetic", "trained", "memory"])
@@ -304,10 +183,6 @@ def test_mairunet_batch_and_determinism(dev):
     y1, y2 = model(x).clone(), model(x).clone()
     assert torch.equal(y1, y2)
     assert (model(x[1:2]) - y1[1:2]).abs().max() <= 5e-5
-
-
-FLAT_CFG = dict(upscale=1, in_chans=3, img_range=1., d_state=16, depths=[2, 2], embed_dim=180, ssm_ratio=1.3, mlp_ratio=2.0,
-                upsampler=None, resi_connection='1conv', img_size=16, dynamic_ids=False, batch_size=1, scan_len=4)
 
 
 @pytest.mark.parametrize("h,w", [(16, 16), (24, 20)])

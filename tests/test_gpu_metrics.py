@@ -7,24 +7,10 @@ import numpy as np
 import pytest
 import torch
 
+from frame_checks import metric_parity, up16
 from irm_amd import dncnn, harness, synth, utils
 
 pytestmark = pytest.mark.gpu
-
-
-def _up(x: np.ndarray, dev) -> torch.Tensor:
-    """numpy uint8 / uint16 frame -> device tensor (uint16 through its int16 bits, then viewed back)."""
-    if x.dtype == np.uint16:
-        return torch.from_numpy(np.ascontiguousarray(x.view(np.int16))).to(dev).view(torch.uint16)
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-
-
-def _parity(pred: np.ndarray, tgt: np.ndarray, dev, data_range=None):
-    ph, sh = utils.calculate_metrics(pred, tgt, data_range)
-    pd, sd = utils.calculate_metrics_device(_up(pred, dev), _up(tgt, dev), data_range)
-    assert abs(sd - sh) <= 1e-9, (pred.shape, sd, sh)
-    assert (pd == ph == float("inf")) or abs(pd - ph) <= 1e-9, (pred.shape, pd, ph)
-    return pd, sd
 
 
 def _perturb(x: np.ndarray, seed: int, amp: int, peak: int = 255) -> np.ndarray:
@@ -36,22 +22,22 @@ def test_random_u8_rgb_720p(dev):
     rng = np.random.default_rng(1)
     a = rng.integers(0, 256, (720, 1280, 3), dtype=np.uint8)
     b = rng.integers(0, 256, (720, 1280, 3), dtype=np.uint8)
-    _parity(a, b, dev)
-    _parity(a, _perturb(a, 2, 12), dev)
+    metric_parity(a, b, dev)
+    metric_parity(a, _perturb(a, 2, 12), dev)
 
 
 def test_synthetic_pairs_degraded_and_perturbed(dev):
     inp, tgt = synth.synth_image_pair(3, 720, 1280, 3, seed_base=1000, blur=15)
-    _, s_deg = _parity(inp, tgt, dev)
-    _, s_near = _parity(_perturb(tgt, 4, 2), tgt, dev)
+    _, s_deg = metric_parity(inp, tgt, dev)
+    _, s_near = metric_parity(_perturb(tgt, 4, 2), tgt, dev)
     assert 0.0 < s_deg < s_near < 1.0
 
 
 def test_grey_hw1_and_hw(dev):
     inp, tgt = synth.synth_image_pair(5, 300, 421, 1, seed_base=7, blur=9)
     assert inp.shape == (300, 421, 1)
-    p1, s1 = _parity(inp, tgt, dev)
-    p2, s2 = _parity(inp[:, :, 0], tgt[:, :, 0], dev)
+    p1, s1 = metric_parity(inp, tgt, dev)
+    p2, s2 = metric_parity(inp[:, :, 0], tgt[:, :, 0], dev)
     assert p1 == p2 and s1 == s2
 
 
@@ -60,11 +46,11 @@ def test_u16_rgb(dev):
     rng = np.random.default_rng(6)
     t16 = (tgt.astype(np.uint16) * 257 + rng.integers(0, 257, tgt.shape)).astype(np.uint16)
     p16 = _perturb(t16, 7, 3000, 65535)
-    _parity(p16, t16, dev)
-    _parity(inp.astype(np.uint16) * 257, t16, dev)
+    metric_parity(p16, t16, dev)
+    metric_parity(inp.astype(np.uint16) * 257, t16, dev)
     # the tiler's uint16 frames are int16 tensors: same values, data_range 65535 by default
-    pd, sd = utils.calculate_metrics_device(_up(p16, dev).view(torch.int16), _up(t16, dev).view(torch.int16))
-    assert (pd, sd) == utils.calculate_metrics_device(_up(p16, dev), _up(t16, dev))
+    pd, sd = utils.calculate_metrics_device(up16(p16, dev).view(torch.int16), up16(t16, dev).view(torch.int16))
+    assert (pd, sd) == utils.calculate_metrics_device(up16(p16, dev), up16(t16, dev))
 
 
 @pytest.mark.parametrize("h,w,c", [(7, 7, 3), (7, 7, 1), (7, 300, 3), (7, 300, 1), (13, 1001, 3), (719, 1279, 3),
@@ -72,18 +58,18 @@ def test_u16_rgb(dev):
 def test_awkward_sizes(dev, h, w, c):
     rng = np.random.default_rng(h * 10007 + w * 3 + c)
     t = rng.integers(0, 256, (h, w, c), dtype=np.uint8)
-    _parity(_perturb(t, h + w, 40), t, dev)
+    metric_parity(_perturb(t, h + w, 40), t, dev)
 
 
 def test_custom_data_range(dev):
     rng = np.random.default_rng(11)
     t = rng.integers(0, 256, (64, 90, 3), dtype=np.uint8)
-    _parity(_perturb(t, 12, 9), t, dev, data_range=200)
+    metric_parity(_perturb(t, 12, 9), t, dev, data_range=200)
 
 
 def test_identical_frames_exact(dev):
     _, tgt = synth.synth_image_pair(2, 97, 203, 3, seed_base=3, blur=5)
-    d = _up(tgt, dev)
+    d = up16(tgt, dev)
     sse, ssim = utils.frame_metrics_device([d], [d.clone()])
     assert int(sse[0]) == 0 and float(ssim[0]) == 1.0
     assert utils.calculate_metrics_device(d, d.clone()) == (float("inf"), 1.0)
@@ -92,16 +78,16 @@ def test_identical_frames_exact(dev):
 def test_constant_frames_finite_and_match_host(dev):
     for a, b in ((0, 0), (255, 255), (17, 200), (0, 255)):
         x, y = np.full((31, 45, 3), a, np.uint8), np.full((31, 45, 3), b, np.uint8)
-        pd, sd = _parity(x, y, dev)
+        pd, sd = metric_parity(x, y, dev)
         assert np.isfinite(sd)
     x16 = np.full((20, 20, 1), 65535, np.uint16)
-    _parity(x16, np.full_like(x16, 1), dev)
+    metric_parity(x16, np.full_like(x16, 1), dev)
 
 
 def test_batch_equals_single_calls_bitwise_and_repeats(dev):
     frames = [synth.synth_image_pair(i, 181, 257, 3, seed_base=50, blur=11) for i in range(4)]
-    preds = [_up(i, dev) for i, _ in frames]
-    tgts = [_up(t, dev) for _, t in frames]
+    preds = [up16(i, dev) for i, _ in frames]
+    tgts = [up16(t, dev) for _, t in frames]
     sse_b, ssim_b = utils.frame_metrics_device(preds, tgts)
     assert sse_b.dtype == torch.int64 and ssim_b.dtype == torch.float64 and tuple(sse_b.shape) == (4,)
     for k in range(4):
@@ -141,7 +127,7 @@ def test_harness_device_prediction_is_the_host_prediction(dev):
     pred, _ = utils.get_model_prediction(model, inp, dev, **cfg)
     pred2, ms, out_dev = utils._get_model_prediction(model, inp, dev, **cfg)
     assert ms > 0 and np.array_equal(pred, pred2) and np.array_equal(out_dev.cpu().numpy(), pred)
-    assert utils.calculate_metrics_device(out_dev, _up(tgt, dev)) == pytest.approx(utils.calculate_metrics(pred, tgt),
+    assert utils.calculate_metrics_device(out_dev, up16(tgt, dev)) == pytest.approx(utils.calculate_metrics(pred, tgt),
                                                                                    abs=1e-9)
 
 

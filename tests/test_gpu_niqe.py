@@ -8,15 +8,14 @@ import numpy as np
 import pytest
 import torch
 
+from frame_checks import NIQE_MARGIN as MARGIN
+from frame_checks import check_against_host, up
 from irm_amd import _hip, dncnn, harness, utils
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ("synth_crop0", "synth_crop4", "noise", "grey", "u16")
-#: margin on the distances recorded in niqe.json (host_vs_reference by the generator, device_vs_host by its
-#: --device-bound run on an MI355X)
-MARGIN = 4.0
 
 
 @pytest.fixture(scope="module")
@@ -30,30 +29,8 @@ def params():
     return utils.load_niqe_params(os.path.join(GOLDEN, "niqe_pris_params.npz"))
 
 
-def up(a: np.ndarray, dev) -> torch.Tensor:
-    """A uint8 / uint16 host frame on the GPU (uint16 as its int16 bit pattern)."""
-    return torch.from_numpy(np.ascontiguousarray(a.view(np.int16) if a.dtype == np.uint16 else a)).to(dev)
-
-
 def bits(t: torch.Tensor) -> np.ndarray:
     return t.cpu().numpy().view(np.int64)
-
-
-def check_against_host(dev_feat, frame, crop, params, meta, what, order="bgr"):
-    """alpha: equal, or one grid step apart in at most one entry of the frame; the other features and the score within
-    4 x the distance measured on an MI355X (niqe.json, device_vs_host).  Returns (host score, device score)."""
-    bound = meta["device_vs_host"]
-    host = utils.niqe_features(utils.niqe_plane(frame, crop, "HWC", order), params)
-    differing, steps, rel = utils.niqe_feature_distance(dev_feat, host)
-    hs, ds = utils.niqe_score(host, params), utils.niqe_score(dev_feat, params)
-    srel = abs(ds - hs) / abs(hs)
-    print(f"{what}: alpha differing {differing} (max {steps:.3g} steps), features {rel:.3e}, score {ds:.12f} vs host "
-          f"{hs:.12f} ({srel:.3e})")
-    assert dev_feat.shape == host.shape
-    assert differing <= 1 and steps <= 1.0 + 1e-6
-    assert rel <= MARGIN * bound["features_rel"]
-    assert srel <= MARGIN * bound["score_rel"]
-    return hs, ds
 
 
 @pytest.mark.parametrize("case", CASES)

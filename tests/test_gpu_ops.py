@@ -8,19 +8,17 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import block_model as bm
+import guards
+from block_model import OPS_TOL as TOL
+from block_model import unpack_gemm, unpack_presplit
 from irm_amd import _hip, ops, synth
 
 pytestmark = pytest.mark.gpu
-TOL = 2e-4
 
 
 def rnd(name, shape, lo=-1.0, hi=1.0):
     return synth.uniform(123, name, shape, lo, hi)
-
-
-def unpack_gemm(wp, M, K):
-    mt, ks = (M + 15) // 16, 4 * ((K + 15) // 16)
-    return wp.view(mt, ks, 4, 16).permute(0, 3, 1, 2).reshape(mt * 16, ks * 4)[:M, :K]
 
 
 def test_pack_roundtrip_cpu_side():
@@ -36,8 +34,7 @@ def test_ln_stats(dev, B, C, H, W):
     stats = torch.empty(B, 2, H * W, device=dev)
     ops.ln_stats(x, stats, 1e-5)
     xr = big[:, 2:2 + C].double()
-    mean = xr.mean(1).reshape(B, -1)
-    rstd = 1.0 / torch.sqrt(xr.var(1, unbiased=False) + 1e-5).reshape(B, -1)
+    mean, rstd = (s.reshape(B, -1) for s in bm.ln_stats(xr))
     s = stats.cpu().double()
     assert (s[:, 0] - mean).abs().max() < 1e-5
     assert ((s[:, 1] - rstd).abs() / rstd).max() < 1e-5
@@ -75,25 +72,10 @@ def test_gemm1x1(dev, M, K, H, W, B, ln, res, bias, act, ct, yg):
     bv = rnd(tag + "b", (M,)) if bias else None
     lnw = rnd(tag + "lw", (K,), 0.5, 1.5)
     lnb = rnd(tag + "lb", (K,), -0.2, 0.2)
-    xd = x.double()
-    if ln:
-        mu = xd.mean(1, keepdim=True)
-        var = xd.var(1, unbiased=False, keepdim=True)
-        if ln == 1:
-            xn = (xd - mu) / torch.sqrt(var + 1e-5) * lnw.double().view(1, -1, 1, 1) + lnb.double().view(1, -1, 1, 1)
-        else:
-            xn = xd / torch.sqrt(var + 1e-5) * lnw.double().view(1, -1, 1, 1)
-    else:
-        xn = xd
-    ref = torch.einsum("mk,bkhw->bmhw", w.double(), xn)
+    ref = torch.einsum("mk,bkhw->bmhw", w.double(), bm.layer_norm(x.double(), lnw, lnb, ln))
     if bias:
         ref = ref + bv.double().view(1, -1, 1, 1)
-    if act == 1:
-        ref = torch.relu(ref)
-    elif act == 2:
-        ref = F.gelu(ref)
-    elif act == 3:
-        ref = F.silu(ref)
+    ref = bm.act(ref, act)
     if res:
         ref = ref + r.double()
 
@@ -121,8 +103,7 @@ def test_gemm1x1_fused_output_statistics(dev, M, K, H, W, B, res):
     x = rnd(tag + "x", (B, K, H, W), -1.5, 2.0)
     r = rnd(tag + "r", (B, M, H, W), -3, 3) if res else None
     ref = torch.einsum("mk,bkhw->bmhw", w.double(), x.double()) + (r.double() if res else 0)
-    mean = ref.mean(1).reshape(B, -1)
-    rstd = 1.0 / torch.sqrt(ref.var(1, unbiased=False) + 1e-5).reshape(B, -1)
+    mean, rstd = (s.reshape(B, -1) for s in bm.ln_stats(ref))
     y = torch.empty(B, M, H, W, device=dev)
     st = torch.full((B, 2, H * W), float("nan"), device=dev)
     ops.gemm1x1(_hip.pack_gemm_weight(w).to(dev), x.to(dev), y, M, K, res=r.to(dev) if res else None, stats_out=st)
@@ -184,16 +165,7 @@ def test_gemm1x1_f16x3(dev, M, K, H, W, B, ln, bias, ct):
     w = rnd(f"sw{M}{K}", (M, K), -0.3, 0.3)
     lnw, lnb = rnd(f"slw{K}", (K,), 0.5, 1.5), rnd(f"slb{K}", (K,), -0.2, 0.2)
     bv = rnd(f"sb{M}", (M,), -0.3, 0.3) if bias else None
-    xd = x.double()
-    if ln:
-        mu, var = xd.mean(1, keepdim=True), xd.var(1, unbiased=False, keepdim=True)
-        xn = (xd - mu) / torch.sqrt(var + 1e-5) * lnw.double().view(1, K, 1, 1) if ln == 1 else \
-            xd / torch.sqrt(var + 1e-5) * lnw.double().view(1, K, 1, 1)
-        if ln == 1:
-            xn = xn + lnb.double().view(1, K, 1, 1)
-    else:
-        xn = xd
-    ref = torch.einsum("mk,bkhw->bmhw", w.double(), xn)
+    ref = torch.einsum("mk,bkhw->bmhw", w.double(), bm.layer_norm(x.double(), lnw, lnb, ln))
     if bias:
         ref = ref + bv.double().view(1, M, 1, 1)
     xg = x.to(dev)
@@ -211,20 +183,6 @@ def test_gemm1x1_f16x3(dev, M, K, H, W, B, ln, bias, ct):
     assert e16 < 2e-5 and e16 < 8 * max(e32, 1e-7)
 
 
-def _ln_ref(xd, lnw, lnb, ln):
-    K = xd.shape[1]
-    mu, var = xd.mean(1, keepdim=True), xd.var(1, unbiased=False, keepdim=True)
-    xn = ((xd - mu) if ln == 1 else xd) / torch.sqrt(var + 1e-5) * lnw.double().view(1, K, 1, 1)
-    return xn + lnb.double().view(1, K, 1, 1) if ln == 1 else xn
-
-
-def _unpack_presplit(frag, M, K):
-    """fp64 value of the hi + lo fragments written by the host packer / irm_ln_split_f16: [rows][K]."""
-    h = frag.view(torch.float16).double().view(-1, K // 32, 2, 4, 16, 8)      # [tile][ks][hi|lo][g][m][e]
-    v = (h[:, :, 0] + h[:, :, 1]).permute(0, 3, 1, 2, 4).reshape(-1, K)        # [tile][m][ks][g][e]
-    return v[:M]
-
-
 @pytest.mark.parametrize("K,H,W,B,ln,amp", [(192, 16, 16, 2, 1, 1.0), (192, 16, 32, 1, 2, 1.0), (384, 8, 16, 3, 1, 1.0),
                                             (384, 16, 8, 1, 2, 1e-4), (192, 16, 16, 1, 1, 3e4)])
 def test_ln_split(dev, K, H, W, B, ln, amp):
@@ -239,8 +197,8 @@ def test_ln_split(dev, K, H, W, B, ln, amp):
     xs = torch.full((B * K * N + 64,), float("nan"), device=dev)
     ops.ln_split(x, xs, lnw.to(dev), lnb.to(dev) if ln == 1 else None, ln, s_x)
     assert torch.isnan(xs[B * K * N:]).all()                                   # nothing written past the image
-    got = _unpack_presplit(xs[:B * K * N].cpu(), B * N, K).view(B, N, K).permute(0, 2, 1).reshape(B, K, H, W) / s_x
-    ref = _ln_ref(big[:, 2:2 + K].double(), lnw, lnb, ln)
+    got = unpack_presplit(xs[:B * K * N].cpu(), B * N, K).view(B, N, K).permute(0, 2, 1).reshape(B, K, H, W) / s_x
+    ref = bm.layer_norm(big[:, 2:2 + K].double(), lnw, lnb, ln)
     err = float((got - ref).abs().max())
     scale = float(ref.abs().max())
     print(f"ln_split K{K} ln{ln} amp{amp:g}: s_x {s_x:g}  |ref|max {scale:.3e}  max-abs {err:.3e}")
@@ -268,12 +226,12 @@ def test_gemm_presplit(dev, M, K, H, W, B, ln, bias, ct, mgroups, wg_shape):
     lnw = rnd(f"plw{K}", (K,), 0.5, 1.5)
     lnb = rnd(f"plb{K}", (K,), -0.2, 0.2) if ln == 1 else None
     bv = rnd(f"pb{M}", (M,), -0.3, 0.3) if bias else None
-    ref = torch.einsum("mk,bkhw->bmhw", w.double(), _ln_ref(x.double(), lnw, lnb, ln))
+    ref = torch.einsum("mk,bkhw->bmhw", w.double(), bm.layer_norm(x.double(), lnw, lnb, ln))
     if bias:
         ref = ref + bv.double().view(1, M, 1, 1)
     xg = x.to(dev)
     frag, s_w = _hip.pack_gemm_weight_presplit(w.to(dev))
-    assert float((_unpack_presplit(frag.cpu(), M, K) / s_w - w.double()).abs().max()) <= 2.0 ** -21 * float(w.abs().max())
+    assert float((unpack_presplit(frag.cpu(), M, K) / s_w - w.double()).abs().max()) <= 2.0 ** -21 * float(w.abs().max())
     s_x = _hip.ln_split_scale(lnw, lnb, K, ln == 1)
     xs = torch.empty(B * K * N, device=dev)
     ops.ln_split(xg, xs, lnw.to(dev), lnb.to(dev) if ln == 1 else None, ln, s_x)
@@ -312,7 +270,7 @@ def test_ln_gemm_presplit_fused(dev, M, H, W, B, ln, bias):
     lnb_c = rnd(f"lflb{M}", (K,), -0.2, 0.2) if ln == 1 else None
     bv_c = rnd(f"lfb{M}", (M,), -0.3, 0.3) if bias else None
     lnw, lnb, bv = lnw_c.to(dev), None if lnb_c is None else lnb_c.to(dev), None if bv_c is None else bv_c.to(dev)
-    ref = torch.einsum("mk,bkhw->bmhw", w.double(), _ln_ref(big[:, 1:1 + K].double(), lnw_c, lnb_c, ln))
+    ref = torch.einsum("mk,bkhw->bmhw", w.double(), bm.layer_norm(big[:, 1:1 + K].double(), lnw_c, lnb_c, ln))
     if bias:
         ref = ref + bv_c.double().view(1, M, 1, 1)
     frag, s_w = _hip.pack_gemm_weight_presplit(w.to(dev))
@@ -349,7 +307,7 @@ def test_gemm_presplit_trained_like(dev):
             w = sign * torch.exp(rnd(tag + "w", (M, K), np.log(1e-5), np.log(10.0)))
             lnw = torch.exp(rnd(tag + "lw", (K,), np.log(0.1), np.log(30.0)))
             lnb = rnd(tag + "lb", (K,), -2.0, 2.0) if ln == 1 else None
-            ref = torch.einsum("mk,bkhw->bmhw", w.double(), _ln_ref(x.double(), lnw, lnb, ln))
+            ref = torch.einsum("mk,bkhw->bmhw", w.double(), bm.layer_norm(x.double(), lnw, lnb, ln))
             xg = x.to(dev)
             frag, s_w = _hip.pack_gemm_weight_presplit(w.to(dev))
             s_x = _hip.ln_split_scale(lnw, lnb, K, ln == 1)
@@ -444,9 +402,8 @@ def test_mdta_fold(dev, B, C, heads, H, W):
     qkv = rnd(f"md{C}{heads}{H}", (B, 3 * C, H, W))
     temp = rnd(f"mdt{C}{heads}", (heads,), 2.0, 6.0)
     wout = rnd(f"mdw{C}", (C, C), -0.3, 0.3)
-    q, k, v = qkv.double().reshape(B, 3, heads, c, N).unbind(1)
-    qn, kn = F.normalize(q, dim=-1), F.normalize(k, dim=-1)
-    attn = torch.softmax(qn @ kn.transpose(-1, -2) * temp.double().view(1, heads, 1, 1), dim=-1)
+    v = qkv[:, 2 * C:].double().reshape(B, heads, c, N)
+    attn = bm.attention_qk(qkv[:, :2 * C].double(), temp, heads)
     ref = torch.einsum("oc,bcn->bon", wout.double(), (attn @ v).reshape(B, C, N)).reshape(B, C, H, W)
 
     chunk, nchunk, rec = ops.mdta_plan(B, C, heads, N)
@@ -496,18 +453,13 @@ def test_mdta_gram_f16x3(dev, B, C, heads, H, W, span):
     wout = rnd(f"gw{C}", (C, C), -0.3, 0.3)
     q, k, _ = qkv.double().reshape(B, 3, heads, c, N).unbind(1)
     G = q @ k.transpose(-1, -2)
-    attn = torch.softmax(F.normalize(q, dim=-1) @ F.normalize(k, dim=-1).transpose(-1, -2)
-                         * temp.double().view(1, heads, 1, 1), dim=-1)
+    attn = bm.attention(q.reshape(B, C, N), k.reshape(B, C, N), temp, heads)
     chunk, nchunk, rec = ops.mdta_plan(B, C, heads, N)
     qg = qkv.to(dev)
     outs = []
     for sc in (None, scale.to(dev)):
-        part = torch.full((B * heads * nchunk * rec,), float("nan"), device=dev)
-        gsum = torch.empty(B * heads * rec, device=dev)
-        mfold = torch.zeros(B * ops.mfold_numel(C), device=dev)
-        attn_out = torch.empty(B, heads, c, c, device=dev)
-        ops.mdta_fold(qg, part, gsum, temp.to(dev), wout.to(dev), mfold, C, heads, attn=attn_out, gram_scale=sc)
-        outs.append((gsum.cpu().double().view(B, heads, rec), attn_out.cpu().double()))
+        attn_out, _, gsum = bm.run_mdta_fold(dev, qg, temp, wout, C, heads, gram_scale=sc)
+        outs.append((gsum.double().view(B, heads, rec), attn_out.double()))
     gref = torch.cat([G.reshape(B, heads, c * c), (q * q).sum(-1), (k * k).sum(-1)], -1)
     mag = gref.abs().max()
     e32, e16 = (outs[0][0] - gref).abs().max() / mag, (outs[1][0] - gref).abs().max() / mag
@@ -540,19 +492,8 @@ def test_conv3x3(dev, ci, co, H, W, B, bias, relu1, res_mode, relu2, store):
     x = rnd(tag + "x", (B, ci, H, W))
     w = rnd(tag + "w", (co, ci, 3, 3), -0.2, 0.2)
     bv = rnd(tag + "b", (co,)) if bias else None
-    ref = F.conv2d(x.double(), w.double(), bv.double() if bias else None, padding=1)
-    if relu1:
-        ref = torch.relu(ref)
-    r = None
-    if res_mode:
-        r = rnd(tag + "r", (B, co, H, W))
-        ref = ref + r.double() if res_mode == 1 else r.double() - ref
-    if relu2:
-        ref = torch.relu(ref)
-    if store == 1:
-        ref = F.pixel_unshuffle(ref, 2)
-    elif store == 2:
-        ref = F.pixel_shuffle(ref, 2)
+    r = rnd(tag + "r", (B, co, H, W)) if res_mode else None
+    ref = bm.conv_epilogue(F.conv2d(x.double(), w.double(), bv.double() if bias else None, padding=1), r, relu1, res_mode, relu2, store)
     ybig = torch.full((B, ref.shape[1] + 2, ref.shape[2], ref.shape[3]), 5.0, device=dev)
     y = ybig[:, 1:1 + ref.shape[1]]
     ops.conv3x3(_hip.pack_conv3x3_weight(w).to(dev), x.to(dev), y, ci, co, bias=bv.to(dev) if bias else None,
@@ -609,19 +550,8 @@ def test_conv3x3_f16x3(dev, ci, co, H, W, B, bias, relu1, res_mode, relu2, store
     bv = rnd(tag + "b", (co,)) if bias else None
     oc, oh, ow = (co, H, W) if store_mode == 0 else (co * 4, H // 2, W // 2) if store_mode == 1 else (co // 4, 2 * H, 2 * W)
     r = rnd(tag + "r", (B, oc, oh, ow)) if res_mode else None
-    ref = F.conv2d(x.double(), w.double(), None if bv is None else bv.double(), padding=1)
-    if relu1:
-        ref = F.relu(ref)
-    if res_mode == 1:
-        ref = ref + r.double()
-    elif res_mode == 2:
-        ref = r.double() - ref
-    if relu2:
-        ref = F.relu(ref)
-    if store_mode == 1:
-        ref = F.pixel_unshuffle(ref, 2)
-    elif store_mode == 2:
-        ref = F.pixel_shuffle(ref, 2)
+    ref = bm.conv_epilogue(F.conv2d(x.double(), w.double(), None if bv is None else bv.double(), padding=1), r, relu1, res_mode, relu2,
+                           store_mode)
     xd = x.to(dev)
     kw = dict(bias=None if bv is None else bv.to(dev), relu1=relu1, res=None if r is None else r.to(dev), res_mode=res_mode,
               relu2=relu2, store_mode=store_mode)
@@ -660,17 +590,7 @@ def test_conv3x3_thin(dev, ci, co, H, W, B, bias, relu1, res_mode, relu2):
     x = rnd(tag + "x", (B, ci, H, W), -1.5, 2.0)
     bv = rnd(tag + "b", (co,)) if bias else None
     r = rnd(tag + "r", (B, co, H, W)) if res_mode else None
-    ref = F.conv2d(x.double(), w.double(), None if bv is None else bv.double(), padding=1)
-    if relu1:
-        ref = F.relu(ref)
-    if res_mode == 1:
-        ref = ref + r.double()
-    elif res_mode == 2:
-        ref = r.double() - ref
-    elif res_mode == 3:
-        ref = torch.clamp(torch.tanh(ref) + r.double(), -1, 1)
-    if relu2:
-        ref = F.relu(ref)
+    ref = bm.conv_epilogue(F.conv2d(x.double(), w.double(), None if bv is None else bv.double(), padding=1), r, relu1, res_mode, relu2)
     cw = _hip.pack_conv3x3(w.to(dev))
     assert cw.raw is not None
     ybig = torch.full((B, co + 2, H, W), 5.0, device=dev)
@@ -711,16 +631,6 @@ def test_kernel_timer_only_times_the_selected_group(dev):
 
 
 # --------------------------------------------------------------------------- no writes outside the output
-def _guarded(dev, shape, pad=1 << 14):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * pad,), 12345.0, device=dev)
-    return buf, buf[pad:pad + n].view(*shape), pad
-
-
-def _intact(buf, n, pad):
-    return bool((buf[:pad] == 12345.0).all()) and bool((buf[pad + n:] == 12345.0).all())
-
-
 @pytest.mark.parametrize("C,H,W", [(48, 64, 96), (96, 40, 56), (192, 32, 32), (384, 16, 24), (96, 9, 15)])
 def test_no_write_outside_the_output(dev, C, H, W):
     """Every kernel of a TransformerBlock and the dense convs write into the middle of a sentinel-filled buffer: the
@@ -731,10 +641,10 @@ def test_no_write_outside_the_output(dev, C, H, W):
     checks = []
 
     def run(name, shape, fn):
-        buf, y, pad = _guarded(dev, shape)
+        buf, y = guards.sentinel_out(shape, dev, pad=1 << 14)
         fn(y)
         torch.cuda.synchronize()
-        checks.append((name, _intact(buf, y.numel(), pad)))
+        checks.append((name, guards.intact(buf, y)))
     aligned = W % 4 == 0
     run("ln_stats", (B, 2, H, W), lambda y: ops.ln_stats(X, y))
     st = torch.empty(B, 2, H, W, device=dev)
@@ -764,14 +674,14 @@ def test_no_write_outside_the_output(dev, C, H, W):
     chunk, nchunk, rec = ops.mdta_plan(B, C, heads, H * W)
     sc = torch.full((2 * C,), 1024.0, device=dev)
     for gs in (None, sc):
-        bp, part, p1 = _guarded(dev, (B * heads * nchunk * rec,))
-        bg, gsum, p2 = _guarded(dev, (B * heads * rec,))
-        bm, mf, p3 = _guarded(dev, (B * ops.mfold_numel(C),))
+        bp, part = guards.sentinel_out((B * heads * nchunk * rec,), dev, pad=1 << 14)
+        bg, gsum = guards.sentinel_out((B * heads * rec,), dev, pad=1 << 14)
+        bf, mf = guards.sentinel_out((B * ops.mfold_numel(C),), dev, pad=1 << 14)
         mf.zero_()
         ops.mdta_fold(QKV, part, gsum, temp, wout, mf, C, heads, split=aligned, gram_scale=gs)
         torch.cuda.synchronize()
-        checks.append((f"mdta f16x3={gs is not None}", _intact(bp, part.numel(), p1) and _intact(bg, gsum.numel(), p2)
-                       and _intact(bm, mf.numel(), p3)))
+        checks.append((f"mdta f16x3={gs is not None}", guards.intact(bp, part) and guards.intact(bg, gsum)
+                       and guards.intact(bf, mf)))
     if C <= 96 and aligned:
         pk = _hip.pack_gdfn_fused(rnd("fa", (2 * hid, C), -.3, .3).to(dev), None, rnd("fb", (2 * hid, 9), -.4, .4), None,
                                   rnd("fc", (C, hid), -.3, .3), rnd("fd", (C,), .5, 1.5), rnd("fe", (C,), -.2, .2))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from frame_checks import check_quantised, check_resize, down, quantise_ref, up
 from irm_amd import _hip, harness, mair, synth, utils
 
 pytestmark = pytest.mark.gpu
@@ -23,49 +24,6 @@ SCALE = {"down2": 0.5, "down3": 1.0 / 3.0, "down4": 0.25, "up2": 2, "up3": 3, "u
 def meta():
     with open(os.path.join(GOLDEN, "sr_protocol.json")) as f:
         return json.load(f)
-
-
-def up(a: np.ndarray, dev) -> torch.Tensor:
-    """A uint8 / uint16 host frame on the GPU (uint16 as its int16 bit pattern)."""
-    return torch.from_numpy(np.ascontiguousarray(a.view(np.int16) if a.dtype == np.uint16 else a)).to(dev)
-
-
-def down(t: torch.Tensor, dtype=None) -> np.ndarray:
-    a = t.cpu().numpy()
-    return a.view(np.uint16) if dtype == np.uint16 else a
-
-
-def quantise_ref(x32):
-    return (np.clip(x32, np.float32(0), np.float32(1)) * 255.0).round().astype(np.uint8)
-
-
-def check_quantised(got, ref, what):
-    """Every value within 1 of the reference's, differing values at most 1e-3 of the frame for bytes.  Where that share
-    comes from: two results that agree to 1e-6 before rounding (the float bound below) round differently only when
-    one lies within 1e-6 of a rounding boundary, i.e. for at most 2 x 1e-6 x R of uniformly placed values: 5.1e-4
-    for R = 255, under the 1e-3 of the byte rule.  uint16 steps are 257 times finer, so the same reasoning gives
-    2 x 1e-6 x 65535 = 0.131 there (the values still within 1)."""
-    diff = np.abs(got.astype(np.int64) - ref.astype(np.int64))
-    share = float((diff > 0).mean())
-    limit = 1e-3 if got.dtype == np.uint8 else 2 * 1e-6 * 65535
-    print(f"{what}: max difference {int(diff.max())}, differing share {share:.2e} ({int((diff > 0).sum())} of {diff.size})")
-    assert got.shape == ref.shape and got.dtype == ref.dtype
-    assert int(diff.max()) <= 1 and share <= limit
-
-
-def check_resize(src, scale, dev, what):
-    """Device float output within 1e-6 of imresize_host (an fp32 chain of at most 18 taps on values in [0, 1]), the
-    quantised output by the byte rule; returns the device float result."""
-    want = utils.imresize_host(src, scale)
-    got = utils.imresize_device(up(src, dev), scale, out="float")
-    assert got.dtype == torch.float32 and tuple(got.shape) == want.shape
-    got = got.cpu().numpy()
-    err = float(np.abs(got.astype(np.float64) - want).max())
-    print(f"{what}: {src.shape} {src.dtype} -> {got.shape}, device fp32 vs float64 host max-abs {err:.3e}")
-    assert err <= 1e-6
-    q = utils.imresize_device(up(src, dev), scale, out="same")
-    check_quantised(down(q, src.dtype), utils.imresize_host(src, scale, out="same"), what + " quantised")
-    return got
 
 
 # --------------------------------------------------------------------------- 1. resize

@@ -3,8 +3,8 @@ they make must be one the C switches accept, with no workgroup group left withou
 import pytest
 
 from irm_amd import ops
-from test_gpu_conv_variants import CASE_STRUCTURES, CONV_VARIANTS, expected_conv_variant, pass_structure, passes_per_group
-from test_gpu_gemm_variants import VARIANTS, expected_variant
+from variant_model import (CASE_STRUCTURES, CONV_VARIANTS, VARIANTS, expected_conv_variant, expected_variant, pass_structure,
+                           passes_per_group)
 
 GEMM_CTS = {3, 4, 6, 8, 9}               # gemm_entry (gemm_pw.hip)
 CONV_CTS = {1, 2, 3, 4, 6}               # irm_conv3x3_f32 (conv3x3.hip)

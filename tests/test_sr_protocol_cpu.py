@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from frame_checks import check_quantised, quantise_ref
 from irm_amd import _hip, harness, utils
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,19 +31,6 @@ def meta():
 def source_of(g, key, name):
     """The uint8 frame a golden resize was made from: the HR frame when shrinking, the reference's LR (1/4) frame."""
     return g[f"hr_{name}"] if key.startswith("down") else g[f"lr4_{name}"]
-
-
-def quantise_ref(x32):
-    """tensor2img on the reference's fp32 result: clamp, x 255 in fp32, round half to even."""
-    return (np.clip(x32, np.float32(0), np.float32(1)) * 255.0).round().astype(np.uint8)
-
-
-def check_quantised(got, ref_u8, what):
-    diff = np.abs(got.astype(np.int32) - ref_u8.astype(np.int32))
-    share = float((diff > 0).mean())
-    print(f"{what}: max byte difference {int(diff.max())}, differing share {share:.2e} ({int((diff > 0).sum())} of {diff.size})")
-    assert got.shape == ref_u8.shape and got.dtype == ref_u8.dtype
-    assert int(diff.max()) <= 1 and share <= 1e-3
 
 
 @pytest.mark.parametrize("name", NAMES)

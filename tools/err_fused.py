@@ -5,13 +5,19 @@ import torch, torch.nn.functional as F
 import irm_amd  # noqa
 from irm_amd import _hip, ops, synth
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-from test_gpu_fused import gdfn_ref, qkv_ref, rnd
+from block_model import gdfn, qkv
+
+
+def rnd(name, shape, lo=-1.0, hi=1.0):
+    return synth.uniform(321, name, shape, lo, hi)
+
+
 dev = torch.device("cuda:0")
 for C, hid, H, W in [(96, 255, 64, 64), (48, 127, 64, 64)]:
     x = rnd("ex", (1, C, H, W), -1.5, 2.0)
     lnw, lnb = rnd("elw", (C,), .5, 1.5), rnd("elb", (C,), -.2, .2)
     pin, pout, dw = rnd("e1", (2 * hid, C), -.3, .3), rnd("e2", (C, hid), -.3, .3), rnd("e3", (2 * hid, 9), -.4, .4)
-    ref = gdfn_ref(x, lnw, lnb, 1, pin, None, dw, None, pout, None)
+    ref = gdfn(x.double(), lnw, lnb, 1, pin, None, dw, None, pout, None)
     pk = _hip.pack_gdfn_fused(pin.to(dev), None, dw, None, pout, lnw, lnb)
     y = torch.empty(1, C, H, W, device=dev)
     ops.gdfn_fused(pk, x.to(dev), y, C, hid, ln_mode=1)
@@ -26,7 +32,7 @@ for C, hid, H, W in [(96, 255, 64, 64), (48, 127, 64, 64)]:
     i = d.argmax(); print("   worst at", [int(v) for v in torch.unravel_index(i, d.shape)])
     M = 3 * C
     w, dq = rnd("e4", (M, C), -.3, .3), rnd("e5", (M, 9), -.4, .4)
-    refq = qkv_ref(x, lnw, lnb, 1, w, None, dq, None)
+    refq = qkv(x.double(), lnw, lnb, 1, w, None, dq, None)
     pkq = _hip.pack_qkv_fused(w.to(dev), None, dq, None, lnw, lnb)
     yq = torch.empty(1, M, H, W, device=dev)
     ops.qkv_dw_fused(pkq, x.to(dev), yq, C, M, ln_mode=1)

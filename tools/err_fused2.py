@@ -4,13 +4,19 @@ import torch, torch.nn.functional as F
 import irm_amd  # noqa
 from irm_amd import _hip, ops, synth
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-from test_gpu_fused import qkv_ref, rnd
+from block_model import qkv
+
+
+def rnd(name, shape, lo=-1.0, hi=1.0):
+    return synth.uniform(321, name, shape, lo, hi)
+
+
 dev = torch.device("cuda:0")
 C, H, W = 96, 64, 64
 M = 3 * C
 x = rnd("ex", (1, C, H, W), -1.5, 2.0)
 def run(tag, w, dq, lnw, lnb):
-    refq = qkv_ref(x, lnw, lnb, 1, w, None, dq, None)
+    refq = qkv(x.double(), lnw, lnb, 1, w, None, dq, None)
     pkq = _hip.pack_qkv_fused(w.to(dev), None, dq, None, lnw, lnb)
     yq = torch.empty(1, M, H, W, device=dev)
     ops.qkv_dw_fused(pkq, x.to(dev), yq, C, M, ln_mode=1)
