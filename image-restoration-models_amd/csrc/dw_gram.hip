@@ -230,9 +230,8 @@ extern "C" int irm_dw_gram_cm_f16x3_f32(const float* qkv, long bs, const float* 
     const long units = (long)B * heads * (tiles / QC_NCH);
     if (units >= (1L << 28)) return IRM_EINVAL;
     IRM_ALLOW_BIG_LDS((&dw_gram_kernel));
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return IRM_ELAUNCH;
+    int n = 0;
+    if (irm_cu_count(n) != IRM_OK) return IRM_ELAUNCH;
     DgArgs a;
     a.qkv = qkv; a.bs = bs; a.taps = taps; a.bias = bias; a.gscale = gscale; a.part = part;
     a.C = C; a.heads = heads; a.H = H; a.W = W;

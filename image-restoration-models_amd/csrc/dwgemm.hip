@@ -23,63 +23,6 @@ struct DwGemmArgs {
     int M, K, H, W, mtiles, ksteps, tiles_x, tiles;
 };
 
-// LayerNorm statistics of the finished output pixels (same contract as irm_stats_from_acc in gemm_pw.hip):
-// lane (g, j) holds channel 16c + j of PT pixel quads; pix[q] < 0 marks a quad outside the image.
-template <int CT, int PT>
-__device__ __forceinline__ void dg_stats(const float4 (&t)[PT][CT], int M, long N, int j, const long (&pix)[PT],
-                                         float* st, float eps) {
-    float sum[PT][4], sq[PT][4];
-#pragma unroll
-    for (int q = 0; q < PT; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { sum[q][e] = 0.f; sq[q][e] = 0.f; }
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const bool ok = c * 16 + j < M;
-#pragma unroll
-        for (int q = 0; q < PT; ++q) {
-            const float v[4] = {t[q][c].x, t[q][c].y, t[q][c].z, t[q][c].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sum[q][e] += ok ? v[e] : 0.f;
-        }
-    }
-    const float inv = 1.0f / (float)M;
-#pragma unroll
-    for (int q = 0; q < PT; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) sum[q][e] += __shfl_xor(sum[q][e], o);
-            sum[q][e] *= inv;
-        }
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const bool ok = c * 16 + j < M;
-#pragma unroll
-        for (int q = 0; q < PT; ++q) {
-            const float v[4] = {t[q][c].x, t[q][c].y, t[q][c].z, t[q][c].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = v[e] - sum[q][e];
-                sq[q][e] += ok ? d * d : 0.f;
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < PT; ++q) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) sq[q][e] += __shfl_xor(sq[q][e], o);
-            sq[q][e] = 1.0f / sqrtf(sq[q][e] * inv + eps);
-        }
-        if (j == 0 && pix[q] >= 0) {
-            *reinterpret_cast<float4*>(st + pix[q]) = make_float4(sum[q][0], sum[q][1], sum[q][2], sum[q][3]);
-            *reinterpret_cast<float4*>(st + N + pix[q]) = make_float4(sq[q][0], sq[q][1], sq[q][2], sq[q][3]);
-        }
-    }
-}
-
 // Packed-fp32 (v_pk_fma_f32) stencil: PT+2 rows x 3 columns around PT vertically neighbouring pixels, the
 // outputs as register pairs (o0,o1)[, (o2,o3)].  kk[t] holds tap t twice (k,k); bias first, then the taps row
 // by row, as dw_apply in elementwise.hip.  Lanes of a wave read consecutive columns of the halo image: no LDS
@@ -331,7 +274,7 @@ void dwgemm_kernel(DwGemmArgs a) {
             constexpr float sc = F16 ? 16.0f : 1.0f;
             t[q][c] = make_float4(acc[q][c][0] * sc, acc[q][c][1] * sc, acc[q][c][2] * sc, acc[q][c][3] * sc);
         }
-    if (a.stats_out) dg_stats<CT, PT>(t, a.M, plane, i, pix, a.stats_out + (long)b * 2 * plane, a.eps);
+    if (a.stats_out) irm_tile_stats<true>(t, 0, a.M, plane, i, pix, a.stats_out + (long)b * 2 * plane, a.eps);
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
         const int co = c * 16 + i;

@@ -749,30 +749,28 @@ template <int KS, int CT, bool GATE = true, bool APPLY = false, bool YCL = false
 static int gdfn_launch(FusedArgs a, int B, hipStream_t stream) {
     const size_t lds = ((size_t)2 * IRM_PLF + 2 * (KS * 1024 + 512) + (GATE ? CT * 512 + 2048 : 0)) * sizeof(float);
     static_assert(((size_t)2 * IRM_PLF + 2 * (KS * 1024 + 512) + CT * 512 + 2048) * sizeof(float) <= 160 * 1024, "LDS");
-    static int configured_dev[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IRM_ELAUNCH;
-    if (!configured_dev[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lnpw_dw_fused_kernel<KS, CT, GATE, APPLY, YCL, XVCL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return IRM_ELAUNCH;
-        configured_dev[dev] = 1;
-    }
+    IRM_ALLOW_BIG_LDS((&lnpw_dw_fused_kernel<KS, CT, GATE, APPLY, YCL, XVCL>));
+    int n = 0;
+    if (irm_cu_count(n) != IRM_OK) return IRM_ELAUNCH;
     a.tiles_x = (a.W + IRM_TW - 1) / IRM_TW;
     a.tiles = a.tiles_x * ((a.H + IRM_TH - 1) / IRM_TH);
     a.items = B * a.tiles;
-    static int cus_dev[64] = {0};
-    if (!cus_dev[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return IRM_ELAUNCH;
-        cus_dev[dev] = n;
-    }
     // one workgroup per CU (the kernel holds ~150 KiB of LDS), in whole groups of 8 (one per XCD)
     const int per = (a.items + 7) >> 3;
-    a.gpx = (cus_dev[dev] + 7) / 8;
+    a.gpx = (n + 7) / 8;
     if (a.gpx > per) a.gpx = per;
     hipLaunchKernelGGL((lnpw_dw_fused_kernel<KS, CT, GATE, APPLY, YCL, XVCL>), dim3(a.gpx * 8), dim3(512), lds, stream, a);
     return irm_launch_status();
+}
+
+// What the three entries below share of FusedArgs.  Everything else starts out absent: no project_out (w2, bias2, inv_s2),
+// no APPLY inputs, M = 0, every layout planar; the tile counts are gdfn_launch's.
+static FusedArgs fused_args(const float* rec, const float* x, long x_bs, float* y, long y_bs, int ln_mode, float eps,
+                            float inv_s1, int C, int H, int W, int S) {
+    FusedArgs a{};
+    a.X = x; a.x_bs = x_bs; a.Y = y; a.y_bs = y_bs; a.rec = rec;
+    a.C = C; a.H = H; a.W = W; a.S = S; a.ln_mode = ln_mode; a.eps = eps; a.inv_s1 = inv_s1;
+    return a;
 }
 
 extern "C" int irm_gdfn_fused_f16x3_f32(const float* rec, const float* w2, const float* bias2, const float* x, long x_bs,
@@ -783,11 +781,8 @@ extern "C" int irm_gdfn_fused_f16x3_f32(const float* rec, const float* w2, const
     if (ln_mode != IRM_LN_WITHBIAS && ln_mode != IRM_LN_BIASFREE) return IRM_EINVAL;
     if ((x_bs & 3) || (y_bs & 3) || !irm_aligned16(x) || !irm_aligned16(y) || !irm_aligned16(rec) || !irm_aligned16(w2))
         return IRM_EINVAL;
-    FusedArgs a;
-    a.X = x; a.x_bs = x_bs; a.Y = y; a.y_bs = y_bs; a.rec = rec; a.w2 = w2; a.bias2 = bias2;
-    a.C = C; a.H = H; a.W = W; a.S = (hid + 15) / 16; a.M = 0; a.ln_mode = ln_mode; a.eps = eps; a.inv_s1 = inv_s1; a.inv_s2 = inv_s2;
-    a.V = nullptr; a.v_bs = 0; a.mf = nullptr; a.mf_bs = 0; a.bias_o = nullptr; a.tm = 0; a.x_tm = 0; a.v_tm = 0; a.y_tm = 0;
-    a.tiles_x = 0; a.tiles = 0;
+    FusedArgs a = fused_args(rec, x, x_bs, y, y_bs, ln_mode, eps, inv_s1, C, H, W, (hid + 15) / 16);
+    a.w2 = w2; a.bias2 = bias2; a.inv_s2 = inv_s2;
     const int ks = (C + 31) / 32, ct = (C + 15) / 16;
     if (ks == 3) {
         if (ct <= 6) return gdfn_launch<3, 6>(a, B, stream);
@@ -813,12 +808,11 @@ extern "C" int irm_attn_gdfn_fused_f16x3_f32(const float* rec, const float* w2, 
     if ((x_bs & 3) || (y_bs & 3) || (v_bs & 3) || !irm_aligned16(x) || !irm_aligned16(y) || !irm_aligned16(v) ||
         !irm_aligned16(rec) || !irm_aligned16(w2) || !irm_aligned16(mfold_frag) || (bias_o && !irm_aligned16(bias_o)))
         return IRM_EINVAL;
-    FusedArgs a;
-    a.X = x; a.x_bs = x_bs; a.Y = y; a.y_bs = y_bs; a.rec = rec; a.w2 = w2; a.bias2 = bias2;
-    a.C = C; a.H = H; a.W = W; a.S = (hid + 15) / 16; a.M = 0; a.ln_mode = ln_mode; a.eps = eps; a.inv_s1 = inv_s1; a.inv_s2 = inv_s2;
+    FusedArgs a = fused_args(rec, x, x_bs, y, y_bs, ln_mode, eps, inv_s1, C, H, W, (hid + 15) / 16);
+    a.w2 = w2; a.bias2 = bias2; a.inv_s2 = inv_s2;
     const int ks = (C + 31) / 32, ct = (C + 15) / 16;
-    a.V = v; a.v_bs = v_bs; a.mf = mfold_frag; a.mf_bs = (long)2 * ks * ks * 512; a.bias_o = bias_o; a.tm = 0; a.x_tm = lay & 1; a.v_tm = (lay >> 1) & 1; a.y_tm = (lay >> 2) & 1;
-    a.tiles_x = 0; a.tiles = 0;
+    a.V = v; a.v_bs = v_bs; a.mf = mfold_frag; a.mf_bs = (long)2 * ks * ks * 512; a.bias_o = bias_o;
+    a.x_tm = lay & 1; a.v_tm = (lay >> 1) & 1; a.y_tm = (lay >> 2) & 1;
     if (a.x_tm && a.v_tm && ks == 3) return a.y_tm ? ((bias2 && !irm_aligned16(bias2)) ? IRM_EINVAL : gdfn_launch<3, 6, true, true, true, true>(a, B, stream))
                                                    : gdfn_launch<3, 6, true, true, false, true>(a, B, stream);
     if (a.x_tm && a.v_tm && ks == 2 && ct <= 3) return a.y_tm ? ((bias2 && !irm_aligned16(bias2)) ? IRM_EINVAL : gdfn_launch<2, 3, true, true, true, true>(a, B, stream))
@@ -842,11 +836,8 @@ static int qkv_dw_fused(const float* rec, const float* x, long x_bs, float* y, l
     if (C > 96 || (W & 3) || (long)M * H * W >= (1L << 30)) return IRM_EINVAL;
     if (ln_mode != IRM_LN_WITHBIAS && ln_mode != IRM_LN_BIASFREE) return IRM_EINVAL;
     if ((x_bs & 3) || (y_bs & 3) || !irm_aligned16(x) || !irm_aligned16(y) || !irm_aligned16(rec)) return IRM_EINVAL;
-    FusedArgs a;
-    a.X = x; a.x_bs = x_bs; a.Y = y; a.y_bs = y_bs; a.rec = rec; a.w2 = nullptr; a.bias2 = nullptr;
-    a.C = C; a.H = H; a.W = W; a.S = (M + 31) / 32; a.M = M; a.ln_mode = ln_mode; a.eps = eps; a.inv_s1 = inv_s1; a.inv_s2 = 0.f;
-    a.V = nullptr; a.v_bs = 0; a.mf = nullptr; a.mf_bs = 0; a.bias_o = nullptr; a.tm = tm & 1; a.x_tm = (tm >> 1) & 1; a.v_tm = (tm >> 2) & 1; a.y_tm = 0;
-    a.tiles_x = 0; a.tiles = 0;
+    FusedArgs a = fused_args(rec, x, x_bs, y, y_bs, ln_mode, eps, inv_s1, C, H, W, (M + 31) / 32);
+    a.M = M; a.tm = tm & 1; a.x_tm = (tm >> 1) & 1; a.v_tm = (tm >> 2) & 1;
     if (a.x_tm) {            // the blocks inside a stage: no planar load path in the instantiation
         if ((C + 31) / 32 == 3) return gdfn_launch<3, 1, false, false, false, true>(a, B, stream);
         if ((C + 31) / 32 == 2) return gdfn_launch<2, 1, false, false, false, true>(a, B, stream);

@@ -386,9 +386,8 @@ template <int KS, bool GRAM = false>
 static int qc_launch(QcArgs a, int B, hipStream_t stream) {
     const size_t lds = (size_t)3 * (KS * 1024 + 512) * 4 + 2 * 368 * 4 + 2 * QC_IMG;
     IRM_ALLOW_BIG_LDS((&qkv_cm_kernel<KS, GRAM>));
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return IRM_ELAUNCH;
+    int n = 0;
+    if (irm_cu_count(n) != IRM_OK) return IRM_ELAUNCH;
     a.tiles_x = a.W / QC_TW;
     a.tiles = a.tiles_x * (a.H / QC_TH);
     a.items = B * a.tiles;

@@ -251,9 +251,8 @@ extern "C" int irm_gdfn_tail_f16x3_f32(const float* h_cl, long h_bs, const float
     constexpr int CT = 12;
     const size_t lds = (size_t)(2 * 512 + CT * 512 + 2 * IRM_PLF + 2048) * sizeof(float);
     IRM_ALLOW_BIG_LDS((&gdfn_tail_kernel<CT>));
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return IRM_ELAUNCH;
+    int n = 0;
+    if (irm_cu_count(n) != IRM_OK) return IRM_ELAUNCH;
     const int per = (a.items + 7) >> 3;
     a.gpx = (n + 7) / 8;
     if (a.gpx > per) a.gpx = per;

@@ -40,64 +40,6 @@ struct GemmArgs {
 };
 
 
-// LayerNorm statistics of the finished output tile straight from the accumulators: lane (r, g)
-// holds pixels pix..pix+3 of channels 16 c + r, so a channel reduction is CT in-lane adds plus
-// a 16-lane butterfly.  Two passes (mean, then centred squares) in registers.
-template <int PT, int CT>
-__device__ __forceinline__ void irm_stats_from_acc(const f32x4 (&acc)[PT][CT], int mt0, int M, int N, int r,
-                                                   const int (&pixs)[PT], float* st, float eps) {
-    float sum[PT][4], sq[PT][4];
-#pragma unroll
-    for (int p = 0; p < PT; ++p)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { sum[p][e] = 0.f; sq[p][e] = 0.f; }
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const bool ok = (mt0 + c) * 16 + r < M;
-#pragma unroll
-        for (int p = 0; p < PT; ++p)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sum[p][e] += ok ? acc[p][c][e] : 0.f;
-    }
-    const float inv = 1.0f / (float)M;
-#pragma unroll
-    for (int p = 0; p < PT; ++p)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) sum[p][e] += __shfl_xor(sum[p][e], o);
-            sum[p][e] *= inv;                                   // mean
-        }
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const bool ok = (mt0 + c) * 16 + r < M;
-#pragma unroll
-        for (int p = 0; p < PT; ++p)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = acc[p][c][e] - sum[p][e];
-                sq[p][e] += ok ? d * d : 0.f;
-            }
-    }
-#pragma unroll
-    for (int p = 0; p < PT; ++p) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) sq[p][e] += __shfl_xor(sq[p][e], o);
-            sq[p][e] = 1.0f / sqrtf(sq[p][e] * inv + eps);      // rstd
-        }
-        if (r == 0) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (pixs[p] + e < N) {
-                    st[pixs[p] + e] = sum[p][e];
-                    st[N + pixs[p] + e] = sq[p][e];
-                }
-        }
-    }
-}
-
 template <int PT, int CT, bool VEC>
 __global__ __launch_bounds__(256) void gemm_pw_kernel(GemmArgs a) {
     constexpr int BN = 64 * PT;      // pixels per workgroup
@@ -249,7 +191,7 @@ __global__ __launch_bounds__(256) void gemm_pw_kernel(GemmArgs a) {
             }
         }
         if (a.stats_out)
-            irm_stats_from_acc<PT, CT>(acc, mt0, a.M, a.N, lane & 15, pixs, a.stats_out + (long)b * 2 * a.N, a.eps);
+            irm_tile_stats<false>(acc, mt0, a.M, a.N, lane & 15, pixs, a.stats_out + (long)b * 2 * a.N, a.eps);
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
             const int co = (mt0 + c) * 16 + (lane & 15);
@@ -516,7 +458,7 @@ __global__ __launch_bounds__(256, (PT == 2 && NS == 3) ? 3 : 2) void gemm_ring_k
                         acc[p][c][2] = fmaf(rv[p][c].z, sc, acc[p][c][2]); acc[p][c][3] = fmaf(rv[p][c].w, sc, acc[p][c][3]);
                     }
             }
-            if (a.stats_out) irm_stats_from_acc<PT, CT>(acc, mt0, a.M, a.N, r, pixs, a.stats_out + (long)b * 2 * a.N, a.eps);
+            if (a.stats_out) irm_tile_stats<false>(acc, mt0, a.M, a.N, r, pixs, a.stats_out + (long)b * 2 * a.N, a.eps);
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
                 const int co = (mt0 + c) * 16 + r;
@@ -565,35 +507,41 @@ static int launch_ring(const GemmArgs& a, int B, int ygroups, hipStream_t stream
     return launch_ring_ns<PT, CT, PT == 2 ? 4 : 3, LN, RES, F16>(a, B, ygroups, stream);
 }
 
+// Run-time values that select an instantiation, as compile-time constants: f(irm_ic<value>{}).
+// The output tiles per pass that are instantiated (anything else: IRM_EINVAL) ...
+template <class F>
+static int dispatch_ct(int ct, F&& f) {
+    switch (ct) {
+        case 3: return f(irm_ic<3>{});
+        case 4: return f(irm_ic<4>{});
+        case 6: return f(irm_ic<6>{});
+        case 8: return f(irm_ic<8>{});
+        case 9: return f(irm_ic<9>{});
+        default: return IRM_EINVAL;
+    }
+}
+// ... and the LayerNorm prologue (gemm_entry has checked the range)
+template <class F>
+static int dispatch_ln(int ln_mode, F&& f) {
+    if (ln_mode == IRM_LN_WITHBIAS) return f(irm_ic<IRM_LN_WITHBIAS>{});
+    if (ln_mode == IRM_LN_BIASFREE) return f(irm_ic<IRM_LN_BIASFREE>{});
+    return f(irm_ic<IRM_LN_NONE>{});
+}
+
 // instantiated combinations: 64-pixel waves (PT 4) only without a residual (the prefetched residual
 // doubles the accumulator-sized register block); LayerNorm prologue only without a residual (the
-// path never combines them)
-template <int CT>
+// path never combines them); the split-fp16 variant (F16) without a residual has 64-pixel waves only
+template <int CT, bool F16>
 static int launch_ring_any(const GemmArgs& a, int B, int ygroups, int pt, hipStream_t stream) {
     if (a.R) {
         if (a.ln_mode != IRM_LN_NONE) return IRM_EINVAL;
-        return launch_ring<2, CT, IRM_LN_NONE, true>(a, B, ygroups, stream);
+        return launch_ring<2, CT, IRM_LN_NONE, true, F16>(a, B, ygroups, stream);
     }
-    if (pt == 4) {
-        if (a.ln_mode == IRM_LN_WITHBIAS) return launch_ring<4, CT, IRM_LN_WITHBIAS, false>(a, B, ygroups, stream);
-        if (a.ln_mode == IRM_LN_BIASFREE) return launch_ring<4, CT, IRM_LN_BIASFREE, false>(a, B, ygroups, stream);
-        return launch_ring<4, CT, IRM_LN_NONE, false>(a, B, ygroups, stream);
-    }
-    if (a.ln_mode == IRM_LN_WITHBIAS) return launch_ring<2, CT, IRM_LN_WITHBIAS, false>(a, B, ygroups, stream);
-    if (a.ln_mode == IRM_LN_BIASFREE) return launch_ring<2, CT, IRM_LN_BIASFREE, false>(a, B, ygroups, stream);
-    return launch_ring<2, CT, IRM_LN_NONE, false>(a, B, ygroups, stream);
-}
-
-// split-fp16 variant: 64-pixel waves, no residual
-template <int CT>
-static int launch_ring_split(const GemmArgs& a, int B, int ygroups, hipStream_t stream) {
-    if (a.R) {
-        if (a.ln_mode != IRM_LN_NONE) return IRM_EINVAL;
-        return launch_ring<2, CT, IRM_LN_NONE, true, true>(a, B, ygroups, stream);
-    }
-    if (a.ln_mode == IRM_LN_WITHBIAS) return launch_ring<4, CT, IRM_LN_WITHBIAS, false, true>(a, B, ygroups, stream);
-    if (a.ln_mode == IRM_LN_BIASFREE) return launch_ring<4, CT, IRM_LN_BIASFREE, false, true>(a, B, ygroups, stream);
-    return launch_ring<4, CT, IRM_LN_NONE, false, true>(a, B, ygroups, stream);
+    if (F16 || pt == 4)
+        return dispatch_ln(a.ln_mode, [&](auto ln) { return launch_ring<4, CT, decltype(ln)::value, false, F16>(a, B, ygroups, stream); });
+    if constexpr (!F16)
+        return dispatch_ln(a.ln_mode, [&](auto ln) { return launch_ring<2, CT, decltype(ln)::value, false>(a, B, ygroups, stream); });
+    return IRM_EINVAL;
 }
 
 template <int PT, int CT>
@@ -642,36 +590,15 @@ static int gemm_entry(const float* wp, long w_bs, const float* x, long x_bs, flo
             const int rc = irm_gemm_xres_dispatch(wp, x, x_bs, y, y_bs, bias, stats, lnw, lnb, ln_mode, act, B, M, K, N, stream);
             if (rc != IRM_EINVAL) return rc;
         }
-        switch (ct) {
-            case 3: return launch_ring_split<3>(a, B, ygroups, stream);
-            case 4: return launch_ring_split<4>(a, B, ygroups, stream);
-            case 6: return launch_ring_split<6>(a, B, ygroups, stream);
-            case 8: return launch_ring_split<8>(a, B, ygroups, stream);
-            case 9: return launch_ring_split<9>(a, B, ygroups, stream);
-            default: return IRM_EINVAL;
-        }
+        return dispatch_ct(ct, [&](auto c) { return launch_ring_any<decltype(c)::value, true>(a, B, ygroups, 4, stream); });
     }
     if (vec && N >= 4 && !(res && ln_mode != IRM_LN_NONE)) {
         // 64 pixels per wave (PT 4) doubles the MFMAs per barrier; it is used when the accumulators
         // (+ the prefetched residual) still fit 2 waves per SIMD and the grid stays large
         const int pt = (!res && (long)B * ((N + 255) / 256) * ygroups >= 512) ? 4 : 2;
-        switch (ct) {
-            case 3: return launch_ring_any<3>(a, B, ygroups, pt, stream);
-            case 4: return launch_ring_any<4>(a, B, ygroups, pt, stream);
-            case 6: return launch_ring_any<6>(a, B, ygroups, pt, stream);
-            case 8: return launch_ring_any<8>(a, B, ygroups, pt, stream);
-            case 9: return launch_ring_any<9>(a, B, ygroups, pt, stream);
-            default: return IRM_EINVAL;
-        }
+        return dispatch_ct(ct, [&](auto c) { return launch_ring_any<decltype(c)::value, false>(a, B, ygroups, pt, stream); });
     }
-    switch (ct) {
-        case 3: return launch_gemm<2, 3>(a, B, ygroups, vec, stream);
-        case 4: return launch_gemm<2, 4>(a, B, ygroups, vec, stream);
-        case 6: return launch_gemm<2, 6>(a, B, ygroups, vec, stream);
-        case 8: return launch_gemm<2, 8>(a, B, ygroups, vec, stream);
-        case 9: return launch_gemm<2, 9>(a, B, ygroups, vec, stream);
-        default: return IRM_EINVAL;
-    }
+    return dispatch_ct(ct, [&](auto c) { return launch_gemm<2, decltype(c)::value>(a, B, ygroups, vec, stream); });
 }
 
 extern "C" int irm_gemm1x1_f32(const float* wp, long w_bs, const float* x, long x_bs, float* y, long y_bs,

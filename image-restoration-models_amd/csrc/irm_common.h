@@ -45,6 +45,20 @@ static inline int irm_launch_status() {
     return e == hipSuccess ? IRM_OK : IRM_ELAUNCH;
 }
 
+// Compute units of the current device, for the persistent-grid launchers (one workgroup per CU): asked once per device.
+static inline int irm_cu_count(int& n) {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return IRM_ELAUNCH;
+    if (!cus[dev]) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return IRM_ELAUNCH;
+        cus[dev] = v;
+    }
+    n = cus[dev];
+    return IRM_OK;
+}
+
 __device__ __forceinline__ float irm_gelu(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
 }
@@ -231,6 +245,74 @@ __device__ __forceinline__ f32x4 irm_mfma3_f16(irm_h8 ah, irm_h8 al, irm_h8 bh, 
     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);
+}
+
+// LayerNorm statistics (mean and rstd over the M channels, into st [2][N]) of a finished output tile straight from the
+// registers: lane (r, g) holds PT pixel quads t[p][c] of the channels 16 (mt0 + c) + r, c < CT, so a channel reduction
+// is CT in-lane adds plus a 16-lane butterfly.  Two passes (mean, then centred squares) in registers; lane r == 0 stores.
+// Where a quad lives, and what of it lies inside the image, is the caller's rule:
+//   QUAD   pix[p] is the quad's first pixel, or negative for a quad outside the image: two 16-byte stores (dwgemm.hip);
+//   else   pix[p] + e is pixel e, written when it is below N: guarded scalars (gemm_pw.hip).
+__device__ __forceinline__ float irm_quad_elem(const f32x4& v, int e) { return v[e]; }
+__device__ __forceinline__ float irm_quad_elem(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+template <bool QUAD, int PT, int CT, class Tile, class Pix, class Len>
+__device__ __forceinline__ void irm_tile_stats(const Tile (&t)[PT][CT], int mt0, int M, Len N, int r, const Pix (&pix)[PT],
+                                               float* st, float eps) {
+    float sum[PT][4], sq[PT][4];
+#pragma unroll
+    for (int p = 0; p < PT; ++p)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { sum[p][e] = 0.f; sq[p][e] = 0.f; }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        const bool ok = (mt0 + c) * 16 + r < M;
+#pragma unroll
+        for (int p = 0; p < PT; ++p)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sum[p][e] += ok ? irm_quad_elem(t[p][c], e) : 0.f;
+    }
+    const float inv = 1.0f / (float)M;
+#pragma unroll
+    for (int p = 0; p < PT; ++p)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) sum[p][e] += __shfl_xor(sum[p][e], o);
+            sum[p][e] *= inv;                                   // mean
+        }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        const bool ok = (mt0 + c) * 16 + r < M;
+#pragma unroll
+        for (int p = 0; p < PT; ++p)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d = irm_quad_elem(t[p][c], e) - sum[p][e];
+                sq[p][e] += ok ? d * d : 0.f;
+            }
+    }
+#pragma unroll
+    for (int p = 0; p < PT; ++p) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) sq[p][e] += __shfl_xor(sq[p][e], o);
+            sq[p][e] = 1.0f / sqrtf(sq[p][e] * inv + eps);      // rstd
+        }
+        if constexpr (QUAD) {
+            if (r == 0 && pix[p] >= 0) {
+                *reinterpret_cast<float4*>(st + pix[p]) = make_float4(sum[p][0], sum[p][1], sum[p][2], sum[p][3]);
+                *reinterpret_cast<float4*>(st + N + pix[p]) = make_float4(sq[p][0], sq[p][1], sq[p][2], sq[p][3]);
+            }
+        } else if (r == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (pix[p] + e < N) {
+                    st[pix[p] + e] = sum[p][e];
+                    st[N + pix[p] + e] = sq[p][e];
+                }
+        }
+    }
 }
 
 // ---- the 8 x 32 pixel tile of the fused GDFN / qkv branch kernels (fused_block.hip, fused_tail.hip)

@@ -144,29 +144,57 @@ __global__ __launch_bounds__(256) void mdta_gram_kernel(GramArgs a) {
 //   T = 3 (c = 48): BP = 64, the 4 waves split the 16 k-steps of a stage, partial Grams are summed through
 //                   LDS in wave order at the end (deterministic);
 //   T = 6 (c = 96): BP = 32, wave (wa, wb) owns the 48 x 48 quadrant (wa, wb) for all 8 k-steps.
+// GramStage holds what this kernel and mdta_gram_f16x3_kernel below share as ONE definition: the stage geometry and the
+// DMA issue of a stage.  (The guarded mdta_gram_kernel above has no ring; gram_cm.h's qc_gram_flush combines 8 waves of 512
+// threads that hold other tiles: both stay on their own.)
+template <int T, int NS>
+struct GramStage {
+    static constexpr int c = 16 * T;
+    static constexpr int BP = T == 3 ? 64 : 32;    // pixels per stage
+    static constexpr int CPR = BP / 4;             // 16-byte pieces per row segment
+    static constexpr int RPB = 64 / CPR;           // rows per 1 KiB DMA instruction
+    static constexpr int NI = 2 * c / RPB;         // DMA instructions per stage (24)
+    static constexpr int LPS = NI / 4;             // per wave (6)
+    static constexpr int STG = NI * 256;           // floats per stage
+    static constexpr int REC = c * c + 2 * c;      // floats per partial record: G[c][c], nq[c], nk[c]
+    static_assert((NS - 2) * LPS <= 63, "vmcnt field");
+
+    // stage s of the workgroup whose first block starts at pixel nbeg and whose blocks lie sstep pixels apart, into ring
+    // slot s % NS: this wave's LPS instructions from its lanes' sources src (stage 0) + the stage's offset
+    static __device__ __forceinline__ void issue(const GramArgs& a, const float* const (&src)[LPS], int wave, int nbeg,
+                                                 long sstep, int s) {
+        extern __shared__ __attribute__((aligned(16))) float smem[];
+        float* dst = smem + (s % NS) * STG + wave * 256;
+        long so = s * sstep;
+        if (a.tm) {
+            const long n0 = (long)nbeg + so;                 // first pixel (tile order) of this stage's block
+            so = (n0 >> 8) * (2L * a.C * 256) + (n0 & 255);
+        }
+#pragma unroll
+        for (int j = 0; j < LPS; ++j) {
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + so),
+                                             (__attribute__((address_space(3))) void*)(dst + j * 1024), 16, 0, 0);
+        }
+    }
+};
+
 template <int T, int NS>
 __global__ __launch_bounds__(256, 2) void mdta_gram_ring_kernel(GramArgs a) {
-    constexpr int c = 16 * T;
-    constexpr int BP = T == 3 ? 64 : 32;           // pixels per stage
-    constexpr int CPR = BP / 4;                    // 16-byte pieces per row segment
-    constexpr int RPB = 64 / CPR;                  // rows per 1 KiB DMA instruction
-    constexpr int NI = 2 * c / RPB;                // DMA instructions per stage (24)
-    constexpr int LPS = NI / 4;                    // per wave (6)
-    constexpr int STG = NI * 256;                  // floats per stage
+    using Stage = GramStage<T, NS>;
+    constexpr int c = Stage::c, BP = Stage::BP, CPR = Stage::CPR, RPB = Stage::RPB, LPS = Stage::LPS, STG = Stage::STG;
     constexpr int KS = BP / 4;                     // k-steps per stage
-    static_assert((NS - 2) * LPS <= 63, "vmcnt field");
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, kk = lane >> 4;
     const int b = blockIdx.y;
     const int head = blockIdx.x / a.nchunk, chunk_id = blockIdx.x % a.nchunk;
-    // interleaved pixel blocks (see mdta_gram_f16x3_kernel): workgroup j takes the BP-pixel blocks j, j + nchunk, ...
+    // interleaved pixel blocks: workgroup j takes the BP-pixel blocks j, j + nchunk, ... (why: at the emulated kernel)
     const int nbeg = chunk_id * BP;
     const int nblocks = a.N / BP;
     const int S = chunk_id < nblocks ? (nblocks - chunk_id + a.nchunk - 1) / a.nchunk : 0;
     const long sstep = (long)a.nchunk * BP;
-    // (a.tm: q, k tile-major, see mdta_gram_f16x3_kernel)
+    // (a.tm: q, k tile-major, described there too)
     const float* base = a.qkv + (long)b * a.bs + (a.tm ? 0 : nbeg);
     const long rowstride = a.tm ? 256 : a.N;
 
@@ -180,19 +208,7 @@ __global__ __launch_bounds__(256, 2) void mdta_gram_ring_kernel(GramArgs a) {
         const int ch = row < c ? head * c + row : a.C + head * c + (row - c);
         src[j] = base + (long)ch * rowstride + 4 * ((p - rot) & (CPR - 1));
     }
-    auto issue = [&](int s) {
-        float* dst = smem + (s % NS) * STG + wave * 256;
-        long so = s * sstep;
-        if (a.tm) {
-            const long n0 = (long)nbeg + so;
-            so = (n0 >> 8) * (2L * a.C * 256) + (n0 & 255);
-        }
-#pragma unroll
-        for (int j = 0; j < LPS; ++j) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + so),
-                                             (__attribute__((address_space(3))) void*)(dst + j * 1024), 16, 0, 0);
-        }
-    };
+    auto issue = [&](int s) { Stage::issue(a, src, wave, nbeg, sstep, s); };
 
     // operand reads: row 16m + i (+ c for k), pixel quad ks, element kk
     //   T = 3: float offset 1024 m + (i>>2)*256 + (i&3)*64 + 4*((ks + i) & 15) + kk        (k rows: + 3072)
@@ -253,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void mdta_gram_ring_kernel(GramArgs a) {
         nq[m] += __shfl_xor(nq[m], 16); nq[m] += __shfl_xor(nq[m], 32);
         nk[m] += __shfl_xor(nk[m], 16); nk[m] += __shfl_xor(nk[m], 32);
     }
-    constexpr int REC = c * c + 2 * c;
+    constexpr int REC = Stage::REC;
     float* out = a.part + (((long)b * a.heads + head) * a.nchunk + chunk_id) * REC;
     if (T == 6) {
 #pragma unroll
@@ -297,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void mdta_gram_ring_kernel(GramArgs a) {
 // The same Gram pass as an fp32 emulation on the fp16 matrix cores (irm_mdta_gram_f16x3_f32): the f32-input MFMA
 // above needs 2304 matrix cycles per wave and 24 KiB stage - 6.4 TB/s at best with two workgroups per CU -, the
 // emulation 432 (27 v_mfma_f32_16x16x32_f16) plus ~400 cycles of vector work for the hi/lo split, so the sweep over
-// q, k becomes a memory stream.  Same LDS-DMA ring and piece rotation as mdta_gram_ring_kernel; an operand fragment
+// q, k becomes a memory stream.  The LDS-DMA ring of mdta_gram_ring_kernel (GramStage) with the piece rotation gr_rot below; an operand fragment
 // (row, 8 consecutive pixels) is two conflict-free ds_read_b128, scaled by the row's power-of-two factor
 // (`scale`, host side: 2^14-ish / a static bound of |q_c|, |k_c| - exact), split into fp16 hi + lo, and multiplied
 // as lo*hi + hi*lo + hi*hi with fp32 accumulation.  The squared norms stay on the fp32 vector pipe.  Records leave
@@ -321,14 +337,8 @@ __device__ __forceinline__ int gr_rot(int row) {
 
 template <int T, int NS>
 __global__ __launch_bounds__(256, 2) void mdta_gram_f16x3_kernel(GramArgs a, const float* __restrict__ scale) {
-    constexpr int c = 16 * T;
-    constexpr int BP = T == 3 ? 64 : 32;           // pixels per stage
-    constexpr int CPR = BP / 4;                    // 16-byte pieces per row segment
-    constexpr int RPB = 64 / CPR;                  // rows per 1 KiB DMA instruction
-    constexpr int NI = 2 * c / RPB;                // DMA instructions per stage (24)
-    constexpr int LPS = NI / 4;                    // per wave (6)
-    constexpr int STG = NI * 256;                  // floats per stage
-    static_assert((NS - 2) * LPS <= 63, "vmcnt field");
+    using Stage = GramStage<T, NS>;
+    constexpr int c = Stage::c, BP = Stage::BP, CPR = Stage::CPR, RPB = Stage::RPB, LPS = Stage::LPS, STG = Stage::STG;
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -359,19 +369,7 @@ __global__ __launch_bounds__(256, 2) void mdta_gram_f16x3_kernel(GramArgs a, con
         const int ch = row < c ? head * c + row : a.C + head * c + (row - c);
         src[j] = base + (long)ch * rowstride + 4 * ((p - rot) & (CPR - 1));
     }
-    auto issue = [&](int s) {
-        float* dst = smem + (s % NS) * STG + wave * 256;
-        long so = s * sstep;
-        if (a.tm) {
-            const long n0 = (long)nbeg + so;                 // first pixel (tile order) of this stage's block
-            so = (n0 >> 8) * (2L * a.C * 256) + (n0 & 255);
-        }
-#pragma unroll
-        for (int j = 0; j < LPS; ++j) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + so),
-                                             (__attribute__((address_space(3))) void*)(dst + j * 1024), 16, 0, 0);
-        }
-    };
+    auto issue = [&](int s) { Stage::issue(a, src, wave, nbeg, sstep, s); };
 
     // this wave's tiles
     const int wa = wave >> 1, wb = wave & 1;
@@ -446,7 +444,7 @@ __global__ __launch_bounds__(256, 2) void mdta_gram_f16x3_kernel(GramArgs a, con
     for (int m = 0; m < NQ; ++m) { nq[m] += __shfl_xor(nq[m], 16); nq[m] += __shfl_xor(nq[m], 32); }
 #pragma unroll
     for (int m = 0; m < 3; ++m) { nk[m] += __shfl_xor(nk[m], 16); nk[m] += __shfl_xor(nk[m], 32); }
-    constexpr int REC = c * c + 2 * c;
+    constexpr int REC = Stage::REC;
     float* out = a.part + (((long)b * a.heads + head) * a.nchunk + chunk_id) * REC;
     // undo the operand scales (exact): element (q row, k row) by 1 / (s_q s_k)
     float isk[3];
@@ -510,29 +508,6 @@ static int launch_gram_f16x3(const GramArgs& a, const float* scale, int B, hipSt
     return irm_launch_status();
 }
 
-extern "C" int irm_mdta_gram_f16x3_f32(const float* qkv, long bs, const float* scale, float* part, int B, int C,
-                                       int heads, int N, int chunk, hipStream_t stream) {
-    if (!qkv || !scale || !part || B <= 0 || C <= 0 || heads <= 0 || N <= 0 || chunk <= 0) return IRM_EINVAL;
-    if (C % heads || (chunk & 63) || B > 65535) return IRM_EINVAL;
-    const int c = C / heads;
-    if ((c != 48 && c != 96) || (N & 63) || (bs & 3) || !irm_aligned16(qkv)) return IRM_EINVAL;
-    if ((long)heads * ((N + chunk - 1) / chunk) > 2147483647L) return IRM_EINVAL;
-    GramArgs a{qkv, bs, part, C, heads, N, chunk, (N + chunk - 1) / chunk, 0};
-    return c == 48 ? launch_gram_f16x3<3>(a, scale, B, stream) : launch_gram_f16x3<6>(a, scale, B, stream);
-}
-
-// The same pass over tile-major q, k (header): N % 256 == 0.
-extern "C" int irm_mdta_gram_tm_f16x3_f32(const float* qkv, long bs, const float* scale, float* part, int B, int C,
-                                          int heads, int N, int chunk, hipStream_t stream) {
-    if (!qkv || !scale || !part || B <= 0 || C <= 0 || heads <= 0 || N <= 0 || chunk <= 0) return IRM_EINVAL;
-    if (C % heads || (chunk & 63) || B > 65535) return IRM_EINVAL;
-    const int c = C / heads;
-    if ((c != 48 && c != 96) || (N & 255) || (bs & 3) || !irm_aligned16(qkv)) return IRM_EINVAL;
-    if ((long)heads * ((N + chunk - 1) / chunk) > 2147483647L) return IRM_EINVAL;
-    GramArgs a{qkv, bs, part, C, heads, N, chunk, (N + chunk - 1) / chunk, 1};
-    return c == 48 ? launch_gram_f16x3<3>(a, scale, B, stream) : launch_gram_f16x3<6>(a, scale, B, stream);
-}
-
 template <int T>
 static int launch_gram_ring(const GramArgs& a, int B, hipStream_t stream) {
     constexpr int NS = 3;
@@ -542,33 +517,60 @@ static int launch_gram_ring(const GramArgs& a, int B, hipStream_t stream) {
     return irm_launch_status();
 }
 
+// The argument check of the four Gram entries: fills `a` or returns IRM_EINVAL.
+//   pix     the multiple of pixels the entry needs of N: 64 or 256 for the ring-only entries, which also need 16-byte
+//           aligned rows and a grid within 2^31; 0 for the entry whose guarded kernel takes what the ring cannot;
+//   ring_c  c = C / heads must be 48 or 96 (else: a multiple of 16);
+//   tm      q, k tile-major.
+static int gram_check(GramArgs& a, const float* qkv, long bs, float* part, int B, int C, int heads, int N, int chunk,
+                      int pix, bool ring_c, int tm) {
+    if (!qkv || !part || B <= 0 || C <= 0 || heads <= 0 || N <= 0 || chunk <= 0) return IRM_EINVAL;
+    if (C % heads || (chunk & 63) || B > 65535) return IRM_EINVAL;
+    const int c = C / heads, nchunk = (N + chunk - 1) / chunk;
+    if (ring_c ? (c != 48 && c != 96) : c % 16 != 0) return IRM_EINVAL;
+    if (pix && ((N & (pix - 1)) || (bs & 3) || !irm_aligned16(qkv) || (long)heads * nchunk > 2147483647L)) return IRM_EINVAL;
+    a = GramArgs{qkv, bs, part, C, heads, N, chunk, nchunk, tm};
+    return IRM_OK;
+}
+
+static int gram_f16x3_entry(const float* qkv, long bs, const float* scale, float* part, int B, int C, int heads, int N,
+                            int chunk, int pix, int tm, hipStream_t stream) {
+    GramArgs a;
+    if (!scale || gram_check(a, qkv, bs, part, B, C, heads, N, chunk, pix, true, tm) != IRM_OK) return IRM_EINVAL;
+    return C / heads == 48 ? launch_gram_f16x3<3>(a, scale, B, stream) : launch_gram_f16x3<6>(a, scale, B, stream);
+}
+
+extern "C" int irm_mdta_gram_f16x3_f32(const float* qkv, long bs, const float* scale, float* part, int B, int C,
+                                       int heads, int N, int chunk, hipStream_t stream) {
+    return gram_f16x3_entry(qkv, bs, scale, part, B, C, heads, N, chunk, 64, 0, stream);
+}
+
+// The same pass over tile-major q, k (header): N % 256 == 0.
+extern "C" int irm_mdta_gram_tm_f16x3_f32(const float* qkv, long bs, const float* scale, float* part, int B, int C,
+                                          int heads, int N, int chunk, hipStream_t stream) {
+    return gram_f16x3_entry(qkv, bs, scale, part, B, C, heads, N, chunk, 256, 1, stream);
+}
+
 // The f32-input ring pass over tile-major q, k (header): c = 48 / 96, N % 256 == 0.
 extern "C" int irm_mdta_gram_tm_f32(const float* qkv, long bs, float* part, int B, int C, int heads, int N, int chunk,
                                     hipStream_t stream) {
-    if (!qkv || !part || B <= 0 || C <= 0 || heads <= 0 || N <= 0 || chunk <= 0) return IRM_EINVAL;
-    if (C % heads || (chunk & 63) || B > 65535) return IRM_EINVAL;
-    const int c = C / heads;
-    if ((c != 48 && c != 96) || (N & 255) || (bs & 3) || !irm_aligned16(qkv)) return IRM_EINVAL;
-    if ((long)heads * ((N + chunk - 1) / chunk) > 2147483647L) return IRM_EINVAL;
-    GramArgs a{qkv, bs, part, C, heads, N, chunk, (N + chunk - 1) / chunk, 1};
-    return c == 48 ? launch_gram_ring<3>(a, B, stream) : launch_gram_ring<6>(a, B, stream);
+    GramArgs a;
+    if (gram_check(a, qkv, bs, part, B, C, heads, N, chunk, 256, true, 1) != IRM_OK) return IRM_EINVAL;
+    return C / heads == 48 ? launch_gram_ring<3>(a, B, stream) : launch_gram_ring<6>(a, B, stream);
 }
 
 extern "C" int irm_mdta_gram_f32(const float* qkv, long bs, float* part, int B, int C, int heads, int N,
                                  int chunk, hipStream_t stream) {
-    if (!qkv || !part || B <= 0 || C <= 0 || heads <= 0 || N <= 0 || chunk <= 0) return IRM_EINVAL;
-    if (C % heads || (chunk & 63) || B > 65535) return IRM_EINVAL;
+    GramArgs a;
+    if (gram_check(a, qkv, bs, part, B, C, heads, N, chunk, 0, false, 0) != IRM_OK) return IRM_EINVAL;
     const int c = C / heads;
-    if (c % 16) return IRM_EINVAL;
-    GramArgs a{qkv, bs, part, C, heads, N, chunk, (N + chunk - 1) / chunk, 0};
-    const bool aligned = !(N & 3) && !(bs & 3) && irm_aligned16(qkv);
-    if (aligned && !(N & 63) && (c == 48 || c == 96) && (long)heads * a.nchunk <= 2147483647L)
+    const bool vec = !(N & 3) && !(bs & 3) && irm_aligned16(qkv);
+    if (vec && !(N & 63) && (c == 48 || c == 96) && (long)heads * a.nchunk <= 2147483647L)
         return c == 48 ? launch_gram_ring<3>(a, B, stream) : launch_gram_ring<6>(a, B, stream);
     const int sb = (c % 48 == 0) ? 3 : (c % 32 == 0) ? 2 : 1;
     const int nsb = c / (16 * sb);
     const long units = (long)heads * nsb * nsb * a.nchunk;
     dim3 grid((unsigned)((units + 3) / 4), B);
-    const bool vec = !(N & 3) && !(bs & 3) && irm_aligned16(qkv);
     if (vec) {
         if (sb == 3) hipLaunchKernelGGL((mdta_gram_kernel<3, true>), grid, dim3(256), 0, stream, a);
         else if (sb == 2) hipLaunchKernelGGL((mdta_gram_kernel<2, true>), grid, dim3(256), 0, stream, a);
@@ -623,8 +625,12 @@ struct FinArgs {
     float* mfold;               // [B][mtiles][ksteps][64]
     float* attn;                // optional [B][heads][c][c] (tests) or null
     int C, heads, ksteps;
-    int split;                  // 1: mfold in irm_gemm1x1_f16x3_f32's fp16 hi/lo order instead of packed fp32;
-                                // 2: as 16x16x32 MFMA fragments [mtile][KS][hi|lo][64 lanes][8 halves] (irm_attn_gdfn_fused_f16x3_f32)
+    int split;                  // layout of mfold, one of:
+};
+enum {
+    FIN_PACKED = 0,             // packed fp32 (irm_gemm1x1_f32)
+    FIN_SPLIT = 1,              // irm_gemm1x1_f16x3_f32's fp16 hi/lo order
+    FIN_FRAG = 2,               // 16x16x32 MFMA fragments [mtile][KS][hi|lo][64 lanes][8 halves] (irm_attn_gdfn_fused_f16x3_f32)
 };
 
 // 16 waves: the softmax rows are chains of dependent cross-lane reductions (latency, not throughput), 6 rows per wave
@@ -693,7 +699,7 @@ __global__ __launch_bounds__(1024) void mdta_finalize_kernel(FinArgs a) {
     // fold with project_out; the output rows are split over gridDim.z workgroups
     const int mtiles = (a.C + 15) / 16;
     const int KS32 = (a.C + 31) / 32;
-    float* mf = a.mfold + (a.split == 2 ? (long)b * 2 * KS32 * KS32 * 512 : (long)b * mtiles * a.ksteps * 64);
+    float* mf = a.mfold + (a.split == FIN_FRAG ? (long)b * 2 * KS32 * KS32 * 512 : (long)b * mtiles * a.ksteps * 64);
     const int rows_per = (a.C + gridDim.z - 1) / gridDim.z;
     const int co0 = blockIdx.z * rows_per, co1 = min(co0 + rows_per, a.C);
     // this workgroup's rows of project_out (columns of this head) into LDS: the dot products below then read LDS only
@@ -708,14 +714,14 @@ __global__ __launch_bounds__(1024) void mdta_finalize_kernel(FinArgs a) {
 #pragma unroll 8
         for (int i = 0; i < c; ++i) acc += wrow[i] * G[i * c + j];
         const int kcol = head * c + j;
-        if (a.split == 2) {
+        if (a.split == FIN_FRAG) {
             // fragment (mtile, 32-channel k-step): lane 16 g + m holds W[16 mtile + m][32 ks + 8 g + e], e = 0..7; hi then lo
             _Float16* frag = reinterpret_cast<_Float16*>(mf) + ((long)((co >> 4) * KS32 + (kcol >> 5)) * 2) * 512;
             const int slot = (((kcol & 31) >> 3) * 16 + (co & 15)) * 8 + (kcol & 7);
             const _Float16 hi = (_Float16)acc;
             frag[slot] = hi;
             frag[512 + slot] = (_Float16)(acc - (float)hi);
-        } else if (a.split) {
+        } else if (a.split != FIN_PACKED) {
             // record of (mtile, 16-channel stage): 64 lanes x 4 hi halves, then 64 lanes x 4 lo halves;
             // lane (g, m) slot jj holds W[m][16 stage + 4 jj + g]
             _Float16* rec = reinterpret_cast<_Float16*>(mf + ((long)(co >> 4) * (a.ksteps >> 2) + (kcol >> 4)) * 256);
@@ -759,18 +765,18 @@ static int mdta_finalize(const float* part, float* gsum, const float* temperatur
 extern "C" int irm_mdta_finalize_f32(const float* part, float* gsum, const float* temperature,
                                      const float* wout, float* mfold, float* attn, int B, int C, int heads,
                                      int nchunk, hipStream_t stream) {
-    return mdta_finalize(part, gsum, temperature, wout, mfold, attn, B, C, heads, nchunk, 0, stream);
+    return mdta_finalize(part, gsum, temperature, wout, mfold, attn, B, C, heads, nchunk, FIN_PACKED, stream);
 }
 
 extern "C" int irm_mdta_finalize_frag_f16x3_f32(const float* part, float* gsum, const float* temperature,
                                                 const float* wout, float* mfold_frag, float* attn, int B, int C,
                                                 int heads, int nchunk, hipStream_t stream) {
     if (C & 15) return IRM_EINVAL;
-    return mdta_finalize(part, gsum, temperature, wout, mfold_frag, attn, B, C, heads, nchunk, 2, stream);
+    return mdta_finalize(part, gsum, temperature, wout, mfold_frag, attn, B, C, heads, nchunk, FIN_FRAG, stream);
 }
 
 extern "C" int irm_mdta_finalize_f16x3_f32(const float* part, float* gsum, const float* temperature,
                                            const float* wout, float* mfold_split, float* attn, int B, int C,
                                            int heads, int nchunk, hipStream_t stream) {
-    return mdta_finalize(part, gsum, temperature, wout, mfold_split, attn, B, C, heads, nchunk, 1, stream);
+    return mdta_finalize(part, gsum, temperature, wout, mfold_split, attn, B, C, heads, nchunk, FIN_SPLIT, stream);
 }

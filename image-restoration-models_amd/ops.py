@@ -389,6 +389,15 @@ def mdta_plan(B: int, C: int, heads: int, N: int):
 QKV_GRAM_NCH = 4          # tiles per partial Gram record of the Gram-fused qkv kernel (QC_NCH in fused_qkv_cm.hip)
 
 
+def gram_part_plan(B: int, C: int, heads: int, H: int, W: int, *, tiled: bool):
+    """(nchunk, record size) of the partial Gram records per (image, head): tiled, one record per QKV_GRAM_NCH tiles of
+    8 x 32 pixels (qkv_gram_cm, dw_gram); otherwise the Gram pass's own plan (mdta_plan)."""
+    if tiled:
+        c = C // heads
+        return (H // 8) * (W // 32) // QKV_GRAM_NCH, c * c + 2 * c
+    return mdta_plan(B, C, heads, H * W)[1:]
+
+
 def can_qkv_gram(C: int, heads: int, H: int, W: int) -> bool:
     """qkv_gram_cm: the Gram partials inside the qkv kernel (q, k never written): C = 48 with one head, whole tiles in
     chunks of QKV_GRAM_NCH."""
@@ -403,8 +412,8 @@ def qkv_gram_cm(pk, x, y, gram_scale, part, C: int, *, ln_mode, eps: float = 1e-
     assert can_qkv_gram(C, 1, H, W) and y.shape[1] == 3 * C and gram_scale.numel() == 2 * C
     rec, inv_s1 = pk
     N = H * W
-    nchunk = (H // 8) * (W // 32) // QKV_GRAM_NCH
-    assert part.numel() >= B * nchunk * (C * C + 2 * C)
+    nchunk, nrec = gram_part_plan(B, C, 1, H, W, tiled=True)
+    assert part.numel() >= B * nchunk * nrec
     _launch("qkv_dw_fused", B * N * (2.0 * 3 * C * C + 18.0 * 3 * C + 2.0 * C * C), 4.0 * B * N * 2 * C, "irm_qkv_gram_cm_f16x3_f32",
             _hip.ptr(rec), _hip.ptr(x), _bs(x), _hip.ptr(y), _bs(y), _hip.ptr(gram_scale), _hip.ptr(part), int(ln_mode),
             float(eps), float(inv_s1), B, C, H, W, int(x_tm), int(v_tm), tag=f"C{C} {H}x{W} B{B} gram")
@@ -429,8 +438,8 @@ def dw_gram(qkv, w9, gram_scale, part, C: int, heads: int, *, bias=None) -> int:
     N = H * W
     assert can_dw_gram(C, heads, H, W) and qkv.shape[1] >= 2 * C and gram_scale.numel() == 2 * C and gram_scale.is_contiguous()
     assert w9.shape == (2 * C, 9) and w9.is_contiguous() and (bias is None or (bias.numel() == 2 * C and bias.is_contiguous()))
-    nchunk = (H // 8) * (W // 32) // QKV_GRAM_NCH
-    assert part.numel() >= B * heads * nchunk * (48 * 48 + 96)
+    nchunk, nrec = gram_part_plan(B, C, heads, H, W, tiled=True)
+    assert part.numel() >= B * heads * nchunk * nrec
     _launch("dw_gram", B * N * (18.0 * 2 * C + 2.0 * 48 * C), 4.0 * B * N * 2 * C, "irm_dw_gram_cm_f16x3_f32", _hip.ptr(qkv),
             _bs(qkv), _hip.ptr(w9), _hip.ptr(bias), _hip.ptr(gram_scale), _hip.ptr(part), B, C, heads, H, W,
             tag=f"C{C} h{heads} {H}x{W} B{B}")

@@ -265,9 +265,7 @@ class Restormer(ModelHost):
         fuse_dw = "v_dwp" in w and ops.can_fuse_dw(C, W)
         # C = 192 / 384: the Gram pass reads raw q, k and runs their depth-wise conv itself - dw(q), dw(k) are never written
         gram_dw = split and "gram_s" in w and "qk_dw" in w and ops.can_dw_gram(C, heads, H, W)
-        _, nchunk, rec = ops.mdta_plan(B, C, heads, N)
-        if gram_dw:
-            nchunk = (H // 8) * (W // 32) // ops.QKV_GRAM_NCH
+        nchunk, rec = ops.gram_part_plan(B, C, heads, H, W, tiled=gram_dw)
         part = self._buf("gram_part", B * heads * nchunk * rec, dev)
         nready = None
         if gram_dw:
@@ -339,10 +337,8 @@ class Restormer(ModelHost):
         assert not (x_tm or y_tm) or (tm and fa), "tile-major x / y: only between the kernels that understand them"
         v_tm = tm and fa
         gram_in_qkv = tm and "gram_s" in w and ops.can_qkv_gram(C, heads, H, W)
-        _, nchunk, rec = ops.mdta_plan(B, C, heads, N)
+        nchunk, rec = ops.gram_part_plan(B, C, heads, H, W, tiled=gram_in_qkv)
         nready = None
-        if gram_in_qkv:
-            nchunk = (H // 8) * (W // 32) // ops.QKV_GRAM_NCH
         part = self._buf("gram_part", B * heads * nchunk * rec, dev)
         if gram_in_qkv:
             # C = 48, one head: the Gram partials come out of the qkv kernel, q and k are never written
