@@ -303,7 +303,12 @@ def param_key(module):
     load_state_dict(assign=True), is seen and the list rebuilt) and folds every parameter's storage address and
     `_version` (in-place updates, load_state_dict, optimiser steps, `.to()` / `.float()`) into the key: ~0.1 ms for
     Restormer's 700 tensors.  NOT seen: writes through `p.data` (`.data` carries its own version counter) - after such
-    a write call `_hip.invalidate(module)`."""
+    a write call `_hip.invalidate(module)`.
+
+    A module of the tree with a `mode_key()` method (host.ModelHost) adds that value: state outside the parameters
+    that selects another packing or another forward (a conv stack's `precision`), and what the addresses cannot
+    vouch for (the count of dtype / device conversions, whose new storages may reuse the old addresses, and of the
+    `invalidate` calls that reached that model)."""
     d = module.__dict__
     slots = d.get("_irm_pslots")
     if slots is not None:
@@ -314,23 +319,30 @@ def param_key(module):
     if slots is None:
         slots = [(m._parameters, n, p) for m in module.modules() for n, p in m._parameters.items() if p is not None]
         d["_irm_pslots"] = slots
+        d["_irm_modes"] = [m.mode_key for m in module.modules() if callable(getattr(m, "mode_key", None))]
         d["_irm_pgen"] = d.get("_irm_pgen", 0) + 1
+    modes = tuple(f() for f in d["_irm_modes"])
     if not slots:
-        return (None, 0, 0, d.get("_irm_pgen", 0))
+        return (None, 0, 0, d.get("_irm_pgen", 0), modes)
     ver, addr = 0, 0
     for i, (_, _, p) in enumerate(slots):
         ver += p._version
         addr ^= p.data_ptr() * (2 * i + 1)
-    return (str(slots[0][2].device), addr, ver, d["_irm_pgen"])
+    return (str(slots[0][2].device), addr, ver, d["_irm_pgen"], modes)
 
 
 def invalidate(module):
     """Drop every cache derived from the module's weights (packed operands, HIP graphs): required after writes that
-    param_key cannot see (`p.data.copy_()`, raw pointer writes)."""
-    d = module.__dict__
-    d.pop("_irm_pslots", None)
-    d["_irm_pgen"] = d.get("_irm_pgen", 0) + 1
-    d.pop("_irm_graphs", None)
+    param_key cannot see (`p.data.copy_()`, raw pointer writes).  Reaches the caches of every model below `module`
+    (a wrapper's network packs under its own key) and, through mode_key(), those of every module above it."""
+    for m in module.modules():
+        d = m.__dict__
+        if m is module or "_irm_pslots" in d or callable(getattr(m, "mode_key", None)):
+            d.pop("_irm_pslots", None)
+            d.pop("_irm_modes", None)
+            d.pop("_irm_graphs", None)
+            d["_irm_pgen"] = d.get("_irm_pgen", 0) + 1
+            d["_irm_inval"] = d.get("_irm_inval", 0) + 1
 
 
 def gram_scales(qkv_w, qkv_b, dw_w, dw_b, lnw, lnb, ln_with_bias: bool):

@@ -17,6 +17,25 @@ def check_precision(precision, what, features=None):
     return precision
 
 
+class PrecisionMode:
+    """`precision` of a conv stack as a validated attribute that the caches are keyed on.  Mixed in before ModelHost:
+    an assignment after construction is checked as the constructor's keyword is, and mode_key() carries the value
+    into _hip.param_key, so the packed weights and the HIP graphs of the other mode are never handed to this one.  The
+    class names the attribute that holds its hidden width in WIDTH_ATTR and sets it before `precision`."""
+    WIDTH_ATTR = None
+
+    @property
+    def precision(self):
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        self._precision = check_precision(value, type(self).__name__, getattr(self, self.WIDTH_ATTR))
+
+    def mode_key(self):
+        return super().mode_key() + (self._precision,)
+
+
 def half_workspace(ws, key, names, shape, device):
     """fp16 channel-last buffers `names` of `shape` [B, H, W, C], kept in the dict `ws` while `key` is unchanged."""
     if ws.get("key") != key:

@@ -14,16 +14,18 @@ import torch.nn as nn
 
 from ... import _hip, ops
 from .. import SYNTH_RULES
-from ...convnet_common import check_precision, half_workspace
+from ...convnet_common import PrecisionMode, half_workspace
 from ...host import ModelHost, f32
 
 
-class DnCNN(ModelHost):
+class DnCNN(PrecisionMode, ModelHost):
     SYNTH_RULES = SYNTH_RULES
+    WIDTH_ATTR = "nc"
 
     def __init__(self, in_nc=1, out_nc=1, nc=64, nb=17, act_mode='BR', precision="fp32"):
         super().__init__()
-        self.precision = check_precision(precision, "DnCNN", nc)
+        self.nc = nc
+        self.precision = precision
         if 'B' in act_mode:
             raise NotImplementedError("inference uses BN-merged weights (act_mode='R', src/dncnn/__init__.py:8)")
         assert 'R' in act_mode, 'only ReLU activation is used by the reference loader'
@@ -60,7 +62,7 @@ class DnCNN(ModelHost):
         x = x.float().contiguous()
         B, _, H, W = x.shape
         layers = self._pack()
-        key = (B, H, W, str(x.device))
+        key = (B, H, W, str(x.device), self.precision)
         if self.precision == "fp16":
             return self._forward_half(x, layers, key)
         if self._ws.get("key") != key:

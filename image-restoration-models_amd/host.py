@@ -30,6 +30,22 @@ class ModelHost(nn.Module):
         super().__init__()
         self._packed, self._packed_key = None, None
         self._ws_by_stream = {}
+        self._converted = 0
+
+    # ------------------------------------------------------------------ cache keys
+    def mode_key(self):
+        """Everything but the parameters that decides what _build() and forward() do, as a hashable value:
+        _hip.param_key folds it into the key of the packed weights and of the HIP graphs, for this model and for
+        every module that wraps it.  The base part counts the conversions (`.half()`, `.float()`, `.to()`): they
+        replace every parameter's storage without touching its version, and the allocator may hand the old
+        addresses back; and the calls of _hip.invalidate that reached this model, so that a wrapper's graphs go with
+        them.  A model with a mode of its own (the conv stacks' `precision`) appends it."""
+        return (self._converted, self.__dict__.get("_irm_inval", 0))
+
+    def _apply(self, fn, *args, **kw):
+        out = super()._apply(fn, *args, **kw)
+        self._converted += 1
+        return out
 
     # ------------------------------------------------------------------ weights
     def load_synthetic(self, seed=42):
@@ -44,7 +60,7 @@ class ModelHost(nn.Module):
         raise NotImplementedError
 
     def _pack(self):
-        """The cached result of _build(), rebuilt when the parameters change (_hip.param_key)."""
+        """The cached result of _build(), rebuilt when the parameters or the mode change (_hip.param_key)."""
         key = _hip.param_key(self)
         if self._packed is None or key != self._packed_key:
             self._packed, self._packed_key = self._build(), key

@@ -13,17 +13,18 @@ import torch.nn as nn
 
 from .. import _hip, ops
 from . import SYNTH_RULES
-from ..convnet_common import check_precision, half_workspace
+from ..convnet_common import PrecisionMode, half_workspace
 from ..host import ModelHost, f32
 
 
-class REDNet(ModelHost):
+class REDNet(PrecisionMode, ModelHost):
     SYNTH_RULES = SYNTH_RULES
+    WIDTH_ATTR = "num_features"
 
     def __init__(self, num_channels=1, num_features=128, precision="fp32"):
         super().__init__()
-        self.precision = check_precision(precision, "REDNet", num_features)
         self.num_channels, self.num_features = num_channels, num_features
+        self.precision = precision
         for i in range(1, 16):
             setattr(self, f"conv{i}", nn.Conv2d(num_channels if i == 1 else num_features, num_features, 3, padding=1))
         for i in range(1, 16):
@@ -90,7 +91,7 @@ class REDNet(ModelHost):
         F = self.num_features
         # the features the decoder adds back (c2, c4 ... c14) own a buffer each, everything else ping-pongs
         skips = tuple(f"c{k}" for k in range(2, 15, 2))
-        ws = half_workspace(self._ws, (B, H, W, str(x.device)), ("a", "b") + skips, (B, H, W, F), x.device)
+        ws = half_workspace(self._ws, (B, H, W, str(x.device), self.precision), ("a", "b") + skips, (B, H, W, F), x.device)
 
         def other(t):
             return ws["b"] if t is ws["a"] else ws["a"]
