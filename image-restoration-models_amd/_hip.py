@@ -79,7 +79,7 @@ SIGNATURES_HALF = {
     "irm_conv3x3_h_out_f32": [_P, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P],
 }
 
-#: float32 frames in the tiled-patch loop (tiler_f32.hip), mirrors include/irm_hip_frames.h one to one
+#: float32 frames in the tiled-patch loop (tiler_f32.hip; the tile walk in irm_frame.h), mirrors include/irm_hip_frames.h one to one
 SIGNATURES_FRAMES = {
     "irm_frame_minmax_f32": [_P, _L, _P, _P, _L, _P],
     "irm_tile_extract_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -4,7 +4,7 @@
 // per-(sample, channel) normalisation over H x W with the biased variance: irm_chan_stats_f32 +
 // irm_chan_norm_act_f32.  The remaining pieces are the stride-2 stem conv, the stride-2 depth-wise conv
 // and nearest-neighbour up-sampling (+ lateral add).  All HBM-bound, planar NCHW.
-#include "irm_common.h"
+#include "irm_frame.h"
 
 #define IRM_ACT_RELU6 4
 
@@ -15,16 +15,6 @@
 // constant up to its border (a checkered frame behind the stride-2 stem), and a float32 sum of a few
 // thousand nearly equal values leaves the mean several ulps off - the reference's float32 norm accumulates
 // in float64 too.  The kernel stays bound by its loads.
-__device__ __forceinline__ double block_sum256d(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
 __global__ __launch_bounds__(256) void chan_stats_kernel(const float* __restrict__ x, long x_bs, float* __restrict__ st,
                                                          int C, int N, float eps) {
     __shared__ double sh[4];
@@ -32,10 +22,10 @@ __global__ __launch_bounds__(256) void chan_stats_kernel(const float* __restrict
     const float* p = x + (long)b * x_bs + (long)c * N;
     double s = 0.0;
     for (int i = threadIdx.x; i < N; i += 256) s += (double)p[i];
-    const double mean = block_sum256d(s, sh) / (double)N;
+    const double mean = irm_block_reduce256<FrSum, true>(s, sh) / (double)N;     // (true: `sh` serves both sums)
     double q = 0.0;
     for (int i = threadIdx.x; i < N; i += 256) { const double d = (double)p[i] - mean; q += d * d; }
-    const double var = block_sum256d(q, sh) / (double)N;
+    const double var = irm_block_reduce256<FrSum, true>(q, sh) / (double)N;
     if (threadIdx.x == 0) {
         st[((long)b * C + c) * 2] = (float)mean;
         st[((long)b * C + c) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));

@@ -12,7 +12,13 @@
 // Reproducibility: each workgroup writes its fp64 SSIM sum and u64 SSE to its own workspace slot (a fixed order inside
 // the workgroup), and a second launch sums a frame's slots in a fixed order.  No atomics: a frame's result does not
 // depend on the run or on how many frames share the launch.
-#include "irm_common.h"
+//
+// Shared with metrics_basicsr.hip through irm_frame.h: the tile geometry (SsimTile), the workspace plan, the block
+// sum and the slot reduction.  The staging and the two window passes stay written out in each file and no shared
+// skeleton was built for them: this one issues all loads of a thread before the first wait and keeps exact integer
+// moments, the other converts while it stages and rounds every fp64 tap on its own, so a policy would carry the
+// accumulator type, the taps, the load schedule and the squared-error arithmetic - the whole loop body.
+#include "irm_frame.h"
 
 #define MT_ROWS 16                     // output rows per tile
 #define MT_OUT 192                     // output values (pixel x channel) per tile row: 64 RGB or 192 grey pixels
@@ -26,44 +32,25 @@ struct MetricsArgs {
     double k1, k2;                     // 49^2 c1, 49*48 c2 (c1 = (0.01 R)^2, c2 = (0.03 R)^2)
 };
 
-// Sum over a workgroup of 256 threads in a fixed order: butterfly in each wave, then the four waves in order.
-template <typename V>
-__device__ __forceinline__ V block_sum256(V v, V* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return part[0] + part[1] + part[2] + part[3];
-}
-
 // One workgroup: MT_ROWS output rows x (MT_OUT / C) output pixels of one frame.  The tile plus its 3-pixel halo is
 // staged in LDS (a thread issues all its loads before it waits for the first); per output row, each thread forms the
 // 7-row vertical moments of one loaded column, then each thread sums 7 of those horizontally for one output value and
 // evaluates its SSIM.
 template <typename T, typename A, int C>
 __global__ __launch_bounds__(256) void ssim_tile_kernel(MetricsArgs a) {
-    constexpr int twp = MT_OUT / C, rw = (twp + 6) * C;     // output pixels, loaded values per tile row
+    using Tile = SsimTile<MT_ROWS, MT_OUT, 6, C>;
+    constexpr int rw = Tile::rw;                            // loaded values per tile row
     constexpr int NLD = ((MT_ROWS + 6) * rw + 255) / 256;   // loads per thread
     __shared__ T sx[MT_ROWS + 6][rw], sy[MT_ROWS + 6][rw];
     __shared__ A vm[5][rw];
     __shared__ double dpart[4];
     __shared__ unsigned long long upart[4];
-    const int Ho = a.H - 6, Wo = a.W - 6;
-    const int tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x, k = blockIdx.y;
-    const int ox0 = tx * twp, oy0 = ty * MT_ROWS;
+    const Tile tg(a.H, a.W, a.tiles_x, a.tiles_y, blockIdx.x);
+    const int ox0 = tg.ox0, oy0 = tg.oy0, nrow = tg.nrow, ncol = tg.ncol, k = blockIdx.y;
     const long frame = (long)k * a.H * a.W * C;
     const T* P = reinterpret_cast<const T*>(a.pred) + frame;
     const T* Q = reinterpret_cast<const T*>(a.target) + frame;
 
-    // loaded region: image rows [oy0, oy0 + nrow), row values [ox0*C, ox0*C + ncol)
-    const int nrow = min(MT_ROWS + 6, a.H - oy0);
-    const int ncol = min(rw, (a.W - ox0) * C);
-    // SSE ownership: the tile's output centres, widened to the image border for the first / last tile of a row or
-    // column, so that the tiles of a frame partition it exactly
-    const int cy0 = ty == 0 ? 0 : oy0 + 3;
-    const int cy1 = ty == a.tiles_y - 1 ? a.H : oy0 + MT_ROWS + 3;
-    const int cx0 = (tx == 0 ? 0 : ox0 + 3) * C;
-    const int cx1 = (tx == a.tiles_x - 1 ? a.W : ox0 + twp + 3) * C;
     // unconditional loads (outside the region: the frame's first value, replaced by 0), so none waits for another
     T xr[NLD], yr[NLD];
 #pragma unroll
@@ -81,7 +68,7 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(MetricsArgs a) {
         const int i = threadIdx.x + u * 256, ly = i / rw, lj = i - ly * rw;
         if (ly < MT_ROWS + 6) {
             const int gy = oy0 + ly, gj = ox0 * C + lj;
-            if (gy >= cy0 && gy < cy1 && gj >= cx0 && gj < cx1) {   // (owned values lie inside the loaded region)
+            if (tg.owns(gy, gj)) {                        // (owned values lie inside the loaded region)
                 const long d = (long)xr[u] - (long)yr[u];
                 err += (unsigned long long)(d * d);
             }
@@ -91,8 +78,7 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(MetricsArgs a) {
     }
     __syncthreads();
 
-    const int nout_rows = min(MT_ROWS, Ho - oy0);
-    const int nout = min(twp, Wo - ox0) * C;     // valid output values per row; their windows lie inside ncol
+    const int nout_rows = tg.nout_rows, nout = tg.nout;
     const int t = threadIdx.x;
     double acc = 0.0;
 #pragma unroll 1
@@ -138,8 +124,8 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(MetricsArgs a) {
         __syncthreads();
     }
 
-    const unsigned long long e = block_sum256(err, upart);
-    const double s = block_sum256(acc, dpart);
+    const unsigned long long e = irm_block_reduce256<FrSum>(err, upart);
+    const double s = irm_block_reduce256<FrSum>(acc, dpart);
     if (threadIdx.x == 0) {
         const long slot = (long)k * a.tiles_x * a.tiles_y + blockIdx.x;
         a.sse_part[slot] = e;
@@ -147,48 +133,24 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(MetricsArgs a) {
     }
 }
 
-// One workgroup per frame: its tile slots summed in a fixed order.
-__global__ __launch_bounds__(256) void metrics_reduce_kernel(const unsigned long long* sse_part, const double* ssim_part,
-                                                             int ntiles, double count, unsigned long long* sse,
-                                                             double* ssim) {
-    __shared__ double dpart[4];
-    __shared__ unsigned long long upart[4];
-    const long base = (long)blockIdx.x * ntiles;
-    unsigned long long e = 0;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < ntiles; j += 256) {
-        e += sse_part[base + j];
-        s += ssim_part[base + j];
-    }
-    e = block_sum256(e, upart);
-    s = block_sum256(s, dpart);
-    if (threadIdx.x == 0) {
-        sse[blockIdx.x] = e;
-        ssim[blockIdx.x] = s / count;
-    }
-}
-
 extern "C" int irm_frame_metrics(const void* pred, const void* target, int is_u16, int K, int H, int W, int C,
                                  double data_range, unsigned long long* sse, double* ssim, void* ws, long ws_words,
                                  hipStream_t stream) {
     if (!pred || !target || !sse || !ssim || !ws) return IRM_EINVAL;
-    if ((is_u16 != 0 && is_u16 != 1) || K <= 0 || K > 65535 || H < 7 || W < 7 || (C != 1 && C != 3)) return IRM_EINVAL;
-    if (!(data_range > 0.0) || (long)H * W * C > 0x7fffffffL) return IRM_EINVAL;
-    const int tiles_x = (W - 6 + MT_OUT / C - 1) / (MT_OUT / C), tiles_y = (H - 6 + MT_ROWS - 1) / MT_ROWS;
-    const long ntiles = (long)tiles_x * tiles_y;
-    if (ws_words < 2 * K * ntiles) return IRM_EINVAL;
-    unsigned long long* sse_part = reinterpret_cast<unsigned long long*>(ws);
-    double* ssim_part = reinterpret_cast<double*>(sse_part + K * ntiles);
+    if (!irm_frames_ok(is_u16, K, H, W, C) || H < 7 || W < 7 || !(data_range > 0.0)) return IRM_EINVAL;
+    SsimPlan p;
+    if (!irm_ssim_plan(p, H - 6, W - 6, MT_ROWS, MT_OUT / C, K, ws, ws_words)) return IRM_EINVAL;
     const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
-    MetricsArgs a{pred, target, sse_part, ssim_part, H, W, tiles_x, tiles_y, 2401.0 * c1, 2352.0 * c2};
-    const dim3 grid((unsigned)ntiles, K);
-    if (is_u16 && C == 3) hipLaunchKernelGGL((ssim_tile_kernel<unsigned short, long long, 3>), grid, dim3(256), 0, stream, a);
-    else if (is_u16) hipLaunchKernelGGL((ssim_tile_kernel<unsigned short, long long, 1>), grid, dim3(256), 0, stream, a);
-    else if (C == 3) hipLaunchKernelGGL((ssim_tile_kernel<unsigned char, int, 3>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((ssim_tile_kernel<unsigned char, int, 1>), grid, dim3(256), 0, stream, a);
+    MetricsArgs a{pred, target, p.sse_part, p.ssim_part, H, W, p.tiles_x, p.tiles_y, 2401.0 * c1, 2352.0 * c2};
+    const dim3 grid((unsigned)p.ntiles, K);
+    irm_dispatch_frames(is_u16, C, [&](auto kind) {
+        using T = typename decltype(kind)::type;
+        using A = std::conditional_t<sizeof(T) == 1, int, long long>;       // the exact window moments: see the head
+        hipLaunchKernelGGL((ssim_tile_kernel<T, A, decltype(kind)::C>), grid, dim3(256), 0, stream, a);
+    });
     if (hipGetLastError() != hipSuccess) return IRM_ELAUNCH;
     const double count = (double)C * (H - 6) * (W - 6);   // interior values of one frame
-    hipLaunchKernelGGL(metrics_reduce_kernel, dim3(K), dim3(256), 0, stream, sse_part, ssim_part, (int)ntiles, count,
-                       sse, ssim);
+    hipLaunchKernelGGL(ssim_reduce_kernel<false>, dim3(K), dim3(256), 0, stream, p.sse_part, p.ssim_part, (int)p.ntiles,
+                       count, sse, ssim);
     return irm_launch_status();
 }

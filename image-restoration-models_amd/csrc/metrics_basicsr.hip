@@ -12,7 +12,7 @@
 // Reproducibility as in metrics.hip: each workgroup writes its partials to its own workspace slot (a fixed order inside
 // the workgroup), a second launch sums a frame's slots in a fixed order.  No atomics; a frame's result does not depend
 // on K or on the run.  The final SSIM ratio uses explicitly rounded operations, so identical frames give exactly 1.
-#include "irm_common.h"
+#include "irm_frame.h"
 
 #define BT_ROWS 16                     // output rows per tile
 #define BT_OUT 192                     // output values (pixel x kept channel) per tile row
@@ -28,15 +28,6 @@ struct BasicsrArgs {
     double c1, c2;
     double g[11];                      // the normalised window
 };
-
-template <typename V>
-__device__ __forceinline__ V bt_block_sum256(V v, V* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return part[0] + part[1] + part[2] + part[3];
-}
 
 // s + g v with the product and the sum each rounded (no FMA): the window sums are then the numbers the host restatement's
 // numpy expressions give, tap by tap in ascending order
@@ -60,28 +51,18 @@ __device__ __forceinline__ float bt_value(const T* p, int j, float range, int bg
 template <typename T, int C, bool Y>
 __global__ __launch_bounds__(256) void basicsr_tile_kernel(BasicsrArgs a) {
     constexpr int CE = Y ? 1 : C;
-    constexpr int twp = BT_OUT / CE, rw = (twp + BT_HALO) * CE;
+    using Tile = SsimTile<BT_ROWS, BT_OUT, BT_HALO, CE>;
+    constexpr int rw = Tile::rw;
     __shared__ float sx[BT_ROWS + BT_HALO][rw], sy[BT_ROWS + BT_HALO][rw];
     __shared__ double vm[5][rw];
     __shared__ double dpart[4], epart[4];
     __shared__ unsigned long long upart[4];
-    const int Hc = a.H - 2 * a.crop, Wc = a.W - 2 * a.crop;
-    const int Ho = Hc - BT_HALO, Wo = Wc - BT_HALO;
-    const int tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x, k = blockIdx.y;
-    const int ox0 = tx * twp, oy0 = ty * BT_ROWS;
+    const Tile tg(a.H - 2 * a.crop, a.W - 2 * a.crop, a.tiles_x, a.tiles_y, blockIdx.x);
+    const int ox0 = tg.ox0, oy0 = tg.oy0, nrow = tg.nrow, ncol = tg.ncol, k = blockIdx.y;
     const long frame = (long)k * a.H * a.W * C + ((long)a.crop * a.W + a.crop) * C;
     const T* P = reinterpret_cast<const T*>(a.pred) + frame;
     const T* Q = reinterpret_cast<const T*>(a.target) + frame;
 
-    // staged region: cropped rows [oy0, oy0 + nrow), kept values [ox0 * CE, ox0 * CE + ncol) of each
-    const int nrow = min(BT_ROWS + BT_HALO, Hc - oy0);
-    const int ncol = min(rw, (Wc - ox0) * CE);
-    // SSE ownership: the tile's output centres, widened to the border for the first / last tile of a row or column, so
-    // that the tiles of a frame partition the cropped frame exactly
-    const int cy0 = ty == 0 ? 0 : oy0 + 5;
-    const int cy1 = ty == a.tiles_y - 1 ? Hc : oy0 + BT_ROWS + 5;
-    const int cx0 = (tx == 0 ? 0 : ox0 + 5) * CE;
-    const int cx1 = (tx == a.tiles_x - 1 ? Wc : ox0 + twp + 5) * CE;
     unsigned long long err = 0;
     double errd = 0.0;
     for (int i = threadIdx.x; i < nrow * ncol; i += 256) {
@@ -92,7 +73,7 @@ __global__ __launch_bounds__(256) void basicsr_tile_kernel(BasicsrArgs a) {
         sx[ly][lj] = xv;
         sy[ly][lj] = yv;
         const int gy = oy0 + ly, gj = ox0 * CE + lj;
-        if (gy >= cy0 && gy < cy1 && gj >= cx0 && gj < cx1) {
+        if (tg.owns(gy, gj)) {
             if (Y) {
                 const double d = (double)xv - (double)yv;
                 errd = __dadd_rn(errd, __dmul_rn(d, d));
@@ -104,8 +85,7 @@ __global__ __launch_bounds__(256) void basicsr_tile_kernel(BasicsrArgs a) {
     }
     __syncthreads();
 
-    const int nout_rows = min(BT_ROWS, Ho - oy0);
-    const int nout = min(twp, Wo - ox0) * CE;    // valid output values per row; their windows lie inside ncol
+    const int nout_rows = tg.nout_rows, nout = tg.nout;
     const int t = threadIdx.x;
     double acc = 0.0;
 #pragma unroll 1
@@ -151,44 +131,16 @@ __global__ __launch_bounds__(256) void basicsr_tile_kernel(BasicsrArgs a) {
         __syncthreads();
     }
 
-    const double s = bt_block_sum256(acc, dpart);
+    const double s = irm_block_reduce256<FrSum>(acc, dpart);
     const long slot = (long)k * a.tiles_x * a.tiles_y + blockIdx.x;
     if (Y) {
-        const double e = bt_block_sum256(errd, epart);
+        const double e = irm_block_reduce256<FrSum>(errd, epart);
         if (threadIdx.x == 0) a.sse_part[slot] = (unsigned long long)__double_as_longlong(e);
     } else {
-        const unsigned long long e = bt_block_sum256(err, upart);
+        const unsigned long long e = irm_block_reduce256<FrSum>(err, upart);
         if (threadIdx.x == 0) a.sse_part[slot] = e;
     }
     if (threadIdx.x == 0) a.ssim_part[slot] = s;
-}
-
-// One workgroup per frame: its tile slots summed in a fixed order.
-template <bool Y>
-__global__ __launch_bounds__(256) void basicsr_reduce_kernel(const unsigned long long* sse_part, const double* ssim_part,
-                                                             int ntiles, double count, unsigned long long* sse,
-                                                             double* ssim) {
-    __shared__ double dpart[4], epart[4];
-    __shared__ unsigned long long upart[4];
-    const long base = (long)blockIdx.x * ntiles;
-    unsigned long long e = 0;
-    double ed = 0.0, s = 0.0;
-    for (int j = threadIdx.x; j < ntiles; j += 256) {
-        if (Y) ed += __longlong_as_double((long long)sse_part[base + j]);
-        else e += sse_part[base + j];
-        s += ssim_part[base + j];
-    }
-    s = bt_block_sum256(s, dpart);
-    if (Y) {
-        ed = bt_block_sum256(ed, epart);
-        e = (unsigned long long)__double_as_longlong(ed);
-    } else {
-        e = bt_block_sum256(e, upart);
-    }
-    if (threadIdx.x == 0) {
-        sse[blockIdx.x] = e;
-        ssim[blockIdx.x] = s / count;
-    }
 }
 
 template <typename T, int C>
@@ -201,19 +153,15 @@ extern "C" int irm_frame_metrics_basicsr(const void* pred, const void* target, i
                                          int crop_border, int test_y_channel, int bgr, void* sse, double* ssim, void* ws,
                                          long ws_words, hipStream_t stream) {
     if (!pred || !target || !sse || !ssim || !ws) return IRM_EINVAL;
-    if ((is_u16 != 0 && is_u16 != 1) || (test_y_channel != 0 && test_y_channel != 1) || (bgr != 0 && bgr != 1)) return IRM_EINVAL;
-    if (K <= 0 || K > 65535 || (C != 1 && C != 3) || crop_border < 0 || H <= 0 || W <= 0) return IRM_EINVAL;
-    if ((long)H * W * C > 0x7fffffffL || crop_border > 16384) return IRM_EINVAL;
+    if (!irm_frames_ok(is_u16, K, H, W, C) || !irm_is_flag(test_y_channel) || !irm_is_flag(bgr)) return IRM_EINVAL;
+    if (crop_border < 0 || crop_border > 16384) return IRM_EINVAL;
     const int Hc = H - 2 * crop_border, Wc = W - 2 * crop_border;
     if (Hc < 11 || Wc < 11) return IRM_EINVAL;
     const int CE = test_y_channel ? 1 : C;
-    const int tiles_x = (Wc - BT_HALO + BT_OUT / CE - 1) / (BT_OUT / CE), tiles_y = (Hc - BT_HALO + BT_ROWS - 1) / BT_ROWS;
-    const long ntiles = (long)tiles_x * tiles_y;
-    if (ws_words < 2 * K * ntiles) return IRM_EINVAL;
-    unsigned long long* sse_part = reinterpret_cast<unsigned long long*>(ws);
-    double* ssim_part = reinterpret_cast<double*>(sse_part + K * ntiles);
+    SsimPlan p;
+    if (!irm_ssim_plan(p, Hc - BT_HALO, Wc - BT_HALO, BT_ROWS, BT_OUT / CE, K, ws, ws_words)) return IRM_EINVAL;
     const double R = is_u16 ? 65535.0 : 255.0;
-    BasicsrArgs a{pred, target, sse_part, ssim_part, H, W, crop_border, tiles_x, tiles_y, bgr, (float)R,
+    BasicsrArgs a{pred, target, p.sse_part, p.ssim_part, H, W, crop_border, p.tiles_x, p.tiles_y, bgr, (float)R,
                   (0.01 * R) * (0.01 * R), (0.03 * R) * (0.03 * R), {}};
     double gs = 0.0;
     for (int i = 0; i < 11; ++i) {
@@ -221,19 +169,18 @@ extern "C" int irm_frame_metrics_basicsr(const void* pred, const void* target, i
         gs += a.g[i];
     }
     for (int i = 0; i < 11; ++i) a.g[i] /= gs;
-    const dim3 grid((unsigned)ntiles, K);
-    if (is_u16 && C == 3) launch_basicsr<unsigned short, 3>(a, test_y_channel, grid, stream);
-    else if (is_u16) launch_basicsr<unsigned short, 1>(a, test_y_channel, grid, stream);
-    else if (C == 3) launch_basicsr<unsigned char, 3>(a, test_y_channel, grid, stream);
-    else launch_basicsr<unsigned char, 1>(a, test_y_channel, grid, stream);
+    const dim3 grid((unsigned)p.ntiles, K);
+    irm_dispatch_frames(is_u16, C, [&](auto kind) {
+        launch_basicsr<typename decltype(kind)::type, decltype(kind)::C>(a, test_y_channel, grid, stream);
+    });
     if (hipGetLastError() != hipSuccess) return IRM_ELAUNCH;
     const double count = (double)CE * (Hc - BT_HALO) * (Wc - BT_HALO);
     unsigned long long* sse_out = reinterpret_cast<unsigned long long*>(sse);
     if (test_y_channel)
-        hipLaunchKernelGGL(basicsr_reduce_kernel<true>, dim3(K), dim3(256), 0, stream, sse_part, ssim_part, (int)ntiles,
+        hipLaunchKernelGGL(ssim_reduce_kernel<true>, dim3(K), dim3(256), 0, stream, p.sse_part, p.ssim_part, (int)p.ntiles,
                            count, sse_out, ssim);
     else
-        hipLaunchKernelGGL(basicsr_reduce_kernel<false>, dim3(K), dim3(256), 0, stream, sse_part, ssim_part, (int)ntiles,
+        hipLaunchKernelGGL(ssim_reduce_kernel<false>, dim3(K), dim3(256), 0, stream, p.sse_part, p.ssim_part, (int)p.ntiles,
                            count, sse_out, ssim);
     return irm_launch_status();
 }

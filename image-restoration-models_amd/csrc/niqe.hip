@@ -20,7 +20,7 @@
 // No atomics and a fixed order everywhere: a block's features are bitwise the same on every run and for any K.  A
 // block without negative (or positive) values divides 0 by 0 and carries the NaN through, as the mean of an empty
 // slice does; every comparison with a NaN distance is false and the search then answers index 0, as argmin does.
-#include "irm_common.h"
+#include "irm_frame.h"
 
 #define NQ_BLOCK 96
 #define NQ_HALO 3
@@ -262,17 +262,14 @@ extern "C" int irm_niqe_features(const void* frames, int is_u16, int K, int H, i
                                  const double* window, const double* table, double* feat, long feat_words,
                                  hipStream_t stream) {
     if (!frames || !window || !table || !feat) return IRM_EINVAL;
-    if ((is_u16 != 0 && is_u16 != 1) || (bgr != 0 && bgr != 1)) return IRM_EINVAL;
-    if (K <= 0 || K > 65535 || (C != 1 && C != 3) || crop_border < 0 || crop_border > 16384 || H <= 0 || W <= 0)
-        return IRM_EINVAL;
-    if ((long)H * W * C > 0x7fffffffL) return IRM_EINVAL;
+    if (!irm_frames_ok(is_u16, K, H, W, C) || !irm_is_flag(bgr)) return IRM_EINVAL;
+    if (crop_border < 0 || crop_border > 16384) return IRM_EINVAL;
     const int nbh = (H - 2 * crop_border) / NQ_BLOCK, nbw = (W - 2 * crop_border) / NQ_BLOCK;
     if (H - 2 * crop_border < NQ_BLOCK || W - 2 * crop_border < NQ_BLOCK || nbh * nbw < 2) return IRM_EINVAL;
     if (feat_words < (long)K * nbh * nbw * 36) return IRM_EINVAL;
     const NiqeArgs a{frames, window, table, feat, H, W, crop_border, nbh, nbw, bgr, is_u16};
     const dim3 grid((unsigned)(2 * nbh * nbw), K);
-    if (is_u16 && C == 3) return launch_niqe<unsigned short, 3>(a, grid, stream);
-    if (is_u16) return launch_niqe<unsigned short, 1>(a, grid, stream);
-    if (C == 3) return launch_niqe<unsigned char, 3>(a, grid, stream);
-    return launch_niqe<unsigned char, 1>(a, grid, stream);
+    return irm_dispatch_frames(is_u16, C, [&](auto kind) {
+        return launch_niqe<typename decltype(kind)::type, decltype(kind)::C>(a, grid, stream);
+    });
 }

@@ -17,7 +17,7 @@
 //
 // LDS: RZ_ROWS rows x ncol columns x C floats, ncol <= floor((tow - 1) / scale) + 1 + P; at 1/4 with tow = 32 that
 // is 8 x 143 x 3 floats = 13.4 KiB, which RZ_LDS_FLOATS is sized for (several workgroups per CU).
-#include "irm_common.h"
+#include "irm_frame.h"
 
 #define RZ_ROWS 8
 #define RZ_LDS_FLOATS (RZ_ROWS * 143 * 3)
@@ -32,16 +32,6 @@ struct ResizeArgs {
     int H, W, OH, OW, PH, PW, tow, tiles_x, ncol_max;
     float range;                       // 255 or 65535
 };
-
-// min over a workgroup of 256 threads (butterfly in each wave, then the four waves); `part` is reused after a barrier
-__device__ __forceinline__ int block_min256(int v, int* part) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return min(min(part[0], part[1]), min(part[2], part[3]));
-}
 
 template <typename T, int C, bool OUT_FLOAT>
 __global__ __launch_bounds__(256) void imresize_kernel(ResizeArgs a) {
@@ -59,8 +49,8 @@ __global__ __launch_bounds__(256) void imresize_kernel(ResizeArgs a) {
         lo = min(lo, c);
         hi = max(hi, c);
     }
-    const int cmin = block_min256(lo, ipart);
-    const int cmax = -block_min256(-hi, ipart);
+    const int cmin = irm_block_reduce256<FrMin, true>(lo, ipart);      // (true: `ipart` serves both reductions)
+    const int cmax = -irm_block_reduce256<FrMin, true>(-hi, ipart);
     const int ncol = min(cmax - cmin + 1, a.ncol_max);        // (<= ncol_max by construction of the table)
     const int rowv = ncol * C;                                // values per intermediate row
 
@@ -109,21 +99,20 @@ extern "C" int irm_imresize_bicubic(const void* in, int is_u16, void* out, int o
                                     const float* ww, const int* iw, int K, int H, int W, int C, int s, int shrink,
                                     hipStream_t stream) {
     if (!in || !out || !wh || !ih || !ww || !iw) return IRM_EINVAL;
-    if ((is_u16 != 0 && is_u16 != 1) || (out_float != 0 && out_float != 1) || (shrink != 0 && shrink != 1)) return IRM_EINVAL;
-    if (K <= 0 || K > 65535 || (C != 1 && C != 3) || s < 2 || s > 4) return IRM_EINVAL;
+    if (!irm_frames_ok(is_u16, K, H, W, C) || !irm_is_flag(out_float) || !irm_is_flag(shrink)) return IRM_EINVAL;
+    if (s < 2 || s > 4) return IRM_EINVAL;
     const int P = shrink ? 4 * s + 2 : 6;
     if (H < P || W < P || H > 32768 || W > 32768) return IRM_EINVAL;           // one reflection must reach every tap
     const int OH = shrink ? (H + s - 1) / s : H * s, OW = shrink ? (W + s - 1) / s : W * s;
-    if ((long)OH * OW * C > 0x7fffffffL || (long)H * W * C > 0x7fffffffL) return IRM_EINVAL;
+    if ((long)OH * OW * C > 0x7fffffffL) return IRM_EINVAL;
     const int tow = shrink ? 32 : 128;
     const int ncol_max = (shrink ? (tow - 1) * s : (tow - 1) / s) + 1 + P;
     if (RZ_ROWS * ncol_max * C > RZ_LDS_FLOATS) return IRM_EINVAL;
     const int tiles_x = (OW + tow - 1) / tow, tiles_y = (OH + RZ_ROWS - 1) / RZ_ROWS;
     ResizeArgs a{in, out, wh, ih, ww, iw, H, W, OH, OW, P, P, tow, tiles_x, ncol_max, is_u16 ? 65535.0f : 255.0f};
     const dim3 grid((unsigned)(tiles_x * tiles_y), K);
-    if (is_u16 && C == 3) launch_resize<unsigned short, 3>(a, out_float, grid, stream);
-    else if (is_u16) launch_resize<unsigned short, 1>(a, out_float, grid, stream);
-    else if (C == 3) launch_resize<unsigned char, 3>(a, out_float, grid, stream);
-    else launch_resize<unsigned char, 1>(a, out_float, grid, stream);
+    irm_dispatch_frames(is_u16, C, [&](auto kind) {
+        launch_resize<typename decltype(kind)::type, decltype(kind)::C>(a, out_float, grid, stream);
+    });
     return irm_launch_status();
 }

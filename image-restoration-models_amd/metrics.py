@@ -50,7 +50,8 @@ def calculate_metrics(pred: np.ndarray, target: np.ndarray, data_range=None):
     return psnr_value, ssim_value
 
 
-#: output tile of irm_frame_metrics (csrc/metrics.hip): 16 rows x 192 values (pixels x channels), one partial each
+#: output tile of irm_frame_metrics (csrc/metrics.hip; the geometry is SsimTile of csrc/irm_frame.h): 16 rows x 192 values
+#: (pixels x channels), one partial each
 _METRICS_TILE_ROWS, _METRICS_TILE_VALUES = 16, 192
 
 

@@ -64,12 +64,18 @@ def test_every_float_frame_entry_point_has_a_guard_band_case():
 
 
 def test_kernel_source_keeps_the_repository_rules():
-    """No preprocessor conditional in the new kernel file and header, and the reference's arithmetic is spelled with
-    the correctly rounded intrinsics (a contracted multiply-add would break the bit-exact blend)."""
-    src = open(os.path.join(os.path.dirname(_hip.LIB_PATH), "csrc", "tiler_f32.hip")).read()
+    """No preprocessor conditional in the kernel file, in the frame-side header it includes (where the tile walk
+    lives) and in the C header, and the reference's arithmetic is spelled with the correctly rounded intrinsics (a
+    contracted multiply-add would break the bit-exact blend)."""
+    csrc = os.path.join(os.path.dirname(_hip.LIB_PATH), "csrc")
+    kernels = open(os.path.join(csrc, "tiler_f32.hip")).read()
+    included = re.findall(r'^#include "(\w+\.h)"', kernels, flags=re.M)
+    assert included == ["irm_frame.h"]
+    walk = open(os.path.join(csrc, "irm_frame.h")).read()
     hdr = open(os.path.join(ROOT, "include", "irm_hip_frames.h")).read()
-    for text in (src, hdr):
+    for text in (kernels, walk, hdr):
         assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif)\b", text, flags=re.M)
+    src = kernels + walk
     for word in ("__fdiv_rn(raw, hi)", "__fadd_rn(acc, __fmul_rn(p, w))", "__fdiv_rn(acc, fmaxf(wsum, 1e-8f))",
                  "fminf(fmaxf(__fmul_rn(v, mul), lo), hi)"):
         assert word in src, word
