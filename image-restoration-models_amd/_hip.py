@@ -97,6 +97,13 @@ SIGNATURES_YUV = {
     "irm_rgb_f32_to_yuv420": [_P, _P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 
+#: the K_h x K_w conv and the 3x3 poolings of FPN-Inception's encoder (convkxk.hip, pool3x3.hip), mirrors
+#: include/irm_hip_inception.h one to one
+SIGNATURES_INCEPTION = {
+    "irm_convkxk_f32": [_P, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "irm_pool3x3_f32": [_P, _L, _P, _L, _I, _I, _I, _I, _I, _P],
+}
+
 _lib = None
 
 
@@ -116,7 +123,7 @@ def load():
                 "(make -C image-restoration-models_amd/csrc).  There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM,
-                               **SIGNATURES_YUV}.items():
+                               **SIGNATURES_YUV, **SIGNATURES_INCEPTION}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I
@@ -376,6 +383,22 @@ def pack_conv3x3_weight(w: torch.Tensor) -> torch.Tensor:
     wpad = torch.zeros(9, mt * 16, ks * 4, dtype=torch.float32, device=w.device)
     wpad[:, :co, :ci] = w.reshape(co, ci, 9).permute(2, 0, 1)
     return wpad.view(9, mt, 16, ks, 4).permute(0, 1, 3, 4, 2).contiguous().view(-1)
+
+
+def pack_convkxk_weight(w: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """W [Co][Ci][KH][KW] * scale -> wp[KH*KW][ceil(Co/16)][ceil(Ci/4)][64] of irm_convkxk_f32:
+    wp[tap][mt][ks][l] = W[16 mt + (l & 15)][4 ks + (l >> 4)][tap // KW][tap % KW], zero beyond Co and Ci.
+    scale: the residual scale of an Inception-ResNet block closer, folded into the weight (in float64, one rounding)."""
+    w = w.detach()
+    co, ci, kh, kw = w.shape
+    if scale != 1.0:
+        w = (w.double() * float(scale))
+    w = w.float()
+    t, mt, ks = kh * kw, (co + 15) // 16, (ci + 3) // 4
+    wpad = torch.zeros(t, mt * 16, ks * 4, dtype=torch.float32, device=w.device)
+    wpad[:, :co, :ci] = w.reshape(co, ci, t).permute(2, 0, 1)
+    # [tap][mt][16 r][ks][4 g] -> [tap][mt][ks][g][r]  (lane = g*16 + r)
+    return wpad.view(t, mt, 16, ks, 4).permute(0, 1, 3, 4, 2).contiguous().view(-1)
 
 
 def pack_conv3x3_weight_split(w: torch.Tensor):

@@ -1,4 +1,5 @@
-"""DeblurGANv2 (FPN-MobileNet generator) on MI355X - call surface of src/deblurganv2/__init__.py:11-41."""
+"""DeblurGANv2 (FPN-MobileNet and FPN-Inception generators) on MI355X - call surface of
+src/deblurganv2/__init__.py:11-41, plus get_model_inception for the FPN-Inception checkpoint."""
 
 #: synthetic-weight rules (synth.py)
 SYNTH_RULES = (
@@ -7,14 +8,16 @@ SYNTH_RULES = (
 )
 
 import os as _os
+import re as _re
 
 import numpy as _np
 import torch as _torch
 
 from .models.fpn_mobilenet import FPNMobileNet  # noqa: E402
-from .models.fpn_inception import FPNInceptionDecoder  # noqa: E402
+from .models.fpn_inception import INCEPTION_TAIL, FPNInception, FPNInceptionDecoder  # noqa: E402
 
-__all__ = ["FPNMobileNet", "FPNInceptionDecoder", "get_model", "normalize", "pad", "postprocess", "SYNTH_RULES"]
+__all__ = ["FPNMobileNet", "FPNInception", "FPNInceptionDecoder", "get_model", "get_model_inception", "normalize", "pad",
+           "postprocess", "SYNTH_RULES"]
 
 
 def normalize(x: _np.ndarray):
@@ -40,13 +43,27 @@ def get_model(weights_path: str, device: _torch.device):
     DataParallel 'module.' prefix; the model is returned in TRAIN mode like the reference."""
     name = _os.path.basename(weights_path).split('.')[0]
     if name != 'fpn_mobilenet':
-        raise NotImplementedError(f"generator {name!r}: only fpn_mobilenet is built end to end in the MI355X path.  "
-                                  "fpn_inception's encoder is timm's InceptionResNetV2 (third-party, not vendored in the "
-                                  "reference, absent here); its in-tree decoder is deblurganv2.FPNInceptionDecoder, which "
-                                  "takes the encoder's five feature maps as inputs")
+        raise NotImplementedError(f"generator {name!r}: this loader builds fpn_mobilenet only.  The FPN-Inception generator "
+                                  "(deblurganv2.FPNInception) is loaded with deblurganv2.get_model_inception(weights_path, "
+                                  "device)")
     model = FPNMobileNet()
     sd = _torch.load(weights_path, map_location="cpu", weights_only=True)['model']
     model.load_state_dict({(k[7:] if k.startswith('module.') else k): v for k, v in sd.items()})
+    model.to(device)
+    model.train(True)
+    print(f"Successfully loaded {_np.sum([p.numel() for p in model.parameters()]):,} parameters from {weights_path}")
+    return model
+
+
+def get_model_inception(weights_path: str, device: _torch.device):
+    """The FPN-Inception generator from a reference checkpoint ({'model': state_dict}, keys maybe with the DataParallel
+    'module.' prefix).  The keys of the classifier tail of inception_resnet_v2 (repeat_2, block8, conv2d_7b,
+    last_linear), which FPN.forward never runs, are dropped; everything else loads strictly.  Returned in TRAIN mode
+    like the reference's generators (src/deblurganv2/__init__.py:38)."""
+    model = FPNInception()
+    sd = _torch.load(weights_path, map_location="cpu", weights_only=True)['model']
+    sd = {(k[7:] if k.startswith('module.') else k): v for k, v in sd.items()}
+    model.load_state_dict({k: v for k, v in sd.items() if not _re.search(INCEPTION_TAIL, k)})
     model.to(device)
     model.train(True)
     print(f"Successfully loaded {_np.sum([p.numel() for p in model.parameters()]):,} parameters from {weights_path}")

@@ -647,16 +647,21 @@ def upsample_add(src, out, scale, add=None):
             int(scale), tag=f"C{C} {Hs}x{Ws} x{scale} B{B}")
 
 
-# --------------------------------------------------------------------------- fp16 mode of the conv stacks (ops_half.py)
-_HALF_WRAPPERS = ("conv3x3_h_in", "conv3x3_h", "conv3x3_h_out")
+# --------------------------------------------------------------------------- wrappers that live in modules of their own
+_HALF_WRAPPERS = ("conv3x3_h_in", "conv3x3_h", "conv3x3_h_out")                           # ops_half.py: the fp16 mode
+_INCEPTION_WRAPPERS = ("convkxk", "pool3x3", "plan_convkxk", "convkxk_out_size", "CONVKXK_GEOMETRIES", "POOL_MAX_S2",
+                       "POOL_AVG_S1")                                                     # ops_inception.py
 
 
 def __getattr__(name):
-    """ops.conv3x3_h_in / conv3x3_h / conv3x3_h_out: the wrappers of ops_half.py, bound here at their first use (that
-    module imports this one, so neither depends on which of the two is imported first)."""
-    if name in _HALF_WRAPPERS:
-        from . import ops_half
-        for n in _HALF_WRAPPERS:
-            globals()[n] = getattr(ops_half, n)
-        return globals()[name]
+    """ops.conv3x3_h_in / conv3x3_h / conv3x3_h_out (ops_half.py) and ops.convkxk / pool3x3 / plan_convkxk ...
+    (ops_inception.py): bound here at their first use (those modules import this one, so neither depends on which is
+    imported first)."""
+    for names, module in ((_HALF_WRAPPERS, "ops_half"), (_INCEPTION_WRAPPERS, "ops_inception")):
+        if name in names:
+            import importlib
+            mod = importlib.import_module("." + module, __package__)
+            for n in names:
+                globals()[n] = getattr(mod, n)
+            return globals()[name]
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -33,7 +33,7 @@ from .convnet_common import check_precision
 from .configs import PATCH_CONFIG, ROOT_RESULTS_DIR, ROOT_WEIGHTS_DIR
 from .restormer import Restormer
 from .mair import MaIR, MaIRPlus, MaIRUNet
-from .deblurganv2 import FPNMobileNet
+from .deblurganv2 import FPNInception, FPNMobileNet
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -555,7 +555,7 @@ def _get_model_prediction(model, input_image, device, patch_size, patch_overlap,
     """get_model_prediction through _run_model_inference: (prediction, inference_time_ms, out_dev or None)."""
     kw = dict(patch_size=patch_size, patch_overlap=patch_overlap, need_degradation=need_degradation,
               noise_level=noise_level)
-    if isinstance(model, (FPNMobileNet,)):                      # utils.py:280-291
+    if isinstance(model, (FPNMobileNet, FPNInception)):         # utils.py:280-291
         return _run_model_inference(model, input_image, device, normalize=deblurganv2.normalize, pad=deblurganv2.pad,
                                     postprocess=deblurganv2.postprocess, **kw)
     if isinstance(model, _PAD8_MODELS):

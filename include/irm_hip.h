@@ -538,6 +538,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- YUV 4:2:0 video frames to and from the float32 frame: irm_yuv420_to_rgb_f32, irm_rgb_f32_to_yuv420 */
 #include "irm_hip_yuv.h"
 
+/* ---- the Inception-ResNet-v2 encoder of FPN-Inception: irm_convkxk_f32, irm_pool3x3_f32 */
+#include "irm_hip_inception.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,7 +55,7 @@ def run_case(out, name):
         inputs += [synth.uniform(11, f"trace_enc{i}", (1, c, int(s[0]), int(s[1])), -1.0, 1.0).cuda()
                    for i, (c, s) in enumerate(zip((32, 64, 192, 1088, 2080), sizes))]
     sigs = {**_hip.SIGNATURES, **_hip.SIGNATURES_HALF, **_hip.SIGNATURES_FRAMES, **_hip.SIGNATURES_GRAM,
-            **_hip.SIGNATURES_YUV}
+            **_hip.SIGNATURES_YUV, **_hip.SIGNATURES_INCEPTION}
     trace, call = [], _hip.call
 
     def logged(entry, *args):
