@@ -4,7 +4,8 @@ the reference's column names.  Dataset file IO is out of scope - `loader` is any
 (input_uint8_hwc, target_uint8_hwc, name), e.g. `synthetic_loader`.  For a super-resolving model (`model.upscale`
 s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `evaluate_sr` make them from HR frames
 by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics).  Where no target exists
-(real captures), `evaluate_blind` scores the frames by NIQE instead."""
+(real captures), `evaluate_blind` scores the frames by NIQE instead.  `evaluate_stream` is `evaluate` over the frame
+stream (stream.py): several frames per forward, the copies under the forwards."""
 from __future__ import annotations
 
 import csv
@@ -80,6 +81,48 @@ def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: s
     row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
                     model_name=model_name, params=get_model_total_parameters(model))
     row['Failed'] = failed
+    return row
+
+
+def evaluate_stream(model, loader, device, patch_config: dict, *, task: str, subtask: str, dataset: str,
+                    model_name: str, frames_per_step: int = 4, metrics="device", sigma='N/A', need_degradation=False,
+                    noise_level=None, with_ssim=True) -> dict:
+    """The row of `evaluate` from the frame stream (stream.py): groups of `frames_per_step` frames per forward, the
+    copies under the forwards, the hooks by the model class as get_model_prediction picks them.
+
+    metrics="device" scores a whole group with one launch of calculate_metrics_device's kernel (frame_metrics_device)
+    on the device output slot, before the slot is used again; the targets go up through a pinned slot like the
+    inputs, and the scores come down with the frames.  metrics="host" scores the yielded arrays with
+    calculate_metrics.  The time of a frame is the stream's `ms`: its group's share of the wall time, the scoring of
+    a device-scored group included - a throughput figure, so Avg_Time_ms x frames is the time of the sweep.
+
+    There is no skip_failed: a frame that raises ends the sweep and the exception propagates, as in the reference's
+    loop (scripts/tests.py).  The row's 'Failed' is always empty."""
+    from . import stream
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
+    k = stream._check_frames_per_step(frames_per_step)
+    front = stream._Front(model, patch_config["patch_size"], patch_config["patch_overlap"], need_degradation,
+                          noise_level, "same", False, triples=True, with_targets=metrics == "device")
+    items = ((inp, tgt, tgt) for inp, tgt, _ in loader)
+    psnr_list, ssim_list, time_list = [], [], []
+    frames = stream._stream(front, items, device, k)
+    try:
+        for pred, ms, target_img, score in frames:
+            if score is not None:
+                p, s = stream.score_psnr(score[0], pred.shape, pred.dtype), score[1] if with_ssim else float('nan')
+            elif with_ssim:
+                p, s = calculate_metrics(pred, target_img)
+            else:
+                p, s = psnr(target_img, pred, 255 if pred.dtype == np.uint8 else 65535), float('nan')
+            psnr_list.append(p)
+            ssim_list.append(s)
+            time_list.append(ms)
+    finally:
+        frames.close()
+    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
+                    model_name=model_name, params=get_model_total_parameters(model))
+    row['Failed'] = []
     return row
 
 

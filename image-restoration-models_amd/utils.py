@@ -1,7 +1,7 @@
 """Glue API with the reference's call surface (src/utils.py): model factory,
 patch-config lookup and the tiled-patch inference loop; the metrics (metrics.py),
-the super-resolution resize (resize.py), NIQE (niqe.py) and the YUV 4:2:0
-conversions (yuv.py) are re-exported.
+the super-resolution resize (resize.py), NIQE (niqe.py), the YUV 4:2:0
+conversions (yuv.py) and the frame stream (stream.py) are re-exported.
 
 The hot loop (reference: src/utils.py:353-454, one synchronous forward + D2H +
 numpy blend per tile) runs here as ONE device pipeline per image:
@@ -12,6 +12,9 @@ given equal per-tile predictions (same float32 operation order).
 """
 from __future__ import annotations
 
+import contextlib
+import dataclasses
+import gc
 import os
 import time
 from typing import Callable
@@ -29,6 +32,7 @@ from .niqe import (calculate_niqe, calculate_niqe_device, load_niqe_params, niqe
 from .resize import imresize_device, imresize_host, mod_crop, resize_table  # noqa: F401
 from .yuv import (YUV_FORMATS, rgb_to_yuv420_device, rgb_to_yuv420_host, yuv420_to_rgb_device,  # noqa: F401
                   yuv420_to_rgb_host)
+from .stream import group_frames, run_model_inference_stream  # noqa: F401
 from .convnet_common import check_precision
 from .configs import PATCH_CONFIG, ROOT_RESULTS_DIR, ROOT_WEIGHTS_DIR
 from .restormer import Restormer
@@ -239,6 +243,22 @@ def _release_workspace(model: Module):
         rel()
 
 
+@contextlib.contextmanager
+def _no_cyclic_gc():
+    """No cyclic garbage collection inside the block: a capture must not be where dead cycles are freed.  A dead
+    cycle can hold GPU objects whose release synchronises - another model's HIP graph (its destructor synchronises
+    the device on ROCm), pinned host memory - and a synchronising call is illegal while a stream captures: the
+    error is raised inside a destructor and ends the process.  torch.cuda.graph collected garbage on entry once and
+    no longer does by default; what is dead stays dead until the capture has ended."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
 def graphed_forward(model: Module, x: torch.Tensor) -> torch.Tensor:
     """model(x) replayed from a HIP graph where that pays: the conv stacks and MaIR at small images are bound by
     the host's launch rate (hundreds of kernels of 10-60 us per image), not by the GPU.
@@ -275,7 +295,7 @@ def graphed_forward(model: Module, x: torch.Tensor) -> torch.Tensor:
         static_in = x.clone()
         g = torch.cuda.CUDAGraph()
         before = torch.cuda.memory_reserved(x.device)
-        with torch.cuda.graph(g):
+        with _no_cyclic_gc(), torch.cuda.graph(g):
             static_out = model(static_in)
         _release_workspace(model)                    # the buffers stay reserved in g's private pool
         ent = (g, static_in, static_out, max(torch.cuda.memory_reserved(x.device) - before, 0))
@@ -394,6 +414,64 @@ def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_
     integer squared error (targets_dev raises ValueError), and hooks="deblurganv2" is defined on raw integer values
     with an integer result (a float32 input or out="float32" raises ValueError).  Non-finite values in a float frame
     are outside the contract."""
+    img0 = imgs_dev[0]
+    plan = _tile_pipeline_plan(model, tuple(img0.shape), img0.dtype, img0.device, patch_size, patch_overlap, pad8,
+                               noise_sigma, hooks, unit_range, out, targets_dev is not None,
+                               frames=[(tuple(im.shape), im.dtype) for im in imgs_dev])
+    return _tile_pipeline_run(model, plan, imgs_dev, targets_dev, max_batch, keep_tiles)
+
+
+@dataclasses.dataclass
+class TilePipelinePlan:
+    """What the device pipeline needs for frames of one shape and dtype and does not depend on their values: the tile
+    geometry, the origins, the blend window and the noise field on the device, the value kinds and the hook constants.
+    _tile_pipeline_plan makes it (no launch), _tile_pipeline_run holds the launches."""
+    h: int
+    w: int
+    c: int
+    c_out: int
+    s: int
+    ps: int
+    th: int
+    tw: int
+    ph: int
+    pw: int
+    T: int
+    dtype: torch.dtype
+    device: torch.device
+    zero32: bool
+    norm_mean: float
+    norm_inv_std: float
+    post_scale: float
+    post_shift: float
+    is_f32: bool
+    f32_out: bool
+    out_dtype: torch.dtype
+    out_u16: bool
+    unit_range: bool
+    org: torch.Tensor
+    window: torch.Tensor
+    noise: torch.Tensor | None
+
+    @property
+    def frame_dtype(self) -> torch.dtype:
+        """dtype of a result frame."""
+        return torch.float32 if self.f32_out else self.out_dtype
+
+
+def noise_field(sigma, shape) -> np.ndarray:
+    """The float64 field add_gaussian_noise adds to every tile (src/utils.py:29-36): the values of
+    np.random.seed(0); np.random.normal(0, sigma / 255., shape), drawn from a generator of their own so that the
+    process-wide numpy state is left alone."""
+    return np.random.RandomState(0).normal(0, sigma / 255., shape)
+
+
+def _tile_pipeline_plan(model: Module, shape: tuple, dtype, dev, patch_size, patch_overlap, pad8: bool, noise_sigma,
+                        hooks, unit_range: bool, out: str, has_targets: bool = False,
+                        frames: list | None = None) -> TilePipelinePlan:
+    """The plan of tiled_forward_device_batch for [H, W, C] frames of `dtype` on `dev`, with that call's checks in
+    its order (`frames`: the (shape, dtype) of every frame of the batch).  The origins and the noise field are per-
+    device constants: a call after the first uploads nothing and draws nothing on the host."""
     if out not in ("same", "float32", "uint8", "uint16"):
         raise ValueError(f"out must be 'same', 'float32', 'uint8' or 'uint16', not {out!r}")
     norm_mean, norm_inv_std, post_scale, post_shift = 0.0, 1.0, 1.0, 0.0
@@ -403,32 +481,44 @@ def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_
         norm_inv_std = float(np.float32(1.0) / (np.float32(0.5) * np.float32(255.0)))
         post_scale, post_shift, pad_mode = 0.5, 1.0, "zero32"
     s = _upscale(model, noise_sigma is not None)
-    img0 = imgs_dev[0]
-    h, w, c = img0.shape
-    if any(tuple(im.shape) != (h, w, c) or im.dtype != img0.dtype for im in imgs_dev):
+    h, w, c = shape
+    if any(sh != (h, w, c) or dt != dtype for sh, dt in frames or ()):
         raise ValueError("tiled_forward_device_batch: the images of a batch must share shape and dtype")
-    is_f32, f32_out, out_dtype, out_u16 = _value_kinds(img0.dtype, out, unit_range, hooks, targets_dev is not None)
-    dev = img0.device
+    is_f32, f32_out, out_dtype, out_u16 = _value_kinds(dtype, out, unit_range, hooks, has_targets)
+    dev = torch.device(dev)
     ps, origins, th, tw, ph, pw = tile_plan(h, w, patch_size, patch_overlap, pad_mode)
-    T, K, c_out = len(origins), len(imgs_dev), min(3, c)
-    org = torch.tensor(origins, dtype=torch.int32).to(dev, non_blocking=True)
+    org = device_constant(("origins", str(dev), tuple(origins)),
+                          lambda: torch.tensor(origins, dtype=torch.int32).to(dev))
     noise = None
-    if noise_sigma is not None:
-        np.random.seed(seed=0)                       # utils.py:33: same field for every tile
-        noise = torch.from_numpy(np.random.normal(0, noise_sigma / 255., (th, tw, c))).to(dev)
+    if noise_sigma is not None:                      # utils.py:33: same field for every tile
+        noise = device_constant(("noise", str(dev), float(noise_sigma), th, tw, c),
+                                lambda: torch.from_numpy(noise_field(noise_sigma, (th, tw, c))).to(dev))
+    return TilePipelinePlan(h, w, c, min(3, c), s, ps, th, tw, ph, pw, len(origins), dtype, dev, pad_mode == "zero32",
+                            float(norm_mean), float(norm_inv_std), post_scale, post_shift, is_f32, f32_out, out_dtype,
+                            out_u16, bool(unit_range), org, _window_on(dev, s * ps), noise)
+
+
+def _tile_pipeline_run(model: Module, plan: TilePipelinePlan, imgs_dev: list, targets_dev: list | None = None,
+                       max_batch: int = 8, keep_tiles: list | None = None, frames_out: list | None = None) -> list:
+    """The launches of tiled_forward_device_batch for the K frames `imgs_dev` of `plan`'s shape: extract, forward,
+    blend, all on the current stream.  `frames_out`, K [s H, s W, c_out] tensors of plan.frame_dtype, receives the
+    results (the stream's static output slots); without it the frames are allocated here."""
+    p, dev = plan, plan.device
+    h, w, c, s, T, K = p.h, p.w, p.c, p.s, p.T, len(imgs_dev)
+    org, noise, th, tw, ph, pw = p.org, p.noise, p.th, p.tw, p.ph, p.pw
     tiles = torch.empty(K * T, c, ph, pw, dtype=torch.float32, device=dev)
-    ranges = [_unit_range_on(dev)] * K if (is_f32 or f32_out) else None
-    if is_f32 and not unit_range:
+    ranges = [_unit_range_on(dev)] * K if (p.is_f32 or p.f32_out) else None
+    if p.is_f32 and not p.unit_range:
         ws = torch.empty(_MINMAX_WS_FLOATS, dtype=torch.float32, device=dev)      # (one stream: the frames take turns)
         ranges = [_frame_range_on(im, ws) for im in imgs_dev]
     for k, im in enumerate(imgs_dev):
-        if is_f32:
+        if p.is_f32:
             _hip.call("irm_tile_extract_f32", _hip.ptr(im), _hip.ptr(ranges[k]), _hip.ptr(org), _hip.ptr(noise),
-                      _hip.ptr(tiles[k * T:]), h, w, c, th, tw, ph, pw, T, int(pad_mode == "zero32"))
+                      _hip.ptr(tiles[k * T:]), h, w, c, th, tw, ph, pw, T, int(p.zero32))
         else:
-            _hip.call("irm_tile_extract", _hip.ptr(im), int(img0.dtype in (torch.uint16, torch.int16)), _hip.ptr(org),
-                      _hip.ptr(noise), _hip.ptr(tiles[k * T:]), h, w, c, th, tw, ph, pw, T, float(norm_mean),
-                      float(norm_inv_std), int(pad_mode == "zero32"))
+            _hip.call("irm_tile_extract", _hip.ptr(im), int(p.dtype in (torch.uint16, torch.int16)), _hip.ptr(org),
+                      _hip.ptr(noise), _hip.ptr(tiles[k * T:]), h, w, c, th, tw, ph, pw, T, p.norm_mean,
+                      p.norm_inv_std, int(p.zero32))
     if ops.TIMER is not None:
         ops.TIMER.break_chain()                    # the tile extraction above is not a timed launch
     pred = _forward_tiles(model, tiles, max_batch)
@@ -436,27 +526,28 @@ def tiled_forward_device_batch(model: Module, imgs_dev: list, patch_size, patch_
         raise ValueError(f"model.upscale = {s}: expected {s * ph}x{s * pw} predictions for {ph}x{pw} tiles, "
                          f"got {tuple(pred.shape[2:])}")
     if keep_tiles is not None:
-        keep_tiles.append(pred[:, :c_out, :s * th, :s * tw].clone())
+        keep_tiles.append(pred[:, :p.c_out, :s * th, :s * tw].clone())
     results = []
     for k in range(K):
-        frame = torch.empty(s * h, s * w, c_out, dtype=torch.float32 if f32_out else out_dtype, device=dev)
+        frame = (frames_out[k] if frames_out is not None
+                 else torch.empty(s * h, s * w, p.c_out, dtype=p.frame_dtype, device=dev))
         sse, tgt = None, None
         if targets_dev is not None and targets_dev[k] is not None:
             sse, tgt = torch.zeros(1, dtype=torch.int64, device=dev), targets_dev[k]
-        if f32_out:
+        if p.f32_out:
             # extents in input pixels, predictions and window at output scale (irm_hip_frames.h)
-            _hip.call("irm_window_blend_f32", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, s * ps)),
-                      _hip.ptr(frame), _hip.ptr(ranges[k]), h, w, c_out, pred.shape[1], th, tw, pred.shape[2] // s,
-                      pred.shape[3] // s, ps, T, s)
+            _hip.call("irm_window_blend_f32", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(p.window),
+                      _hip.ptr(frame), _hip.ptr(ranges[k]), h, w, p.c_out, pred.shape[1], th, tw, pred.shape[2] // s,
+                      pred.shape[3] // s, p.ps, T, s)
         elif s > 1:
             # tiles cut at input scale, blended at output scale: origins x s, window of s * ps (irm_hip.h)
-            _hip.call("irm_window_blend_scaled", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, s * ps)),
-                      _hip.ptr(frame), int(out_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw, ph, pw,
-                      ps, T, s, post_scale, post_shift)
+            _hip.call("irm_window_blend_scaled", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(p.window),
+                      _hip.ptr(frame), int(p.out_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, p.c_out, pred.shape[1], th, tw,
+                      ph, pw, p.ps, T, s, p.post_scale, p.post_shift)
         else:
-            _hip.call("irm_window_blend", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(_window_on(dev, ps)), _hip.ptr(frame),
-                      int(out_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, c_out, pred.shape[1], th, tw,
-                      pred.shape[2], pred.shape[3], ps, T, post_scale, post_shift)
+            _hip.call("irm_window_blend", _hip.ptr(pred[k * T:]), _hip.ptr(org), _hip.ptr(p.window), _hip.ptr(frame),
+                      int(p.out_u16), _hip.ptr(tgt), _hip.ptr(sse), h, w, p.c_out, pred.shape[1], th, tw,
+                      pred.shape[2], pred.shape[3], p.ps, T, p.post_scale, p.post_shift)
         results.append((frame, sse))
     return results
 
@@ -555,12 +646,22 @@ def _get_model_prediction(model, input_image, device, patch_size, patch_overlap,
     """get_model_prediction through _run_model_inference: (prediction, inference_time_ms, out_dev or None)."""
     kw = dict(patch_size=patch_size, patch_overlap=patch_overlap, need_degradation=need_degradation,
               noise_level=noise_level)
-    if isinstance(model, (FPNMobileNet, FPNInception)):         # utils.py:280-291
+    hooks, pad8 = _model_hooks(model)
+    if hooks == "deblurganv2":                                  # utils.py:280-291
         return _run_model_inference(model, input_image, device, normalize=deblurganv2.normalize, pad=deblurganv2.pad,
                                     postprocess=deblurganv2.postprocess, **kw)
-    if isinstance(model, _PAD8_MODELS):
+    if pad8:
         return _run_model_inference(model, input_image, device, pad=pad, **kw)
     return _run_model_inference(model, input_image, device, **kw)
+
+
+def _model_hooks(model) -> tuple:
+    """(hooks, pad8) of the device pipeline for a model, by its class as the reference dispatches (utils.py:270-311):
+    ("deblurganv2", True) for the two DeblurGANv2 generators, (None, True) - reflect pad to a multiple of 8 - for
+    Restormer and MaIR, (None, False) otherwise."""
+    if isinstance(model, (FPNMobileNet, FPNInception)):
+        return "deblurganv2", True
+    return None, isinstance(model, _PAD8_MODELS)
 
 
 def _chain_hooks(model) -> bool:
