@@ -81,6 +81,25 @@ def to_host(t: torch.Tensor) -> np.ndarray:
     return a.view(np.uint16) if a.dtype == np.int16 else a
 
 
+def plane_slots(shapes, dtype, k: int, device, pinned: bool) -> tuple:
+    """One buffer for k frames whose planes (`shapes`) lie behind one another, pinned host memory or on `device`:
+    (buffer, per frame the views of its planes, elements of a frame).  The views of a pinned buffer are numpy's."""
+    sizes = [int(np.prod(s)) for s in shapes]
+    per = sum(sizes)
+    buf = torch.empty(k * per, dtype=dtype, pin_memory=True) if pinned else torch.empty(k * per, dtype=dtype, device=device)
+    flat = buf.numpy() if pinned else buf
+    if pinned and dtype == torch.int16:
+        flat = flat.view(np.uint16)                                          # the uint16 bit pattern, as to_host reads it
+    views, off = [], 0
+    for _ in range(k):
+        frame = []
+        for n, s in zip(sizes, shapes):
+            frame.append(flat[off:off + n].reshape(s))
+            off += n
+        views.append(frame)
+    return buf, views, per
+
+
 _DEVICE_CONSTANTS: dict = {}
 
 

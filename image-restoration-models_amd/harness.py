@@ -8,20 +8,20 @@ by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metr
 stream (stream.py): several frames per forward, the copies under the forwards."""
 from __future__ import annotations
 
+import contextlib
 import csv
 import os
 import time
 
 import numpy as np
-import torch
 
-from . import synth
+from . import stream, synth
 from .frames import to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,
                       calculate_metrics_device, psnr)
 from .niqe import calculate_niqe, calculate_niqe_device
 from .resize import imresize_device, mod_crop
-from .utils import _get_model_prediction, get_model_prediction, get_model_total_parameters
+from .utils import _get_model_prediction, get_model_total_parameters
 
 COLUMNS = ['Task', 'Type', 'Dataset', 'Sigma', 'Model', 'Model_Params', 'PSNR', 'SSIM', 'Std_PSNR', 'Std_SSIM',
            'Avg_Time_ms', 'Std_Time_ms']
@@ -34,6 +34,31 @@ def synthetic_loader(n_images: int, h: int = 720, w: int = 1280, c: int = 3, see
     for i in range(n_images):
         inp, tgt = synth.synth_image_pair(i, h, w, c, seed_base=seed_base, blur=blur)
         yield inp, tgt, f"synthetic_{i:04d}.png"
+
+
+def _check_metrics(metrics) -> None:
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
+
+
+@contextlib.contextmanager
+def _frame_guard(failed: list, name, skip_failed: bool, model_name, dataset):
+    """The work on one frame of a sweep: an exception in the block is recorded in `failed` as (name, "Type: message"),
+    printed, and the frame skipped - unless skip_failed is false or it is an out-of-memory error: those propagate."""
+    try:
+        yield
+    except Exception as e:                                      # noqa: BLE001 (reported, not swallowed)
+        if not skip_failed or "out of memory" in str(e).lower():
+            raise
+        failed.append((name, f"{type(e).__name__}: {e}"))
+        print(f"[harness] {model_name} on {dataset}: frame {name} failed ({type(e).__name__}: {e}); skipped")
+
+
+def _host_metrics(pred, target_img, with_ssim: bool) -> tuple:
+    """(psnr, ssim) of a downloaded prediction: calculate_metrics, or the PSNR alone and NaN."""
+    if with_ssim:
+        return calculate_metrics(pred, target_img)
+    return psnr(target_img, pred, 255 if pred.dtype == np.uint8 else 65535), float('nan')
 
 
 def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: str, dataset: str, model_name: str,
@@ -51,33 +76,21 @@ def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: s
     restored frame while it is still on the GPU (calculate_metrics_device, uint8 / uint16 frames only): the target is
     uploaded, and PSNR / SSIM differ from the host's by rounding only (the tests allow 1e-9).  Either way the prediction and the timed work (input
     upload through output download) are the same, and the metrics are not timed."""
-    if metrics not in ("host", "device"):
-        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
+    _check_metrics(metrics)
     psnr_list, ssim_list, time_list, failed = [], [], [], []
     for input_img, target_img, name in loader:
-        try:
+        with _frame_guard(failed, name, skip_failed, model_name, dataset):
+            pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
+                                                       need_degradation=need_degradation, noise_level=noise_level)
             if metrics == "device":
-                pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
-                                                           need_degradation=need_degradation, noise_level=noise_level)
                 p, s = _device_metrics(pred, pred_dev, target_img, device)
                 if not with_ssim:
                     s = float('nan')
             else:
-                pred, ms = get_model_prediction(model, input_img, device, **patch_config,
-                                                need_degradation=need_degradation, noise_level=noise_level)
-                if with_ssim:
-                    p, s = calculate_metrics(pred, target_img)
-                else:
-                    p, s = psnr(target_img, pred, 255 if pred.dtype == np.uint8 else 65535), float('nan')
-        except Exception as e:                                  # noqa: BLE001 (reported, not swallowed)
-            if not skip_failed or "out of memory" in str(e).lower():
-                raise
-            failed.append((name, f"{type(e).__name__}: {e}"))
-            print(f"[harness] {model_name} on {dataset}: frame {name} failed ({type(e).__name__}: {e}); skipped")
-            continue
-        psnr_list.append(p)
-        ssim_list.append(s)
-        time_list.append(ms)
+                p, s = _host_metrics(pred, target_img, with_ssim)
+            psnr_list.append(p)
+            ssim_list.append(s)
+            time_list.append(ms)
     row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
                     model_name=model_name, params=get_model_total_parameters(model))
     row['Failed'] = failed
@@ -98,9 +111,7 @@ def evaluate_stream(model, loader, device, patch_config: dict, *, task: str, sub
 
     There is no skip_failed: a frame that raises ends the sweep and the exception propagates, as in the reference's
     loop (scripts/tests.py).  The row's 'Failed' is always empty."""
-    from . import stream
-    if metrics not in ("host", "device"):
-        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
+    _check_metrics(metrics)
     k = stream._check_frames_per_step(frames_per_step)
     front = stream._Front(model, patch_config["patch_size"], patch_config["patch_overlap"], need_degradation,
                           noise_level, "same", False, triples=True, with_targets=metrics == "device")
@@ -111,10 +122,8 @@ def evaluate_stream(model, loader, device, patch_config: dict, *, task: str, sub
         for pred, ms, target_img, score in frames:
             if score is not None:
                 p, s = stream.score_psnr(score[0], pred.shape, pred.dtype), score[1] if with_ssim else float('nan')
-            elif with_ssim:
-                p, s = calculate_metrics(pred, target_img)
             else:
-                p, s = psnr(target_img, pred, 255 if pred.dtype == np.uint8 else 65535), float('nan')
+                p, s = _host_metrics(pred, target_img, with_ssim)
             psnr_list.append(p)
             ssim_list.append(s)
             time_list.append(ms)
@@ -164,8 +173,7 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
     metrics="host" the downloaded one (calculate_metrics_basicsr); they differ by rounding only.
     model=None gives the bicubic baseline row: the prediction is imresize_device(lr, scale), the time that of the
     upload, the resize and the download.  Failed frames are handled as in `evaluate`."""
-    if metrics not in ("host", "device"):
-        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
+    _check_metrics(metrics)
     if scale not in (2, 3, 4):
         raise ValueError(f"evaluate_sr: scale must be 2, 3 or 4, not {scale!r}")
     if model is not None and int(getattr(model, "upscale", 1) or 1) != scale:
@@ -179,7 +187,7 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
         model_name = "Bicubic" if model is None else type(model).__name__
     psnr_list, ssim_list, time_list, failed = [], [], [], []
     for lr, hr, name in sr_pairs(hr_loader, scale, device):
-        try:
+        with _frame_guard(failed, name, skip_failed, model_name, dataset):
             if model is None:
                 start = time.time()
                 pred_dev = imresize_device(to_device(lr, device), scale, out="same")
@@ -196,15 +204,9 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
                                                         channel_order)
             else:
                 p, s = calculate_metrics_basicsr(pred, hr, crop, test_y_channel, channel_order)
-        except Exception as e:                                  # noqa: BLE001 (reported, not swallowed)
-            if not skip_failed or "out of memory" in str(e).lower():
-                raise
-            failed.append((name, f"{type(e).__name__}: {e}"))
-            print(f"[harness] {model_name} on {dataset}: frame {name} failed ({type(e).__name__}: {e}); skipped")
-            continue
-        psnr_list.append(p)
-        ssim_list.append(s)
-        time_list.append(ms)
+            psnr_list.append(p)
+            ssim_list.append(s)
+            time_list.append(ms)
     row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask or f"x{scale}", dataset=dataset, sigma=sigma,
                     model_name=model_name, params=0 if model is None else get_model_total_parameters(model))
     row['Failed'] = failed
@@ -223,14 +225,13 @@ def evaluate_blind(model, loader, device, patch_config: dict, *, niqe_params, cr
     downloaded one (calculate_niqe); they differ by rounding only.  model=None scores the inputs themselves (the
     "before" row; its times are 0).  The row has the reference's columns - PSNR and SSIM are NaN - plus 'NIQE' and
     'Std_NIQE' (COLUMNS_BLIND).  Failed frames are handled as in `evaluate`."""
-    if metrics not in ("host", "device"):
-        raise ValueError(f"metrics must be 'host' or 'device', not {metrics!r}")
+    _check_metrics(metrics)
     if model_name is None:
         model_name = "Input" if model is None else type(model).__name__
     niqe_list, time_list, failed = [], [], []
     for item in loader:
         input_img, name = item[0], item[-1]
-        try:
+        with _frame_guard(failed, name, skip_failed, model_name, dataset):
             if model is None:
                 pred, ms, pred_dev = input_img, 0.0, None
             else:
@@ -244,14 +245,8 @@ def evaluate_blind(model, loader, device, patch_config: dict, *, niqe_params, cr
                 q = calculate_niqe_device(pred_dev, crop_border, niqe_params, channel_order=channel_order)
             else:
                 q = calculate_niqe(pred, crop_border, niqe_params, channel_order=channel_order)
-        except Exception as e:                                  # noqa: BLE001 (reported, not swallowed)
-            if not skip_failed or "out of memory" in str(e).lower():
-                raise
-            failed.append((name, f"{type(e).__name__}: {e}"))
-            print(f"[harness] {model_name} on {dataset}: frame {name} failed ({type(e).__name__}: {e}); skipped")
-            continue
-        niqe_list.append(q)
-        time_list.append(ms)
+            niqe_list.append(q)
+            time_list.append(ms)
     nan = [float('nan')] * len(niqe_list)
     row = aggregate(nan, nan, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
                     model_name=model_name, params=0 if model is None else get_model_total_parameters(model))

@@ -2,9 +2,9 @@
 
 The one-frame calls of utils.py upload from pageable memory, run, download and synchronise, one frame at a time.
 `run_model_inference_stream` takes any iterable of frames, forms groups of `frames_per_step` consecutive frames of one
-shape and dtype, runs each group as one tiled_forward_device_batch step (utils._tile_pipeline_plan / _tile_pipeline_run
-on static buffers) and keeps two groups in flight: while group g computes, group g + 1 is copied up and group g - 1
-comes down.
+shape and dtype, runs each group as one tiled_forward_device_batch step (pipeline._tile_pipeline_plan /
+_tile_pipeline_run on static buffers) and keeps two groups in flight: while group g computes, group g + 1 is copied up
+and group g - 1 comes down.
 
 Three streams: torch's current stream for EVERY kernel (tiler, model, converters, metrics), one upload stream and one
 download stream, cached per device under keys of their own.  One copy stream would not do: the upload of g + 1 would
@@ -25,8 +25,6 @@ steady state enqueues pinned asynchronous copies and kernels only: no pageable c
 
 The first group of a plan, and the first group of a plan with another number of frames, runs unpipelined (drain, fill,
 upload, compute, synchronise): that is where graphed_forward captures, and a capture synchronises the device.
-
-utils.py re-exports this module, so utils is imported at call time here.
 """
 from __future__ import annotations
 
@@ -36,9 +34,11 @@ import time
 import numpy as np
 import torch
 
-from . import _hip, yuv
-from .frames import device_constant, psnr_from_error
+from . import yuv
+from .frames import device_constant, plane_slots, psnr_from_error
 from .metrics import frame_metrics_device
+from .pipeline import (_check_out, _tile_pipeline_plan, _tile_pipeline_run, _value_kinds, cuda_device, model_route,
+                       refuse_deblurgan)
 from .yuv import YUV_FORMATS
 
 #: plans (buffers of one frame shape and dtype) a stream keeps, least recently used first out
@@ -91,46 +91,34 @@ def _check_frames_per_step(frames_per_step) -> int:
     return int(frames_per_step)
 
 
-def _is_deblurgan(model) -> bool:
-    from . import deblurganv2
-    return isinstance(model, deblurganv2.FPNMobileNet) or type(model).__module__.startswith(deblurganv2.__name__ + ".")
-
-
 class _Front:
     """What the stream does with one kind of frame: the checks that need no GPU (`prepare`), the layout of a frame in
     the input and output slots, and the device work of a group (`compute`).  This one is the plain [H, W, C] frame."""
 
     def __init__(self, model, patch_size, patch_overlap, need_degradation, noise_level, out, unit_range,
                  triples=False, with_targets=False):
-        from . import utils
         if model is None or not callable(model):
             raise ValueError("run_model_inference_stream: model must be a model, not None")
         self.model, self.patch_size, self.patch_overlap = model, patch_size, patch_overlap
-        self.sigma = noise_level if (need_degradation and noise_level is not None) else None
         #: triples: an item is (frame, target or None, extra) and not the frame; with_targets: the targets go up too
         self.out, self.unit_range, self.triples, self.with_targets = out, bool(unit_range), triples, with_targets
-        self.hooks, self.pad8 = utils._model_hooks(model)
-        self.s = utils._upscale(model, need_degradation)
-        if out not in ("same", "float32", "uint8", "uint16"):
-            raise ValueError(f"out must be 'same', 'float32', 'uint8' or 'uint16', not {out!r}")
-        if self.hooks == "deblurganv2" and out == "float32":
-            raise ValueError("hooks='deblurganv2' normalises raw integer values and requantises: no float32 frames")
+        self.route = model_route(model, need_degradation, noise_level)
+        _check_out(out, self.route.hooks)
 
     def prepare(self, item):
         """(key, arrays to upload, target or None, what comes back with the result) of one frame, or ValueError."""
-        from . import utils
         frame, target, extra = item if self.triples else (item, None, None)
         if not isinstance(frame, np.ndarray) or frame.ndim != 3 or frame.dtype not in _TORCH_KIND:
             raise ValueError("run_model_inference_stream: a frame is a uint8, uint16 or float32 [H, W, C] array")
         if min(frame.shape) < 1:
             raise ValueError(f"run_model_inference_stream: an empty frame, shape {frame.shape}")
         dtype = _TORCH_KIND[frame.dtype]
-        _, f32_out, out_dtype, _ = utils._value_kinds(dtype, self.out, self.unit_range, self.hooks, False)
-        if self.hooks == "deblurganv2" and frame.dtype != np.uint8:
+        _, f32_out, out_dtype, _ = _value_kinds(dtype, self.out, self.unit_range, self.route.hooks, False)
+        if self.route.hooks == "deblurganv2" and frame.dtype != np.uint8:
             raise ValueError("DeblurGANv2 streams uint8 frames only: its hooks are defined on raw 8-bit values")
         if self.with_targets:
             h, w, c = frame.shape
-            want = (self.s * h, self.s * w, min(3, c))
+            want = (self.route.s * h, self.route.s * w, min(3, c))
             if (not isinstance(target, np.ndarray) or target.dtype not in (np.uint8, np.uint16) or f32_out
                     or _TORCH_KIND[target.dtype] != out_dtype or target.shape != want):
                 raise ValueError("metrics='device' needs uint8 or uint16 target frames of the prediction's shape and dtype")
@@ -141,12 +129,11 @@ class _Front:
         tile plan's)."""
         (h, w, c), dt = key
         return ((h, w, c), _TORCH_KIND[dt], self.out, self.unit_range), [(h, w, c)], _TORCH_KIND[dt], \
-            [(self.s * h, self.s * w, min(3, c))], None
+            [(self.route.s * h, self.route.s * w, min(3, c))], None
 
     def compute(self, plan, slot: int, k: int):
-        from . import utils
-        utils._tile_pipeline_run(self.model, plan.tp, [f[0] for f in plan.dev_in[slot][:k]], None, plan.max_batch, None,
-                                 frames_out=[f[0] for f in plan.dev_out[slot][:k]])
+        _tile_pipeline_run(self.model, plan.tp, [f[0] for f in plan.dev_in[slot][:k]], None, self.route.max_batch, None,
+                           frames_out=[f[0] for f in plan.dev_out[slot][:k]])
 
     def finish(self, extra, outs):
         """What the stream yields for a frame: `outs` are the caller's own copies of its output planes."""
@@ -158,13 +145,11 @@ class _YuvFront(_Front):
 
     def __init__(self, model, patch_size, patch_overlap, need_degradation, noise_level, fmt, matrix, full_range, siting,
                  luma_only):
-        if model is not None and _is_deblurgan(model):
-            raise ValueError("run_model_inference_stream: DeblurGANv2 normalises raw integer values and has no float32 "
-                             "frames; convert with yuv420_to_rgb_host and stream the RGB frames")
+        refuse_deblurgan(model, "run_model_inference_stream", "convert with yuv420_to_rgb_host and stream the RGB frames")
         yuv._check_options(fmt, matrix, siting)
         super().__init__(model, patch_size, patch_overlap, need_degradation, noise_level, "float32", True)
-        if luma_only and self.s > 1:
-            raise ValueError(f"luma_only with model.upscale = {self.s}: the chroma planes would need a resize")
+        if luma_only and self.route.s > 1:
+            raise ValueError(f"luma_only with model.upscale = {self.route.s}: the chroma planes would need a resize")
         self.fmt, self.luma_only = fmt, bool(luma_only)
         self.opts = dict(matrix=matrix, full_range=full_range, siting=siting, luma_only=self.luma_only)
         self.np_dtype = np.uint16 if YUV_FORMATS[fmt][1] == 10 else np.uint8
@@ -173,21 +158,15 @@ class _YuvFront(_Front):
         h, w = yuv._check_planes(planes, self.fmt, False, np.ndarray, (self.np_dtype,))
         return (h, w), tuple(planes[:1] if self.luma_only else planes), None, tuple(planes)
 
-    def _plane_shapes(self, h, w):
-        if self.luma_only:
-            return [(h, w)]
-        return [(h, w)] + ([(h // 2, w // 2)] * 2 if self.fmt == "i420" else [(h // 2, w // 2, 2)])
-
     def layout(self, key):
         h, w = key
-        dt, s = _TORCH_KIND[np.dtype(self.np_dtype)], self.s
-        return ((h, w, 1 if self.luma_only else 3), torch.float32, "float32", True), self._plane_shapes(h, w), dt, \
-            self._plane_shapes(s * h, s * w), dt
+        dt = _TORCH_KIND[np.dtype(self.np_dtype)]
+        planes_in, planes_out = (yuv.plane_shapes(m * h, m * w, self.fmt, self.luma_only) for m in (1, self.route.s))
+        return ((h, w, 1 if self.luma_only else 3), torch.float32, "float32", True), planes_in, dt, planes_out, dt
 
     def compute(self, plan, slot: int, k: int):
-        from . import utils
         rgb = [yuv.yuv420_to_rgb_device(tuple(p), self.fmt, **self.opts) for p in plan.dev_in[slot][:k]]
-        res = utils._tile_pipeline_run(self.model, plan.tp, rgb, None, plan.max_batch, None)
+        res = _tile_pipeline_run(self.model, plan.tp, rgb, None, self.route.max_batch, None)
         for (frame, _), planes in zip(res, plan.dev_out[slot][:k]):
             yuv.rgb_to_yuv420_device(frame, self.fmt, out=tuple(planes), **self.opts)
 
@@ -195,55 +174,29 @@ class _YuvFront(_Front):
         return tuple(outs) + tuple(planes[1:]) if self.luma_only else tuple(outs)     # the chroma as it came in
 
 
-def _slots(shapes, dtype, k: int, device, pinned: bool):
-    """One buffer for k frames whose planes (`shapes`) lie behind one another, and per frame the views of its planes."""
-    sizes = [int(np.prod(s)) for s in shapes]
-    per = sum(sizes)
-    buf = torch.empty(k * per, dtype=dtype, pin_memory=True) if pinned else torch.empty(k * per, dtype=dtype, device=device)
-    flat = buf.numpy() if pinned else buf
-    if pinned and dtype == torch.int16:
-        flat = flat.view(np.uint16)                                          # the uint16 bit pattern, as to_host reads it
-    views, off = [], 0
-    for _ in range(k):
-        frame = []
-        for n, s in zip(sizes, shapes):
-            frame.append(flat[off:off + n].reshape(s))
-            off += n
-        views.append(frame)
-    return buf, views, per
-
-
 class _Plan:
     """The static buffers, events and tile plan of one (shape, dtype): two slots of each (module docstring)."""
 
     def __init__(self, front: _Front, key, k: int, device, with_targets: bool):
-        from . import utils
         (shape, dtype, out, unit_range), in_shapes, in_dtype, out_shapes, out_dtype = front.layout(key)
-        self.tp = utils._tile_pipeline_plan(front.model, shape, dtype, device, front.patch_size, front.patch_overlap,
-                                            front.pad8, front.sigma, front.hooks, unit_range, out)
-        self.max_batch = getattr(front.model, 'max_tiles_per_batch', 8)
+        r = front.route
+        self.tp = _tile_pipeline_plan(front.model, shape, dtype, device, front.patch_size, front.patch_overlap, r.pad8,
+                                      r.sigma, r.hooks, unit_range, out)
         out_dtype = out_dtype or self.tp.frame_dtype
         self.seen, self.count = set(), 0
-        self.pin_in, self.np_in, self.dev_in_buf, self.dev_in = [], [], [], []
-        self.pin_out, self.np_out, self.dev_out_buf, self.dev_out = [], [], [], []
-        self.pin_tgt, self.np_tgt, self.dev_tgt_buf, self.dev_tgt = [], [], [], []
-        self.dev_score, self.pin_score = [], []
-        for _ in range(DEPTH):
-            buf, views, self.in_per = _slots(in_shapes, in_dtype, k, device, True)
-            self.pin_in.append(buf), self.np_in.append(views)
-            buf, views, _ = _slots(in_shapes, in_dtype, k, device, False)
-            self.dev_in_buf.append(buf), self.dev_in.append(views)
-            buf, views, self.out_per = _slots(out_shapes, out_dtype, k, device, True)
-            self.pin_out.append(buf), self.np_out.append(views)
-            buf, views, _ = _slots(out_shapes, out_dtype, k, device, False)
-            self.dev_out_buf.append(buf), self.dev_out.append(views)
-            if with_targets:
-                buf, views, _ = _slots(out_shapes, out_dtype, k, device, True)
-                self.pin_tgt.append(buf), self.np_tgt.append(views)
-                buf, views, _ = _slots(out_shapes, out_dtype, k, device, False)
-                self.dev_tgt_buf.append(buf), self.dev_tgt.append(views)
-                self.dev_score.append(torch.empty(2, k, dtype=torch.int64, device=device))      # sse; the bits of ssim
-                self.pin_score.append(torch.empty(2, k, dtype=torch.int64, pin_memory=True))
+
+        def slots(shapes, dtype, n=DEPTH):
+            """n slots, pinned and on the device: (pinned buffers, their numpy views, device buffers, their views)."""
+            pin = [plane_slots(shapes, dtype, k, device, True) for _ in range(n)]
+            dev = [plane_slots(shapes, dtype, k, device, False) for _ in range(n)]
+            return [p[0] for p in pin], [p[1] for p in pin], [d[0] for d in dev], [d[1] for d in dev]
+        n_tgt = DEPTH if with_targets else 0
+        self.pin_in, self.np_in, self.dev_in_buf, self.dev_in = slots(in_shapes, in_dtype)
+        self.pin_out, self.np_out, self.dev_out_buf, self.dev_out = slots(out_shapes, out_dtype)
+        self.pin_tgt, self.np_tgt, self.dev_tgt_buf, self.dev_tgt = slots(out_shapes, out_dtype, n_tgt)
+        self.in_per, self.out_per = self.pin_in[0].numel() // k, self.pin_out[0].numel() // k
+        self.dev_score = [torch.empty(2, k, dtype=torch.int64, device=device) for _ in range(n_tgt)]   # sse; the bits of ssim
+        self.pin_score = [torch.empty(2, k, dtype=torch.int64, pin_memory=True) for _ in range(n_tgt)]
         self.up = [torch.cuda.Event() for _ in range(DEPTH)]
         self.done = [torch.cuda.Event() for _ in range(DEPTH)]
         self.down = [torch.cuda.Event() for _ in range(DEPTH)]
@@ -341,9 +294,7 @@ def _stream(front: _Front, items, device, frames_per_step: int):
             try:
                 group = next(groups)
                 if streams is None:
-                    if dev.type != "cuda":
-                        raise _hip.HipLibraryError("run_model_inference_stream runs on the GPU only (no CPU fallback); "
-                                                   "pass a 'cuda' device")
+                    cuda_device(dev, "run_model_inference_stream")
                     streams = (torch.cuda.current_stream(dev),) + _copy_streams(dev)
                 key = group[0][0]
                 plan = plans.get(key)

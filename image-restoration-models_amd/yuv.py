@@ -24,6 +24,12 @@ def _check_options(fmt, matrix, siting) -> None:
         raise ValueError(f"siting must be 'left' or 'center', not {siting!r}")
 
 
+def plane_shapes(h: int, w: int, fmt, luma_only: bool = False) -> list:
+    """The plane shapes of an h x w frame in `fmt`: Y, then U and V or the interleaved UV; Y alone with luma_only."""
+    chroma = [(h // 2, w // 2)] * 2 if fmt == "i420" else [(h // 2, w // 2, 2)]
+    return [(h, w)] + ([] if luma_only else chroma)
+
+
 def _check_planes(planes, fmt, luma_only: bool, kind, dtypes) -> tuple:
     """(H, W) of the planes of one frame: their number, type (`kind`: np.ndarray or torch.Tensor), dtype and shapes.
     With luma_only the chroma planes are not looked at and may be missing."""
@@ -156,8 +162,7 @@ def rgb_to_yuv420_host(rgb, fmt, matrix="bt709", full_range=False, siting="left"
     k = _constants(matrix, full_range, depth)
     shift = 6 if fmt == "p010" else 0
     if out is None:
-        out = ((np.empty((h, w), dt), np.empty((h // 2, w // 2), dt), np.empty((h // 2, w // 2), dt)) if n == 3
-               else (np.empty((h, w), dt), np.empty((h // 2, w // 2, 2), dt)))
+        out = tuple(np.empty(s, dt) for s in plane_shapes(h, w, fmt))
     if luma_only:
         out[0][...] = _codes(k["y0"], k["yr"], rgb[:, :, 0], k["top"]) << shift
         return tuple(out)
@@ -230,14 +235,13 @@ def rgb_to_yuv420_device(rgb, fmt, matrix="bt709", full_range=False, siting="lef
     legal.  With luma_only the frame is [H][W][1] and only the Y plane of `out` - required - is written; its chroma
     planes come back as they are."""
     _check_options(fmt, matrix, siting)
-    n, depth = YUV_FORMATS[fmt]
+    depth = YUV_FORMATS[fmt][1]
     h, w = _check_rgb(rgb, luma_only, torch.Tensor)
     if out is None and luma_only:
         raise ValueError("luma_only writes the Y plane alone: pass the frame's planes as out, their chroma is kept")
     if out is None:
         dt = torch.int16 if depth == 10 else torch.uint8
-        shapes = [(h, w), (h // 2, w // 2), (h // 2, w // 2)] if n == 3 else [(h, w), (h // 2, w // 2, 2)]
-        out = tuple(torch.empty(s, dtype=dt, device=rgb.device) for s in shapes)
+        out = tuple(torch.empty(s, dtype=dt, device=rgb.device) for s in plane_shapes(h, w, fmt))
     oh, ow, y, u, v, step, pitch_y, pitch_c = _device_planes(out, fmt, luma_only)
     if (oh, ow) != (h, w) or y.device != rgb.device:
         raise ValueError(f"out holds the planes of another device or frame size than {h} x {w}")

@@ -145,11 +145,14 @@ def test_run_model_chain_validates_before_any_gpu_call():
 
 
 def test_chain_hooks_follow_the_model_class():
-    assert utils._chain_hooks(dncnn.DnCNN(1, 1, 64, 17, "R")) is False
-    assert utils._chain_hooks(utils.Restormer()) is True
+    def chain_pad8(model):                      # what run_model_chain does per stage: the refusal, then the route
+        utils.refuse_deblurgan(model, "run_model_chain", "run it on its own with get_model_prediction")
+        return utils.model_route(model).pad8
+    assert chain_pad8(dncnn.DnCNN(1, 1, 64, 17, "R")) is False
+    assert chain_pad8(utils.Restormer()) is True
     assert all(issubclass(c, torch.nn.Module) for c in utils._PAD8_MODELS) and mair.MaIR in utils._PAD8_MODELS
     with pytest.raises(ValueError, match="DeblurGANv2"):
-        utils._chain_hooks(deblurganv2.FPNMobileNet())
+        chain_pad8(deblurganv2.FPNMobileNet())
 
 
 def test_chain_stage_kinds(monkeypatch):
