@@ -104,6 +104,12 @@ SIGNATURES_INCEPTION = {
     "irm_pool3x3_f32": [_P, _L, _P, _L, _I, _I, _I, _I, _I, _P],
 }
 
+#: PSNR / SSIM of float32 frames and of YUV 4:2:0 planes (metrics_video.hip), mirrors include/irm_hip_metrics.h one to one
+SIGNATURES_METRICS = {
+    "irm_frame_metrics_f32": [_P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _L, _P],
+    "irm_yuv420_metrics": [_P, _P, _P, _I, _L, _L, _P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+}
+
 _lib = None
 
 
@@ -123,7 +129,7 @@ def load():
                 "(make -C image-restoration-models_amd/csrc).  There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM,
-                               **SIGNATURES_YUV, **SIGNATURES_INCEPTION}.items():
+                               **SIGNATURES_YUV, **SIGNATURES_INCEPTION, **SIGNATURES_METRICS}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

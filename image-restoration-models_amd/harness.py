@@ -5,7 +5,8 @@ the reference's column names.  Dataset file IO is out of scope - `loader` is any
 s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `evaluate_sr` make them from HR frames
 by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics).  Where no target exists
 (real captures), `evaluate_blind` scores the frames by NIQE instead.  `evaluate_stream` is `evaluate` over the frame
-stream (stream.py): several frames per forward, the copies under the forwards."""
+stream (stream.py): several frames per forward, the copies under the forwards.  `evaluate_yuv` takes YUV 4:2:0 plane
+tuples and reports PSNR / SSIM per component."""
 from __future__ import annotations
 
 import contextlib
@@ -15,18 +16,20 @@ import time
 
 import numpy as np
 
-from . import stream, synth
+from . import stream, synth, yuv
 from .frames import to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,
-                      calculate_metrics_device, psnr)
+                      calculate_metrics_device, calculate_metrics_f32_device, psnr)
 from .niqe import calculate_niqe, calculate_niqe_device
 from .resize import imresize_device, mod_crop
-from .utils import _get_model_prediction, get_model_total_parameters
+from .utils import _get_model_prediction, _run_model_inference_yuv, get_model_total_parameters
 
 COLUMNS = ['Task', 'Type', 'Dataset', 'Sigma', 'Model', 'Model_Params', 'PSNR', 'SSIM', 'Std_PSNR', 'Std_SSIM',
            'Avg_Time_ms', 'Std_Time_ms']
 #: the columns of an `evaluate_blind` row: the reference's plus the no-reference score
 COLUMNS_BLIND = COLUMNS + ['NIQE', 'Std_NIQE']
+#: the columns of an `evaluate_yuv` row: the reference's, PSNR / SSIM being the luma values, plus the chroma planes'
+COLUMNS_YUV = COLUMNS + ['PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'Std_PSNR_U', 'Std_PSNR_V', 'Std_SSIM_U', 'Std_SSIM_V']
 
 
 def synthetic_loader(n_images: int, h: int = 720, w: int = 1280, c: int = 3, seed_base: int = 1000, blur: int = 15):
@@ -73,9 +76,12 @@ def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: s
     propagates).  Out-of-memory errors always propagate (src/utils.py:91-93 reports them to the caller).
 
     metrics="host" scores the downloaded prediction with calculate_metrics (numpy / scipy); metrics="device" scores the
-    restored frame while it is still on the GPU (calculate_metrics_device, uint8 / uint16 frames only): the target is
-    uploaded, and PSNR / SSIM differ from the host's by rounding only (the tests allow 1e-9).  Either way the prediction and the timed work (input
-    upload through output download) are the same, and the metrics are not timed."""
+    restored frame while it is still on the GPU (calculate_metrics_device for uint8 / uint16 frames;
+    calculate_metrics_f32_device with data_range 1.0, the host's rule for float frames, where input and target are
+    float32 arrays of the prediction's shape): the target is uploaded, and PSNR / SSIM differ from the host's by
+    rounding only (the tests allow 1e-9).  A float target for an integer prediction, or the reverse, raises.  Either way
+    the prediction and the timed work (input upload through output download) are the same, and the metrics are not
+    timed."""
     _check_metrics(metrics)
     psnr_list, ssim_list, time_list, failed = [], [], [], []
     for input_img, target_img, name in loader:
@@ -83,7 +89,7 @@ def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: s
             pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
                                                        need_degradation=need_degradation, noise_level=noise_level)
             if metrics == "device":
-                p, s = _device_metrics(pred, pred_dev, target_img, device)
+                p, s = _device_metrics(pred, pred_dev, target_img, device, input_img)
                 if not with_ssim:
                     s = float('nan')
             else:
@@ -135,9 +141,18 @@ def evaluate_stream(model, loader, device, patch_config: dict, *, task: str, sub
     return row
 
 
-def _device_metrics(pred, pred_dev, target_img, device):
+def _is_f32(a, shape=None) -> bool:
+    return isinstance(a, np.ndarray) and a.dtype == np.float32 and (shape is None or a.shape == shape)
+
+
+def _device_metrics(pred, pred_dev, target_img, device, input_img=None):
     """(psnr, ssim) of one frame on the GPU: pred_dev is the pipeline's output tensor (None after the host tile loop:
-    the prediction is uploaded), the target goes up as the input did (uint16 as its int16 bit pattern)."""
+    the prediction is uploaded), the target goes up as the input did (uint16 as its int16 bit pattern).  A float32
+    prediction of a float32 input with a float32 target of its shape is scored by the float kernel."""
+    if _is_f32(input_img) and _is_f32(pred) and _is_f32(target_img, pred.shape):
+        if pred_dev is None:
+            pred_dev = to_device(pred, device)
+        return calculate_metrics_f32_device(pred_dev, to_device(target_img, pred_dev.device))
     if not isinstance(target_img, np.ndarray) or target_img.dtype not in (np.uint8, np.uint16):
         raise ValueError("metrics='device' needs uint8 or uint16 target frames")
     if pred_dev is None:
@@ -209,6 +224,47 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
             time_list.append(ms)
     row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask or f"x{scale}", dataset=dataset, sigma=sigma,
                     model_name=model_name, params=0 if model is None else get_model_total_parameters(model))
+    row['Failed'] = failed
+    return row
+
+
+def evaluate_yuv(model, loader, device, patch_config: dict, *, fmt, matrix="bt709", full_range=False, siting="left",
+                 luma_only=False, metrics="device", task: str, subtask: str, dataset: str, model_name: str, sigma='N/A',
+                 need_degradation=False, noise_level=None, skip_failed=True) -> dict:
+    """One results_table row for YUV 4:2:0 video frames: `loader` yields (planes, target_planes, name), the planes as
+    run_model_inference_yuv takes them (numpy arrays in `fmt`; matrix, full_range and siting describe the frames).  The
+    prediction and the timed region are run_model_inference_yuv's, plane upload through plane download; scoring is
+    outside it.  metrics="device" scores the restored planes while they are on the GPU (calculate_metrics_yuv_device:
+    the target planes are uploaded), metrics="host" the downloaded ones (calculate_metrics_yuv); they differ by
+    rounding only.  The scores are per component, on the integer codes: the row has the reference's columns with PSNR /
+    SSIM the luma values, plus PSNR_U, PSNR_V, SSIM_U, SSIM_V and their Std_ forms (COLUMNS_YUV); with luma_only the
+    chroma columns are NaN.  Failed frames are handled as in `evaluate`."""
+    _check_metrics(metrics)
+    yuv._check_options(fmt, matrix, siting)
+    if not isinstance(patch_config, dict) or set(patch_config) != {"patch_size", "patch_overlap"}:
+        raise ValueError("evaluate_yuv: patch_config is {'patch_size': .., 'patch_overlap': ..}")
+    scores, time_list, failed = [], [], []
+    for planes, target_planes, name in loader:
+        with _frame_guard(failed, name, skip_failed, model_name, dataset):
+            pred, ms, pred_dev = _run_model_inference_yuv(
+                model, planes, device, fmt=fmt, matrix=matrix, full_range=full_range, siting=siting, luma_only=luma_only,
+                need_degradation=need_degradation, noise_level=noise_level, **patch_config)
+            if metrics == "device":
+                if not isinstance(target_planes, (tuple, list)) or not all(isinstance(t, np.ndarray) for t in target_planes):
+                    raise ValueError("evaluate_yuv: the target planes are numpy arrays")
+                used = target_planes[:1] if luma_only else target_planes
+                target_dev = tuple(to_device(t, pred_dev[0].device) for t in used)
+                m = yuv.calculate_metrics_yuv_device(pred_dev, target_dev, fmt, luma_only)
+            else:
+                m = yuv.calculate_metrics_yuv(pred, target_planes, fmt, luma_only)
+            del pred_dev
+            scores.append(m)
+            time_list.append(ms)
+    row = aggregate([m.psnr_y for m in scores], [m.ssim_y for m in scores], time_list, task=task, subtask=subtask,
+                    dataset=dataset, sigma=sigma, model_name=model_name, params=get_model_total_parameters(model))
+    for col, field in (('PSNR_U', 'psnr_u'), ('PSNR_V', 'psnr_v'), ('SSIM_U', 'ssim_u'), ('SSIM_V', 'ssim_v')):
+        vals = [getattr(m, field) for m in scores] or [float('nan')]
+        row[col], row['Std_' + col] = np.mean(vals), np.std(vals)
     row['Failed'] = failed
     return row
 

@@ -1,6 +1,7 @@
 """PSNR and SSIM: the reference's calculate_metrics (src/utils.py:134-156; skimage is restated) and
 the super-resolution protocol's Y-channel / cropped pair (basicsr), each on the host in float64
-and on the GPU (irm_frame_metrics, irm_frame_metrics_basicsr)."""
+and on the GPU (irm_frame_metrics, irm_frame_metrics_basicsr; irm_frame_metrics_f32 for float32 frames, DESIGN.md
+section 20)."""
 from __future__ import annotations
 
 import numpy as np
@@ -106,6 +107,56 @@ def calculate_metrics_device(pred_dev: torch.Tensor, target_dev: torch.Tensor, d
     host = torch.stack([sse, ssim_dev.view(torch.int64)]).cpu()       # the one host synchronisation
     sse_v, ssim_v = int(host[0, 0]), float(host[1].view(torch.float64)[0])
     return psnr_from_error(data_range, sse_v / (h * w * c)), ssim_v
+
+
+def frame_metrics_f32_device(preds, targets, data_range=1.0):
+    """Device squared error and SSIM of K float32 prediction / target frames of one shape (irm_frame_metrics_f32): lists
+    of float32 HW / HW1 / HW3 GPU tensors, e.g. the pipeline's out="float32" frames.  Returns device tensors
+    (sse [K] float64, the fp64 sum of the squared differences; ssim [K] float64, the values of `ssim` above) without
+    synchronising with the host.  A non-contiguous tensor is made contiguous.  A frame's values are bitwise the same
+    whatever K and on every call.  Non-finite values are outside the contract."""
+    preds, targets = list(preds), list(targets)
+    if not preds or len(preds) != len(targets):
+        raise ValueError(f"{len(preds)} predictions and {len(targets)} targets: need the same number, at least one")
+    for p, t in zip(preds, targets):
+        if not isinstance(p, torch.Tensor) or not isinstance(t, torch.Tensor):
+            raise ValueError("device metrics take torch tensors (use calculate_metrics for numpy arrays)")
+        if p.shape != t.shape or p.dtype != t.dtype:
+            raise ValueError(f"prediction {tuple(p.shape)} {p.dtype} and target {tuple(t.shape)} {t.dtype} differ in "
+                             "shape or dtype")
+        if p.dtype != torch.float32:
+            raise ValueError(f"frame_metrics_f32_device takes float32 frames, not {p.dtype} (frame_metrics_device "
+                             "takes uint8 and uint16)")
+        if p.shape != preds[0].shape:
+            raise ValueError("the frames of one call must share shape and dtype")
+    h, w, c = frame_shape(preds[0].shape, "frame_metrics_f32_device")
+    if min(h, w) < 7:
+        raise ValueError(f"frame {h}x{w}: both sides must be at least 7, the SSIM window (skimage refuses it too)")
+    _pairs_on_gpu(preds, targets)
+    if not (np.isfinite(data_range) and data_range > 0):
+        raise ValueError(f"data_range must be positive and finite, not {data_range}")
+    k, dev = len(preds), preds[0].device
+    tiles = -(-(h - 6) // _METRICS_TILE_ROWS) * -(-(w - 6) // (_METRICS_TILE_VALUES // c))
+    with torch.cuda.device(dev):
+        p, t = frame_bits(preds), frame_bits(targets)
+        ws = torch.empty(2 * k * tiles, dtype=torch.float64, device=dev)
+        sse = torch.empty(k, dtype=torch.float64, device=dev)
+        ssim_dev = torch.empty(k, dtype=torch.float64, device=dev)
+        _hip.call("irm_frame_metrics_f32", _hip.ptr(p), _hip.ptr(t), k, h, w, c, float(data_range), _hip.ptr(sse),
+                  _hip.ptr(ssim_dev), _hip.ptr(ws), ws.numel())
+    return sse, ssim_dev
+
+
+def calculate_metrics_f32_device(pred_dev: torch.Tensor, target_dev: torch.Tensor, data_range=None):
+    """Device twin of calculate_metrics for float32 GPU frames (HW3: channel-mean SSIM; HW1 and HW: grey): (psnr, ssim)
+    as Python floats after one synchronising copy.  data_range=None means 1.0, the reference's rule for a non-integer
+    dtype (src/utils.py:137-143).  PSNR is inf for identical frames."""
+    if data_range is None:
+        data_range = 1.0
+    sse, ssim_dev = frame_metrics_f32_device([pred_dev], [target_dev], data_range)
+    h, w, c = frame_shape(pred_dev.shape)
+    host = torch.stack([sse, ssim_dev]).cpu()                         # the one host synchronisation
+    return psnr_from_error(data_range, float(host[0, 0]) / (h * w * c)), float(host[1, 0])
 
 
 _Y_COEF = {"rgb": (65.481, 128.553, 24.966), "bgr": (24.966, 128.553, 65.481)}

@@ -18,7 +18,8 @@ from torch.nn import Module
 from . import deblurganv2, dncnn, mair, rednet, restormer, yuv
 from .frames import plane_slots, to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,  # noqa: F401
-                      calculate_metrics_device, frame_metrics_basicsr_device, frame_metrics_device, psnr, ssim)
+                      calculate_metrics_device, calculate_metrics_f32_device, frame_metrics_basicsr_device,
+                      frame_metrics_device, frame_metrics_f32_device, psnr, ssim)
 from .niqe import (calculate_niqe, calculate_niqe_device, load_niqe_params, niqe_feature_distance,  # noqa: F401
                    niqe_features, niqe_features_device, niqe_gamma_table, niqe_plane, niqe_score)
 from .pipeline import (_GRAPH_MAX_BYTES, _GRAPH_MAX_ENTRIES, _MINMAX_WS_FLOATS, _PAD8_MODELS, Restormer,  # noqa: F401
@@ -28,7 +29,8 @@ from .pipeline import (_GRAPH_MAX_BYTES, _GRAPH_MAX_ENTRIES, _MINMAX_WS_FLOATS, 
                        is_deblurgan, model_route, noise_field, refuse_deblurgan, tile_origins, tile_plan,
                        tiled_forward_device, tiled_forward_device_batch)
 from .resize import imresize_device, imresize_host, mod_crop, resize_table  # noqa: F401
-from .yuv import (YUV_FORMATS, rgb_to_yuv420_device, rgb_to_yuv420_host, yuv420_to_rgb_device,  # noqa: F401
+from .yuv import (YUV_FORMATS, YuvMetrics, calculate_metrics_yuv, calculate_metrics_yuv_device,  # noqa: F401
+                  frame_metrics_yuv_device, rgb_to_yuv420_device, rgb_to_yuv420_host, yuv420_to_rgb_device,
                   yuv420_to_rgb_host)
 from .stream import group_frames, run_model_inference_stream  # noqa: F401
 from .convnet_common import check_precision
@@ -317,6 +319,16 @@ def run_model_inference_yuv(model: Module, planes, device: torch.device, *, fmt,
     luma_only=True restores Y alone with a one-channel model (REDNet, the gray DnCNN): the chroma planes are not
     uploaded and come back as they are, so an up-scaling model raises ValueError (the chroma would need a resize).
     DeblurGANv2 raises ValueError: its hooks are defined on raw integer values."""
+    return _run_model_inference_yuv(model, planes, device, fmt=fmt, matrix=matrix, full_range=full_range, siting=siting,
+                                    luma_only=luma_only, patch_size=patch_size, patch_overlap=patch_overlap,
+                                    need_degradation=need_degradation, noise_level=noise_level)[:2]
+
+
+def _run_model_inference_yuv(model, planes, device, *, fmt, matrix="bt709", full_range=False, siting="left",
+                             luma_only=False, patch_size=None, patch_overlap=32, need_degradation=False,
+                             noise_level=None):
+    """run_model_inference_yuv that also hands back the device planes of the result, as frame_metrics_yuv_device
+    takes them (the Y plane alone with luma_only): (planes, inference_time_ms, planes_dev)."""
     if model is None or not callable(model):
         raise ValueError("run_model_inference_yuv: model must be a model, not None")
     refuse_deblurgan(model, "run_model_inference_yuv",
@@ -336,11 +348,11 @@ def run_model_inference_yuv(model: Module, planes, device: torch.device, *, fmt,
                                         max_batch=route.max_batch, unit_range=True, out="float32")
         if luma_only:
             rgb_to_yuv420_device(frame, fmt, out=up, **opts)           # same size: Y is overwritten in place
-            result = (to_host(up[0]),) + tuple(planes[1:])
+            result, planes_dev = (to_host(up[0]),) + tuple(planes[1:]), up
         else:
             # the planes of the result lie behind one another in one buffer, as a decoder lays them out: one download
             buf, (views,), _ = plane_slots(yuv.plane_shapes(frame.shape[0], frame.shape[1], fmt), up[0].dtype, 1, dev, False)
             rgb_to_yuv420_device(frame, fmt, out=tuple(views), **opts)
             host = to_host(buf)                                        # and the same views of it on the host
-            result = tuple(host[v.storage_offset():][:v.numel()].reshape(v.shape) for v in views)
-    return result, (time.time() - start_time) * 1000
+            result, planes_dev = tuple(host[v.storage_offset():][:v.numel()].reshape(v.shape) for v in views), tuple(views)
+    return result, (time.time() - start_time) * 1000, planes_dev

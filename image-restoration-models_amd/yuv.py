@@ -1,12 +1,17 @@
 """YUV 4:2:0 video frames: I420, NV12 and P010 planes to the float32 RGB frame in [0, 1] of the
 device pipeline and back, on the GPU (irm_yuv420_to_rgb_f32, irm_rgb_f32_to_yuv420) and restated in numpy float32 on
-the host with the same operation order.  The reference has no YUV path; tests/yuv_model.py states the arithmetic."""
+the host with the same operation order.  The reference has no YUV path; tests/yuv_model.py states the arithmetic.
+Their PSNR / SSIM per component, on the host in float64 and on the GPU (irm_yuv420_metrics)."""
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _hip
+from .frames import psnr_from_error
+from .metrics import psnr, ssim
 
 #: format -> (planes, bit depth); "p010" keeps its 10-bit code in the upper bits of a 16-bit word
 YUV_FORMATS = {"i420": (3, 8), "nv12": (2, 8), "p010": (2, 10)}
@@ -249,3 +254,96 @@ def rgb_to_yuv420_device(rgb, fmt, matrix="bt709", full_range=False, siting="lef
     _hip.call("irm_rgb_f32_to_yuv420", _hip.ptr(rgb), _hip.ptr(y), _hip.ptr(u), _hip.ptr(v), step, pitch_y,
               pitch_c, *_kernel_options(fmt, matrix, full_range, siting, luma_only), h, w)
     return tuple(out)
+
+
+# ---------------------------------------------------------------------------
+# PSNR / SSIM per component: on the integer codes of Y (H x W) and of U and V (H/2 x W/2), with
+# skimage's SSIM defaults and data_range 255 (8 bit) or 1023 (10 bit).  A P010 code is its word shifted right by six.
+
+class YuvMetrics(NamedTuple):
+    """Python floats; with luma_only the four chroma fields are NaN."""
+    psnr_y: float
+    ssim_y: float
+    psnr_u: float
+    ssim_u: float
+    psnr_v: float
+    ssim_v: float
+
+
+def _check_metric_size(h: int, w: int, luma_only: bool) -> None:
+    least = 8 if luma_only else 14
+    if min(h, w) < least:
+        raise ValueError(f"frame {h} x {w}: both sides must be at least {least}"
+                         + (", the 7 x 7 SSIM window" if luma_only else ", so that a chroma plane holds one 7 x 7 SSIM window"))
+
+
+def _metric_tiles(h: int, w: int) -> int:
+    """Output tiles of an h x w plane in irm_yuv420_metrics (csrc/metrics_video.hip): 16 rows x 192 values each."""
+    return -(-(h - 6) // 16) * -(-(w - 6) // 192)
+
+
+def _peak(fmt) -> int:
+    return 2 ** YUV_FORMATS[fmt][1] - 1
+
+
+def calculate_metrics_yuv(pred_planes, target_planes, fmt, luma_only=False) -> YuvMetrics:
+    """PSNR and SSIM of the planes of one 4:2:0 frame against the target's, per component: metrics.psnr / metrics.ssim
+    in float64 on the integer codes.  The numpy twin of calculate_metrics_yuv_device; `planes` as yuv420_to_rgb_host
+    takes them."""
+    _check_options(fmt, "bt709", "left")
+    dtypes = (np.uint16,) if YUV_FORMATS[fmt][1] == 10 else (np.uint8,)
+    size = _check_planes(pred_planes, fmt, luma_only, np.ndarray, dtypes)
+    if _check_planes(target_planes, fmt, luma_only, np.ndarray, dtypes) != size:
+        raise ValueError(f"the target holds the planes of another frame size than {size[0]} x {size[1]}")
+    _check_metric_size(*size, luma_only)
+    peak = _peak(fmt)
+    vals = []
+    for p, t in zip(_split_planes(pred_planes, fmt, luma_only), _split_planes(target_planes, fmt, luma_only)):
+        vals += [float("nan")] * 2 if p is None else [psnr(t, p, peak), ssim(t, p, peak)]
+    return YuvMetrics(*vals)
+
+
+def frame_metrics_yuv_device(pred_planes, target_planes, fmt, luma_only=False) -> tuple:
+    """Device squared errors and SSIMs of the planes of one 4:2:0 frame against the target's (irm_yuv420_metrics):
+    (sse [3] int64, exact; ssim [3] float64) for Y, U, V as device tensors, without synchronising.  The planes are as
+    yuv420_to_rgb_device takes them: row-pitched views and the int16 bit pattern of "p010" included, and the two sides
+    may be pitched differently.  With luma_only the chroma planes are not read; entries 1 and 2 are then 0 and NaN."""
+    _check_options(fmt, "bt709", "left")
+    h, w, y, u, v, step, pitch_y, pitch_c = _device_planes(pred_planes, fmt, luma_only)
+    th, tw, ty, tu, tv, tstep, tpitch_y, tpitch_c = _device_planes(target_planes, fmt, luma_only)
+    if (th, tw) != (h, w) or ty.device != y.device:
+        raise ValueError(f"the target holds the planes of another device or frame size than {h} x {w}")
+    _check_metric_size(h, w, luma_only)
+    if not y.is_cuda:
+        raise ValueError("device metrics need GPU tensors; there is no CPU fallback")
+    dev = y.device
+    words = 2 * (_metric_tiles(h, w) + (0 if luma_only else 2 * _metric_tiles(h // 2, w // 2)))
+    with torch.cuda.device(dev):
+        ws = torch.empty(words, dtype=torch.float64, device=dev)
+        if luma_only:
+            sse = torch.zeros(3, dtype=torch.int64, device=dev)
+            ssim_dev = torch.full((3,), float("nan"), dtype=torch.float64, device=dev)
+        else:
+            sse = torch.empty(3, dtype=torch.int64, device=dev)
+            ssim_dev = torch.empty(3, dtype=torch.float64, device=dev)
+        depth = YUV_FORMATS[fmt][1]
+        _hip.call("irm_yuv420_metrics", _hip.ptr(y), _hip.ptr(u), _hip.ptr(v), step, pitch_y, pitch_c,
+                  _hip.ptr(ty), _hip.ptr(tu), _hip.ptr(tv), tstep, tpitch_y, tpitch_c, depth, int(fmt == "p010"),
+                  int(bool(luma_only)), h, w, _hip.ptr(sse), _hip.ptr(ssim_dev), _hip.ptr(ws), ws.numel())
+    return sse, ssim_dev
+
+
+def calculate_metrics_yuv_device(pred_planes, target_planes, fmt, luma_only=False) -> YuvMetrics:
+    """Device twin of calculate_metrics_yuv: a YuvMetrics of Python floats after one synchronising copy.  PSNR is inf
+    for identical planes."""
+    sse, ssim_dev = frame_metrics_yuv_device(pred_planes, target_planes, fmt, luma_only)
+    h, w = (int(s) for s in pred_planes[0].shape)
+    host = torch.stack([sse, ssim_dev.view(torch.int64)]).cpu()       # the one host synchronisation
+    ssim_v = host[1].view(torch.float64)
+    vals = []
+    for i, n in enumerate((h * w, (h // 2) * (w // 2), (h // 2) * (w // 2))):
+        if luma_only and i:
+            vals += [float("nan")] * 2
+        else:
+            vals += [psnr_from_error(_peak(fmt), int(host[0, i]) / n), float(ssim_v[i])]
+    return YuvMetrics(*vals)

@@ -541,6 +541,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- the Inception-ResNet-v2 encoder of FPN-Inception: irm_convkxk_f32, irm_pool3x3_f32 */
 #include "irm_hip_inception.h"
 
+/* ---- PSNR / SSIM of float32 frames and of YUV 4:2:0 planes: irm_frame_metrics_f32, irm_yuv420_metrics */
+#include "irm_hip_metrics.h"
+
 #ifdef __cplusplus
 }
 #endif
