@@ -110,6 +110,11 @@ SIGNATURES_METRICS = {
     "irm_yuv420_metrics": [_P, _P, _P, _I, _L, _L, _P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
 }
 
+#: the Haar-band noise statistic of integer frames (noise.hip), mirrors include/irm_hip_noise.h one to one
+SIGNATURES_NOISE = {
+    "irm_noise_hh_stats": [_P, _I, _I, _I, _I, _I, _L, _L, _I, _I, _I, _P, _P, _L, _P],
+}
+
 _lib = None
 
 
@@ -129,7 +134,8 @@ def load():
                 "(make -C image-restoration-models_amd/csrc).  There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM,
-                               **SIGNATURES_YUV, **SIGNATURES_INCEPTION, **SIGNATURES_METRICS}.items():
+                               **SIGNATURES_YUV, **SIGNATURES_INCEPTION, **SIGNATURES_METRICS,
+                               **SIGNATURES_NOISE}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

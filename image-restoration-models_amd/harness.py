@@ -6,7 +6,8 @@ s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `ev
 by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics).  Where no target exists
 (real captures), `evaluate_blind` scores the frames by NIQE instead.  `evaluate_stream` is `evaluate` over the frame
 stream (stream.py): several frames per forward, the copies under the forwards.  `evaluate_yuv` takes YUV 4:2:0 plane
-tuples and reports PSNR / SSIM per component."""
+tuples and reports PSNR / SSIM per component.  `evaluate_auto_sigma` takes a bank of per-sigma checkpoints and runs, per
+frame, the one trained for the noise level estimated on the GPU."""
 from __future__ import annotations
 
 import contextlib
@@ -22,13 +23,16 @@ from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_me
                       calculate_metrics_device, calculate_metrics_f32_device, psnr)
 from .niqe import calculate_niqe, calculate_niqe_device
 from .resize import imresize_device, mod_crop
-from .utils import _get_model_prediction, _run_model_inference_yuv, get_model_total_parameters
+from .utils import (SigmaBank, _get_model_prediction, _run_model_inference_auto, _run_model_inference_yuv,
+                    get_model_total_parameters)
 
 COLUMNS = ['Task', 'Type', 'Dataset', 'Sigma', 'Model', 'Model_Params', 'PSNR', 'SSIM', 'Std_PSNR', 'Std_SSIM',
            'Avg_Time_ms', 'Std_Time_ms']
 #: the columns of an `evaluate_blind` row: the reference's plus the no-reference score
 COLUMNS_BLIND = COLUMNS + ['NIQE', 'Std_NIQE']
 #: the columns of an `evaluate_yuv` row: the reference's, PSNR / SSIM being the luma values, plus the chroma planes'
+#: the columns of an `evaluate_auto_sigma` row: the reference's plus the estimated and the used noise levels
+COLUMNS_AUTO = COLUMNS + ['Sigma_Est', 'Std_Sigma_Est', 'Sigma_Used']
 COLUMNS_YUV = COLUMNS + ['PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'Std_PSNR_U', 'Std_PSNR_V', 'Std_SSIM_U', 'Std_SSIM_V']
 
 
@@ -99,6 +103,44 @@ def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: s
             time_list.append(ms)
     row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
                     model_name=model_name, params=get_model_total_parameters(model))
+    row['Failed'] = failed
+    return row
+
+
+def evaluate_auto_sigma(bank, loader, device, patch_config: dict, *, task: str, subtask: str, dataset: str,
+                        model_name: str, metrics="host", with_ssim=True, skip_failed=True) -> dict:
+    """The row of `evaluate` for a SigmaBank (utils.get_model_bank): per frame the noise level is estimated on the GPU
+    and the checkpoint trained for it runs (utils.run_model_inference_auto; the timed work is that call's, the
+    estimate included).  Scored as `evaluate` scores, failed frames handled as there.  The row's 'Sigma' is 'auto'; it
+    adds 'Sigma_Est' and 'Std_Sigma_Est', mean and standard deviation of the estimates, and 'Sigma_Used', a dict of
+    level -> number of frames that ran with it (COLUMNS_AUTO).  Model_Params counts one model of the bank."""
+    _check_metrics(metrics)
+    if not isinstance(bank, SigmaBank):
+        raise ValueError("evaluate_auto_sigma: bank is a SigmaBank (utils.get_model_bank)")
+    if not isinstance(patch_config, dict) or set(patch_config) != {"patch_size", "patch_overlap"}:
+        raise ValueError("evaluate_auto_sigma: patch_config is {'patch_size': .., 'patch_overlap': ..}")
+    psnr_list, ssim_list, time_list, est_list, failed = [], [], [], [], []
+    used = {}
+    for input_img, target_img, name in loader:
+        with _frame_guard(failed, name, skip_failed, model_name, dataset):
+            pred, ms, est, level, pred_dev = _run_model_inference_auto(bank, input_img, device, **patch_config)
+            if metrics == "device":
+                p, s = _device_metrics(pred, pred_dev, target_img, device, input_img)
+                if not with_ssim:
+                    s = float('nan')
+            else:
+                p, s = _host_metrics(pred, target_img, with_ssim)
+            psnr_list.append(p)
+            ssim_list.append(s)
+            time_list.append(ms)
+            est_list.append(est)
+            used[level] = used.get(level, 0) + 1
+    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma='auto',
+                    model_name=model_name, params=get_model_total_parameters(bank.models[bank.levels[0]]))
+    if not est_list:
+        est_list = [float('nan')]
+    row['Sigma_Est'], row['Std_Sigma_Est'] = np.mean(est_list), np.std(est_list)
+    row['Sigma_Used'] = {level: used[level] for level in bank.levels if level in used}
     row['Failed'] = failed
     return row
 

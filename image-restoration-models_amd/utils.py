@@ -2,8 +2,10 @@
 patch-config lookup and the tiled-patch inference calls.  The device tile
 pipeline they run on (pipeline.py: tile plan, graph cache, extract / forward /
 blend), the metrics (metrics.py), the super-resolution resize (resize.py), NIQE
-(niqe.py), the YUV 4:2:0 conversions (yuv.py) and the frame stream (stream.py)
-are re-exported: every name this module had is still reachable through it.
+(niqe.py), the YUV 4:2:0 conversions (yuv.py), the frame stream (stream.py) and
+the noise estimator (noise.py) are re-exported: every name this module had is
+still reachable through it.  The bank of per-sigma checkpoints and the call that
+routes a frame to the one for its estimated noise level live here.
 """
 from __future__ import annotations
 
@@ -20,6 +22,9 @@ from .frames import plane_slots, to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,  # noqa: F401
                       calculate_metrics_device, calculate_metrics_f32_device, frame_metrics_basicsr_device,
                       frame_metrics_device, frame_metrics_f32_device, psnr, ssim)
+from .noise import (estimate_noise_sigma, estimate_noise_sigma_device, estimate_noise_sigma_yuv,  # noqa: F401
+                    estimate_noise_sigma_yuv_device, noise_sigma_from_stats, noise_stats, noise_stats_device,
+                    noise_stats_yuv_device)
 from .niqe import (calculate_niqe, calculate_niqe_device, load_niqe_params, niqe_feature_distance,  # noqa: F401
                    niqe_features, niqe_features_device, niqe_gamma_table, niqe_plane, niqe_score)
 from .pipeline import (_GRAPH_MAX_BYTES, _GRAPH_MAX_ENTRIES, _MINMAX_WS_FLOATS, _PAD8_MODELS, Restormer,  # noqa: F401
@@ -250,6 +255,79 @@ def _get_model_prediction(model, input_image, device, patch_size, patch_overlap,
         return _run_model_inference(model, input_image, device, normalize=deblurganv2.normalize, pad=deblurganv2.pad,
                                     postprocess=deblurganv2.postprocess, **kw)
     return _run_model_inference(model, input_image, device, pad=pad if pad8 else None, **kw)
+
+
+class SigmaBank:
+    """The checkpoints of one non-blind denoiser, one per noise level: `models` maps sigma (0..255 scale) to model.
+    `levels` are the sigmas in ascending order; `pick` chooses the model for an estimated sigma."""
+
+    def __init__(self, models: dict):
+        try:
+            items = sorted((float(s), s, m) for s, m in dict(models).items())
+        except (TypeError, ValueError):
+            raise ValueError("SigmaBank: models maps a positive sigma to a model") from None
+        if not items or any(not (np.isfinite(f) and f > 0) or not callable(m) for f, _, m in items):
+            raise ValueError("SigmaBank: models maps a positive sigma to a model, at least one")
+        self.levels = [s for _, s, _ in items]
+        self.models = {s: m for _, s, m in items}
+
+    def pick(self, sigma_est) -> tuple:
+        """(level, model) for an estimated sigma: the level nearest in log sigma, so the thresholds between two
+        neighbours are their geometric mean (19.36 and 35.36 for 15 / 25 / 50); a tie goes to the lower level, an
+        estimate <= 0 to the lowest.  NaN (a frame without an unsaturated block) raises ValueError."""
+        sigma_est = float(sigma_est)
+        if np.isnan(sigma_est):
+            raise ValueError("SigmaBank.pick: the sigma estimate is NaN (no unsaturated block in the frame)")
+        level = self.levels[0]
+        for lo, hi in zip(self.levels, self.levels[1:]):
+            if sigma_est > 0 and sigma_est * sigma_est > float(lo) * float(hi):      # above the geometric mean of the two neighbours
+                level = hi
+        return level, self.models[level]
+
+
+def get_model_bank(task, subtask, model_name, device: torch.device, gray=False, sigmas=(15, 25, 50),
+                   precision: str = "fp32") -> SigmaBank:
+    """The SigmaBank of get_model_instance(task, subtask, model_name, device, gray, sigma, precision) over `sigmas`."""
+    sigmas = list(sigmas)
+    if not sigmas:
+        raise ValueError("get_model_bank: at least one sigma")
+    return SigmaBank({s: get_model_instance(task, subtask, model_name, device, gray=gray, sigma=s, precision=precision)
+                      for s in sigmas})
+
+
+def run_model_inference_auto(bank: SigmaBank, input_img: np.ndarray, device: torch.device,
+                             patch_size: int | None = None, patch_overlap: int = 32):
+    """Estimate the frame's noise level on the GPU and run the checkpoint trained for it: returns
+    (prediction, inference_time_ms, sigma_est, sigma_used).
+
+    The uint8 / uint16 frame is uploaded once; estimate_noise_sigma_device reads it there (one read-back of a few
+    integers), bank.pick chooses the model, and the device pipeline call that get_model_prediction makes for that model
+    (its hooks and pad8 by the model class) runs on the same device frame; one download.  The time covers all of it.  The
+    prediction is byte-identical to get_model_prediction(bank.models[sigma_used], input_img, device, patch_size,
+    patch_overlap).  There is no need_degradation: the frame is the noisy one, an estimate of a clean frame says
+    nothing."""
+    pred, ms, sigma_est, sigma_used, _ = _run_model_inference_auto(bank, input_img, device, patch_size, patch_overlap)
+    return pred, ms, sigma_est, sigma_used
+
+
+def _run_model_inference_auto(bank, input_img, device, patch_size=None, patch_overlap=32):
+    """run_model_inference_auto that also hands back the device output tensor."""
+    if not isinstance(bank, SigmaBank):
+        raise ValueError("run_model_inference_auto: bank is a SigmaBank (get_model_bank)")
+    if not isinstance(input_img, np.ndarray) or input_img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("run_model_inference_auto takes a uint8 or uint16 [H, W] or [H, W, C] array: a float frame has "
+                         "no integer codes to estimate from")
+    dev = cuda_device(device, "run_model_inference_auto")
+    start_time = time.time()
+    with torch.no_grad():
+        img_dev = to_device(input_img, dev)
+        sigma_est = estimate_noise_sigma_device(img_dev)
+        sigma_used, model = bank.pick(sigma_est)
+        route = model_route(model)
+        out, _ = tiled_forward_device(model, img_dev, patch_size, patch_overlap, route.pad8, None,
+                                      max_batch=route.max_batch, hooks=route.hooks)
+        output_img = to_host(out)
+    return output_img, (time.time() - start_time) * 1000, sigma_est, sigma_used, out
 
 
 def run_model_chain(stages, input_img: np.ndarray, device: torch.device, need_degradation=False, noise_level=None,

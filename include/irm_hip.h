@@ -544,6 +544,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- PSNR / SSIM of float32 frames and of YUV 4:2:0 planes: irm_frame_metrics_f32, irm_yuv420_metrics */
 #include "irm_hip_metrics.h"
 
+/* ---- the noise level of integer frames from the diagonal Haar band: irm_noise_hh_stats */
+#include "irm_hip_noise.h"
+
 #ifdef __cplusplus
 }
 #endif
