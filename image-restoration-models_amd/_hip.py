@@ -115,6 +115,12 @@ SIGNATURES_NOISE = {
     "irm_noise_hh_stats": [_P, _I, _I, _I, _I, _I, _L, _L, _I, _I, _I, _P, _P, _L, _P],
 }
 
+#: the frame front end and the distance head of LPIPS (lpips.hip), mirrors include/irm_hip_lpips.h one to one
+SIGNATURES_LPIPS = {
+    "irm_lpips_pack": [_P, _I, _I, _I, _I, _L, _L, _F, _F, _F, _F, _F, _F, _P, _L, _P],
+    "irm_lpips_head": [_P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _L, _P],
+}
+
 _lib = None
 
 
@@ -135,7 +141,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM,
                                **SIGNATURES_YUV, **SIGNATURES_INCEPTION, **SIGNATURES_METRICS,
-                               **SIGNATURES_NOISE}.items():
+                               **SIGNATURES_NOISE, **SIGNATURES_LPIPS}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

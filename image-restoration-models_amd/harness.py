@@ -4,7 +4,8 @@ the reference's column names.  Dataset file IO is out of scope - `loader` is any
 (input_uint8_hwc, target_uint8_hwc, name), e.g. `synthetic_loader`.  For a super-resolving model (`model.upscale`
 s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `evaluate_sr` make them from HR frames
 by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics).  Where no target exists
-(real captures), `evaluate_blind` scores the frames by NIQE instead.  `evaluate_stream` is `evaluate` over the frame
+(real captures), `evaluate_blind` scores the frames by NIQE instead; `evaluate_perceptual` adds LPIPS, the perceptual
+distance to the target, to the row of `evaluate`.  `evaluate_stream` is `evaluate` over the frame
 stream (stream.py): several frames per forward, the copies under the forwards.  `evaluate_yuv` takes YUV 4:2:0 plane
 tuples and reports PSNR / SSIM per component.  `evaluate_auto_sigma` takes a bank of per-sigma checkpoints and runs, per
 frame, the one trained for the noise level estimated on the GPU."""
@@ -22,6 +23,7 @@ from .frames import to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,
                       calculate_metrics_device, calculate_metrics_f32_device, psnr)
 from .niqe import calculate_niqe, calculate_niqe_device
+from .perceptual import calculate_lpips, calculate_lpips_device
 from .resize import imresize_device, mod_crop
 from .utils import (SigmaBank, _get_model_prediction, _run_model_inference_auto, _run_model_inference_yuv,
                     get_model_total_parameters)
@@ -33,6 +35,8 @@ COLUMNS_BLIND = COLUMNS + ['NIQE', 'Std_NIQE']
 #: the columns of an `evaluate_yuv` row: the reference's, PSNR / SSIM being the luma values, plus the chroma planes'
 #: the columns of an `evaluate_auto_sigma` row: the reference's plus the estimated and the used noise levels
 COLUMNS_AUTO = COLUMNS + ['Sigma_Est', 'Std_Sigma_Est', 'Sigma_Used']
+#: the columns of an `evaluate_perceptual` row: the reference's plus the perceptual distance to the target
+COLUMNS_PERCEPTUAL = COLUMNS + ['LPIPS', 'Std_LPIPS']
 COLUMNS_YUV = COLUMNS + ['PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'Std_PSNR_U', 'Std_PSNR_V', 'Std_SSIM_U', 'Std_SSIM_V']
 
 
@@ -351,6 +355,52 @@ def evaluate_blind(model, loader, device, patch_config: dict, *, niqe_params, cr
     if not niqe_list:
         niqe_list = [float('nan')]
     row['NIQE'], row['Std_NIQE'] = np.mean(niqe_list), np.std(niqe_list)
+    row['Failed'] = failed
+    return row
+
+
+def evaluate_perceptual(model, loader, device, patch_config: dict, *, lpips_params, metrics="device",
+                        task: str = "perceptual", subtask: str = "N/A", dataset: str = "synthetic",
+                        model_name: str | None = None, sigma='N/A', need_degradation=False, noise_level=None,
+                        with_ssim=True, skip_failed=True) -> dict:
+    """The row of `evaluate` with the perceptual distance beside PSNR and SSIM: per frame the model's prediction, its
+    PSNR / SSIM as `evaluate` computes them and its LPIPS against the target (`lpips_params` from
+    utils.load_lpips_params; 3-channel frames of at least 31 x 31).  The timed region is what `evaluate` times (input
+    upload through output download); every score is outside it.  metrics="device" scores the prediction while it is
+    on the GPU (calculate_lpips_device), metrics="host" the downloaded one (calculate_lpips); they differ by the
+    float32 rounding of the trunk.  model=None scores the inputs themselves (the "before" row; its times are 0).  The
+    row has the reference's columns plus 'LPIPS' and 'Std_LPIPS' (COLUMNS_PERCEPTUAL).  Failed frames are handled as in
+    `evaluate`."""
+    _check_metrics(metrics)
+    if model_name is None:
+        model_name = "Input" if model is None else type(model).__name__
+    psnr_list, ssim_list, lpips_list, time_list, failed = [], [], [], [], []
+    for input_img, target_img, name in loader:
+        with _frame_guard(failed, name, skip_failed, model_name, dataset):
+            if model is None:
+                pred, ms, pred_dev = input_img, 0.0, None
+            else:
+                pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
+                                                           need_degradation=need_degradation, noise_level=noise_level)
+            if metrics == "device":
+                if pred_dev is None:
+                    pred_dev = to_device(pred, device)
+                p, s = _device_metrics(pred, pred_dev, target_img, device, input_img)
+                if not with_ssim:
+                    s = float('nan')
+                q = calculate_lpips_device(pred_dev, to_device(target_img, pred_dev.device), lpips_params)
+            else:
+                p, s = _host_metrics(pred, target_img, with_ssim)
+                q = calculate_lpips(pred, target_img, lpips_params)
+            psnr_list.append(p)
+            ssim_list.append(s)
+            lpips_list.append(q)
+            time_list.append(ms)
+    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
+                    model_name=model_name, params=0 if model is None else get_model_total_parameters(model))
+    if not lpips_list:
+        lpips_list = [float('nan')]
+    row['LPIPS'], row['Std_LPIPS'] = np.mean(lpips_list), np.std(lpips_list)
     row['Failed'] = failed
     return row
 

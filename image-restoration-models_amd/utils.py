@@ -2,8 +2,8 @@
 patch-config lookup and the tiled-patch inference calls.  The device tile
 pipeline they run on (pipeline.py: tile plan, graph cache, extract / forward /
 blend), the metrics (metrics.py), the super-resolution resize (resize.py), NIQE
-(niqe.py), the YUV 4:2:0 conversions (yuv.py), the frame stream (stream.py) and
-the noise estimator (noise.py) are re-exported: every name this module had is
+(niqe.py), LPIPS (perceptual.py), the YUV 4:2:0 conversions (yuv.py), the frame
+stream (stream.py) and the noise estimator (noise.py) are re-exported: every name this module had is
 still reachable through it.  The bank of per-sigma checkpoints and the call that
 routes a frame to the one for its estimated noise level live here.
 """
@@ -27,6 +27,8 @@ from .noise import (estimate_noise_sigma, estimate_noise_sigma_device, estimate_
                     noise_stats_yuv_device)
 from .niqe import (calculate_niqe, calculate_niqe_device, load_niqe_params, niqe_feature_distance,  # noqa: F401
                    niqe_features, niqe_features_device, niqe_gamma_table, niqe_plane, niqe_score)
+from .perceptual import (LpipsParams, calculate_lpips, calculate_lpips_device, frame_lpips_device,  # noqa: F401
+                         load_lpips_params, lpips_params_from_state, lpips_taps)
 from .pipeline import (_GRAPH_MAX_BYTES, _GRAPH_MAX_ENTRIES, _MINMAX_WS_FLOATS, _PAD8_MODELS, Restormer,  # noqa: F401
                        TilePipelinePlan, _forward_tiles, _frame_range_on, _model_hooks, _no_cyclic_gc,
                        _release_workspace, _side_stream, _tile_pipeline_plan, _tile_pipeline_run, _unit_range_on,

@@ -547,6 +547,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- the noise level of integer frames from the diagonal Haar band: irm_noise_hh_stats */
 #include "irm_hip_noise.h"
 
+/* ---- LPIPS (AlexNet) around the conv trunk: irm_lpips_pack, irm_lpips_head */
+#include "irm_hip_lpips.h"
+
 #ifdef __cplusplus
 }
 #endif
