@@ -121,6 +121,14 @@ SIGNATURES_LPIPS = {
     "irm_lpips_head": [_P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _L, _P],
 }
 
+#: YUV frames of every sampling structure and depth: the conversions and the scores (yuv.hip, metrics_video.hip), mirrors
+#: include/irm_hip_video.h one to one
+SIGNATURES_VIDEO = {
+    "irm_yuv_to_rgb_f32": [_P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "irm_rgb_f32_to_yuv": [_P, _P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "irm_yuv_metrics": [_P, _P, _P, _I, _L, _L, _P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+}
+
 _lib = None
 
 
@@ -141,7 +149,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM,
                                **SIGNATURES_YUV, **SIGNATURES_INCEPTION, **SIGNATURES_METRICS,
-                               **SIGNATURES_NOISE, **SIGNATURES_LPIPS}.items():
+                               **SIGNATURES_NOISE, **SIGNATURES_LPIPS, **SIGNATURES_VIDEO}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

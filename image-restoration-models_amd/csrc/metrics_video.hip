@@ -1,7 +1,8 @@
 // PSNR / SSIM of the two kinds of frame that never pass through 255 RGB levels (include/irm_hip_metrics.h):
 //   irm_frame_metrics_f32   K float32 frames [H][W][C] against their targets: fp64 squared error and SSIM;
 //   irm_yuv420_metrics      the planes of one YUV 4:2:0 frame (I420, NV12, P010) against the target's, per component:
-//                           exact integer squared error and SSIM of Y, U and V.
+//                           exact integer squared error and SSIM of Y, U and V;
+//   irm_yuv_metrics         the same for 4:2:0, 4:2:2 and 4:4:4 planes at 8, 10 and 12 bit (include/irm_hip_video.h).
 // The SSIM is that of metrics.hip (skimage's defaults: 7x7 uniform window, K1 = .01, K2 = .03, sample covariance 49/48,
 // mean over the interior), and so are the tile geometry (SsimTile), the workspace slots and the fixed-order sums of
 // irm_frame.h.  One kernel template serves both entries; what differs is a policy (Src) that names the plane pair a
@@ -9,7 +10,8 @@
 //   float32   moments in fp64.  A float32 product is exact in fp64, the seven-row and then seven-column sums are rounded
 //             in that fixed order;
 //   8 bit     moments in int32: (49 * 255)^2 < 2^31;
-//   10 bit    moments in int64: (49 * 1023)^2 = 2.5e9 does not fit 32 bits.
+//   10 bit    moments in int64: (49 * 1023)^2 = 2.5e9 does not fit 32 bits;
+//   12 bit    moments in int64: (49 * 4095)^2 = 4.0e10.
 // The last step forms numerator and denominator from the SAME rounded products (pxx, pyy, pxy below), one rounded
 // operation each: identical frames give num == den bit for bit, SSIM exactly 1 and a squared error of exactly 0.  The
 // file is built with -ffp-contract=off (csrc/Makefile), so no product is fused into the sum that takes it.
@@ -226,7 +228,7 @@ extern "C" int irm_frame_metrics_f32(const float* pred, const float* target, int
 }
 
 // ---------------------------------------------------------------------------
-// YUV 4:2:0 planes: the tiles of Y, then those of U, then those of V, in one grid; a tile's slot is its block
+// YUV planes: the tiles of Y, then those of U, then those of V, in one grid; a tile's slot is its block
 struct YuvSide {
     const void* y;
     const void* u;
@@ -244,7 +246,7 @@ struct YuvSrc {
     YuvSide p, q;
     mv_u64* sse_part;                  // [ny + 2 nc]
     double* ssim_part;
-    int H, W, shift;
+    int H, W, CH, CW, shift;           // luma and chroma extents
     int ny, ytx, yty, nc, ctx, cty;    // tiles of the luma plane and of one chroma plane
     double k1, k2;
     __device__ __forceinline__ MvPlane<T> plane() const {
@@ -253,7 +255,7 @@ struct YuvSrc {
             return {(const T*)p.y, (const T*)q.y, p.pitch_y, q.pitch_y, 1, p.vec_y, q.vec_y, H, W, ytx, yty, b, b};
         const bool is_v = b - ny >= nc;
         return {(const T*)(is_v ? p.v : p.u), (const T*)(is_v ? q.v : q.u), p.pitch_c, q.pitch_c, p.step, p.vec_c,
-                q.vec_c, H / 2, W / 2, ctx, cty, b - ny - (is_v ? nc : 0), b};
+                q.vec_c, CH, CW, ctx, cty, b - ny - (is_v ? nc : 0), b};
     }
     __device__ __forceinline__ V value(T s) const { return (V)(s >> shift); }
     static __device__ __forceinline__ mv_u64 bits(mv_u64 e) { return e; }
@@ -282,15 +284,54 @@ __global__ __launch_bounds__(256) void yuv_reduce_kernel(const mv_u64* sse_part,
 
 // The checks of one side and its piece flags; es = bytes per sample
 static bool yuv_side(YuvSide& s, const void* y, const void* u, const void* v, int step, long pitch_y, long pitch_c,
-                     int luma_only, int W, uintptr_t es) {
+                     int luma_only, int W, int CW, uintptr_t es) {
     if (!y || pitch_y < W || (reinterpret_cast<uintptr_t>(y) & (es - 1))) return false;
     s = YuvSide{y, u, v, pitch_y, pitch_c, step, 0, 0};
     s.vec_y = irm_aligned16(y) && (pitch_y * (long)es) % 16 == 0;
     if (luma_only) return true;
-    if (!u || !v || (step != 1 && step != 2) || pitch_c < (long)step * (W / 2)) return false;
+    if (!u || !v || (step != 1 && step != 2) || pitch_c < (long)step * CW) return false;
     if ((reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(v)) & (es - 1)) return false;
     s.vec_c = step == 1 && irm_aligned16(u) && irm_aligned16(v) && (pitch_c * (long)es) % 16 == 0;
     return true;
+}
+
+// What the two entries share: the checks of the sides and the workspace, and the two launches.  shift: the code is the
+// word shifted right by it.  The extents, depth and flags are checked by the entries.
+static int yuv_metrics_run(const void* pred_y, const void* pred_u, const void* pred_v, int pred_step, long pred_pitch_y,
+                           long pred_pitch_c, const void* target_y, const void* target_u, const void* target_v,
+                           int target_step, long target_pitch_y, long target_pitch_c, int sub_w, int sub_h, int depth,
+                           int shift, int luma_only, int H, int W, unsigned long long* sse, double* ssim, void* ws,
+                           long ws_words, hipStream_t stream) {
+    const int CH = H / sub_h, CW = W / sub_w;
+    const uintptr_t es = depth == 8 ? 1 : 2;
+    YuvSide p, q;
+    if (!yuv_side(p, pred_y, pred_u, pred_v, pred_step, pred_pitch_y, pred_pitch_c, luma_only, W, CW, es)) return IRM_EINVAL;
+    if (!yuv_side(q, target_y, target_u, target_v, target_step, target_pitch_y, target_pitch_c, luma_only, W, CW, es))
+        return IRM_EINVAL;
+    if (!luma_only && pred_step != target_step) return IRM_EINVAL;
+    const int ytx = (W - 6 + MV_OUT - 1) / MV_OUT, yty = (H - 6 + MV_ROWS - 1) / MV_ROWS;
+    const int ctx = luma_only ? 0 : (CW - 6 + MV_OUT - 1) / MV_OUT, cty = luma_only ? 0 : (CH - 6 + MV_ROWS - 1) / MV_ROWS;
+    const long ny = (long)ytx * yty, nc = (long)ctx * cty, total = ny + 2 * nc;
+    if (ws_words < 2 * total || total > 0x7fffffffL) return IRM_EINVAL;
+    mv_u64* sse_part = reinterpret_cast<mv_u64*>(ws);
+    double* ssim_part = reinterpret_cast<double*>(sse_part + total);
+    const double range = (double)((1 << depth) - 1);
+    const double c1 = (0.01 * range) * (0.01 * range), c2 = (0.03 * range) * (0.03 * range);
+    if (depth == 8) {
+        const YuvSrc<unsigned char, int> a{p, q, sse_part, ssim_part, H, W, CH, CW, shift, (int)ny, ytx, yty, (int)nc, ctx,
+                                           cty, 2401.0 * c1, 2352.0 * c2};
+        hipLaunchKernelGGL((ssim7_tile_kernel<YuvSrc<unsigned char, int>>), dim3((unsigned)total), dim3(256), 0, stream, a);
+    } else {
+        const YuvSrc<unsigned short, long long> a{p, q, sse_part, ssim_part, H, W, CH, CW, shift, (int)ny, ytx, yty, (int)nc,
+                                                  ctx, cty, 2401.0 * c1, 2352.0 * c2};
+        hipLaunchKernelGGL((ssim7_tile_kernel<YuvSrc<unsigned short, long long>>), dim3((unsigned)total), dim3(256), 0,
+                           stream, a);
+    }
+    if (hipGetLastError() != hipSuccess) return IRM_ELAUNCH;
+    const double count_y = (double)(H - 6) * (W - 6), count_c = (double)(CH - 6) * (CW - 6);
+    hipLaunchKernelGGL(yuv_reduce_kernel, dim3(luma_only ? 1 : 3), dim3(256), 0, stream, sse_part, ssim_part, (int)ny,
+                       (int)nc, count_y, count_c, sse, ssim);
+    return irm_launch_status();
 }
 
 extern "C" int irm_yuv420_metrics(const void* pred_y, const void* pred_u, const void* pred_v, int pred_step,
@@ -305,34 +346,26 @@ extern "C" int irm_yuv420_metrics(const void* pred_y, const void* pred_u, const 
         return IRM_EINVAL;
     const int least = luma_only ? 8 : 14;                  // a chroma plane holds one 7 x 7 window
     if (H < least || W < least || (H & 1) || (W & 1) || H > (1 << 20) || W > (1 << 20)) return IRM_EINVAL;
-    const uintptr_t es = depth == 8 ? 1 : 2;
-    YuvSide p, q;
-    if (!yuv_side(p, pred_y, pred_u, pred_v, pred_step, pred_pitch_y, pred_pitch_c, luma_only, W, es)) return IRM_EINVAL;
-    if (!yuv_side(q, target_y, target_u, target_v, target_step, target_pitch_y, target_pitch_c, luma_only, W, es))
+    return yuv_metrics_run(pred_y, pred_u, pred_v, pred_step, pred_pitch_y, pred_pitch_c, target_y, target_u, target_v,
+                           target_step, target_pitch_y, target_pitch_c, 2, 2, depth, is_p010 ? 6 : 0, luma_only, H, W, sse,
+                           ssim, ws, ws_words, stream);
+}
+
+extern "C" int irm_yuv_metrics(const void* pred_y, const void* pred_u, const void* pred_v, int pred_step,
+                               long pred_pitch_y, long pred_pitch_c, const void* target_y, const void* target_u,
+                               const void* target_v, int target_step, long target_pitch_y, long target_pitch_c, int sub_w,
+                               int sub_h, int depth, int upper_bits, int luma_only, int H, int W, unsigned long long* sse,
+                               double* ssim, void* ws, long ws_words, hipStream_t stream) {
+    if (!sse || !ssim || !ws) return IRM_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(sse) | reinterpret_cast<uintptr_t>(ssim) | reinterpret_cast<uintptr_t>(ws)) & 7)
         return IRM_EINVAL;
-    if (!luma_only && pred_step != target_step) return IRM_EINVAL;
-    const int ytx = (W - 6 + MV_OUT - 1) / MV_OUT, yty = (H - 6 + MV_ROWS - 1) / MV_ROWS;
-    const int ctx = luma_only ? 0 : (W / 2 - 6 + MV_OUT - 1) / MV_OUT, cty = luma_only ? 0 : (H / 2 - 6 + MV_ROWS - 1) / MV_ROWS;
-    const long ny = (long)ytx * yty, nc = (long)ctx * cty, total = ny + 2 * nc;
-    if (ws_words < 2 * total || total > 0x7fffffffL) return IRM_EINVAL;
-    mv_u64* sse_part = reinterpret_cast<mv_u64*>(ws);
-    double* ssim_part = reinterpret_cast<double*>(sse_part + total);
-    const double range = depth == 8 ? 255.0 : 1023.0;
-    const double c1 = (0.01 * range) * (0.01 * range), c2 = (0.03 * range) * (0.03 * range);
-    const int shift = is_p010 ? 6 : 0;
-    if (depth == 8) {
-        const YuvSrc<unsigned char, int> a{p, q, sse_part, ssim_part, H, W, shift, (int)ny, ytx, yty, (int)nc, ctx, cty,
-                                           2401.0 * c1, 2352.0 * c2};
-        hipLaunchKernelGGL((ssim7_tile_kernel<YuvSrc<unsigned char, int>>), dim3((unsigned)total), dim3(256), 0, stream, a);
-    } else {
-        const YuvSrc<unsigned short, long long> a{p, q, sse_part, ssim_part, H, W, shift, (int)ny, ytx, yty, (int)nc, ctx,
-                                                  cty, 2401.0 * c1, 2352.0 * c2};
-        hipLaunchKernelGGL((ssim7_tile_kernel<YuvSrc<unsigned short, long long>>), dim3((unsigned)total), dim3(256), 0,
-                           stream, a);
-    }
-    if (hipGetLastError() != hipSuccess) return IRM_ELAUNCH;
-    const double count_y = (double)(H - 6) * (W - 6), count_c = (double)(H / 2 - 6) * (W / 2 - 6);
-    hipLaunchKernelGGL(yuv_reduce_kernel, dim3(luma_only ? 1 : 3), dim3(256), 0, stream, sse_part, ssim_part, (int)ny,
-                       (int)nc, count_y, count_c, sse, ssim);
-    return irm_launch_status();
+    if (!((sub_w == 2 && sub_h == 2) || (sub_w == 2 && sub_h == 1) || (sub_w == 1 && sub_h == 1))) return IRM_EINVAL;
+    if ((depth != 8 && depth != 10 && depth != 12) || !irm_is_flag(upper_bits) || (depth == 8 && upper_bits)
+        || !irm_is_flag(luma_only)) return IRM_EINVAL;
+    if (H <= 0 || W <= 0 || H % sub_h || W % sub_w || H > (1 << 20) || W > (1 << 20)) return IRM_EINVAL;
+    // a chroma plane holds one 7 x 7 window; the luma plane alone with luma_only
+    if (luma_only ? (H < 7 || W < 7) : (H / sub_h < 7 || W / sub_w < 7)) return IRM_EINVAL;
+    return yuv_metrics_run(pred_y, pred_u, pred_v, pred_step, pred_pitch_y, pred_pitch_c, target_y, target_u, target_v,
+                           target_step, target_pitch_y, target_pitch_c, sub_w, sub_h, depth, upper_bits ? 16 - depth : 0,
+                           luma_only, H, W, sse, ssim, ws, ws_words, stream);
 }

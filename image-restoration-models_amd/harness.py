@@ -6,8 +6,8 @@ s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `ev
 by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics).  Where no target exists
 (real captures), `evaluate_blind` scores the frames by NIQE instead; `evaluate_perceptual` adds LPIPS, the perceptual
 distance to the target, to the row of `evaluate`.  `evaluate_stream` is `evaluate` over the frame
-stream (stream.py): several frames per forward, the copies under the forwards.  `evaluate_yuv` takes YUV 4:2:0 plane
-tuples and reports PSNR / SSIM per component.  `evaluate_auto_sigma` takes a bank of per-sigma checkpoints and runs, per
+stream (stream.py): several frames per forward, the copies under the forwards.  `evaluate_yuv` takes YUV plane
+tuples (4:2:0, 4:2:2, 4:4:4; `y4m_pairs` reads them from two YUV4MPEG2 files) and reports PSNR / SSIM per component.  `evaluate_auto_sigma` takes a bank of per-sigma checkpoints and runs, per
 frame, the one trained for the noise level estimated on the GPU."""
 from __future__ import annotations
 
@@ -18,7 +18,7 @@ import time
 
 import numpy as np
 
-from . import stream, synth, yuv
+from . import stream, synth, y4m, yuv
 from .frames import to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,
                       calculate_metrics_device, calculate_metrics_f32_device, psnr)
@@ -274,11 +274,37 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
     return row
 
 
+class y4m_pairs:
+    """The loader of `evaluate_yuv` over two YUV4MPEG2 files, degraded input and target: yields (planes, target_planes,
+    name) frame by frame, name = "<input file>#<frame index>".  ValueError if the two headers differ in frame size or
+    format.  `fmt` and `siting` (and `full_range`, None if the input does not say) are the keyword values to pass on;
+    `frames` is the number of pairs."""
+
+    def __init__(self, input_path, target_path):
+        self.input, self.target = y4m.read_y4m(input_path), y4m.read_y4m(target_path)
+        a, b = self.input, self.target
+        if (a.width, a.height) != (b.width, b.height):
+            raise ValueError(f"y4m_pairs: {a.path} is {a.width} x {a.height}, {b.path} is {b.width} x {b.height}")
+        if a.fmt != b.fmt:
+            raise ValueError(f"y4m_pairs: {a.path} is {a.fmt!r}, {b.path} is {b.fmt!r}")
+        self.fmt, self.siting, self.full_range = a.fmt, a.siting, a.full_range
+        self.frames = min(a.frames, b.frames)
+
+    def __len__(self):
+        return self.frames
+
+    def __iter__(self):
+        base = os.path.basename(self.input.path)
+        for i, (planes, target_planes) in enumerate(zip(self.input, self.target)):
+            yield planes, target_planes, f"{base}#{i}"
+
+
 def evaluate_yuv(model, loader, device, patch_config: dict, *, fmt, matrix="bt709", full_range=False, siting="left",
                  luma_only=False, metrics="device", task: str, subtask: str, dataset: str, model_name: str, sigma='N/A',
                  need_degradation=False, noise_level=None, skip_failed=True) -> dict:
-    """One results_table row for YUV 4:2:0 video frames: `loader` yields (planes, target_planes, name), the planes as
-    run_model_inference_yuv takes them (numpy arrays in `fmt`; matrix, full_range and siting describe the frames).  The
+    """One results_table row for YUV video frames: `loader` yields (planes, target_planes, name), the planes as
+    run_model_inference_yuv takes them (numpy arrays in `fmt`, any name of yuv.YUV_LAYOUTS; matrix, full_range and
+    siting describe the frames; `y4m_pairs` is such a loader).  The
     prediction and the timed region are run_model_inference_yuv's, plane upload through plane download; scoring is
     outside it.  metrics="device" scores the restored planes while they are on the GPU (calculate_metrics_yuv_device:
     the target planes are uploaded), metrics="host" the downloaded ones (calculate_metrics_yuv); they differ by
@@ -286,7 +312,7 @@ def evaluate_yuv(model, loader, device, patch_config: dict, *, fmt, matrix="bt70
     SSIM the luma values, plus PSNR_U, PSNR_V, SSIM_U, SSIM_V and their Std_ forms (COLUMNS_YUV); with luma_only the
     chroma columns are NaN.  Failed frames are handled as in `evaluate`."""
     _check_metrics(metrics)
-    yuv._check_options(fmt, matrix, siting)
+    yuv._check_layout_options(fmt, matrix, siting)
     if not isinstance(patch_config, dict) or set(patch_config) != {"patch_size", "patch_overlap"}:
         raise ValueError("evaluate_yuv: patch_config is {'patch_size': .., 'patch_overlap': ..}")
     scores, time_list, failed = [], [], []

@@ -39,7 +39,6 @@ from .frames import device_constant, plane_slots, psnr_from_error
 from .metrics import frame_metrics_device
 from .pipeline import (_check_out, _tile_pipeline_plan, _tile_pipeline_run, _value_kinds, cuda_device, model_route,
                        refuse_deblurgan)
-from .yuv import YUV_FORMATS
 
 #: plans (buffers of one frame shape and dtype) a stream keeps, least recently used first out
 MAX_PLANS = 4
@@ -141,18 +140,18 @@ class _Front:
 
 
 class _YuvFront(_Front):
-    """4:2:0 plane tuples: the route of run_model_inference_yuv with the planes of K frames behind one another."""
+    """YUV plane tuples (any format of yuv.YUV_LAYOUTS): the route of run_model_inference_yuv with the planes of K frames behind one another."""
 
     def __init__(self, model, patch_size, patch_overlap, need_degradation, noise_level, fmt, matrix, full_range, siting,
                  luma_only):
         refuse_deblurgan(model, "run_model_inference_stream", "convert with yuv420_to_rgb_host and stream the RGB frames")
-        yuv._check_options(fmt, matrix, siting)
+        yuv._check_layout_options(fmt, matrix, siting)
         super().__init__(model, patch_size, patch_overlap, need_degradation, noise_level, "float32", True)
         if luma_only and self.route.s > 1:
             raise ValueError(f"luma_only with model.upscale = {self.route.s}: the chroma planes would need a resize")
         self.fmt, self.luma_only = fmt, bool(luma_only)
         self.opts = dict(matrix=matrix, full_range=full_range, siting=siting, luma_only=self.luma_only)
-        self.np_dtype = np.uint16 if YUV_FORMATS[fmt][1] == 10 else np.uint8
+        self.np_dtype = yuv._np_dtype(fmt)
 
     def prepare(self, planes):
         h, w = yuv._check_planes(planes, self.fmt, False, np.ndarray, (self.np_dtype,))
@@ -165,10 +164,10 @@ class _YuvFront(_Front):
         return ((h, w, 1 if self.luma_only else 3), torch.float32, "float32", True), planes_in, dt, planes_out, dt
 
     def compute(self, plan, slot: int, k: int):
-        rgb = [yuv.yuv420_to_rgb_device(tuple(p), self.fmt, **self.opts) for p in plan.dev_in[slot][:k]]
+        rgb = [yuv.yuv_to_rgb_device(tuple(p), self.fmt, **self.opts) for p in plan.dev_in[slot][:k]]
         res = _tile_pipeline_run(self.model, plan.tp, rgb, None, self.route.max_batch, None)
         for (frame, _), planes in zip(res, plan.dev_out[slot][:k]):
-            yuv.rgb_to_yuv420_device(frame, self.fmt, out=tuple(planes), **self.opts)
+            yuv.rgb_to_yuv_device(frame, self.fmt, out=tuple(planes), **self.opts)
 
     def finish(self, planes, outs):
         return tuple(outs) + tuple(planes[1:]) if self.luma_only else tuple(outs)     # the chroma as it came in
@@ -343,7 +342,7 @@ def run_model_inference_stream(model, frames, device, *, patch_size=None, patch_
 
     fmt=None: frames are uint8 / uint16 / float32 [H, W, C] numpy arrays, and a prediction is what
     tiled_forward_device_batch(..., unit_range=, out=) gives for the frame, downloaded (uint16 through its int16 bit
-    pattern).  fmt in YUV_FORMATS: a frame is the plane tuple run_model_inference_yuv takes and a prediction the plane
+    pattern).  fmt in yuv.YUV_LAYOUTS: a frame is the plane tuple run_model_inference_yuv takes and a prediction the plane
     tuple it returns, by the same route (matrix, full_range, siting and luma_only as there; out and unit_range do not
     apply).  The hooks follow the model class as get_model_prediction picks them, and what the one-frame calls refuse
     is refused here with ValueError - the arguments when the function is called, a frame when the iterable hands it

@@ -36,9 +36,10 @@ from .pipeline import (_GRAPH_MAX_BYTES, _GRAPH_MAX_ENTRIES, _MINMAX_WS_FLOATS, 
                        is_deblurgan, model_route, noise_field, refuse_deblurgan, tile_origins, tile_plan,
                        tiled_forward_device, tiled_forward_device_batch)
 from .resize import imresize_device, imresize_host, mod_crop, resize_table  # noqa: F401
-from .yuv import (YUV_FORMATS, YuvMetrics, calculate_metrics_yuv, calculate_metrics_yuv_device,  # noqa: F401
-                  frame_metrics_yuv_device, rgb_to_yuv420_device, rgb_to_yuv420_host, yuv420_to_rgb_device,
-                  yuv420_to_rgb_host)
+from .y4m import read_y4m, write_y4m  # noqa: F401
+from .yuv import (YUV_FORMATS, YUV_LAYOUTS, YuvMetrics, calculate_metrics_yuv, calculate_metrics_yuv_device,  # noqa: F401
+                  frame_metrics_yuv_device, rgb_to_yuv420_device, rgb_to_yuv420_host, rgb_to_yuv_device,
+                  rgb_to_yuv_host, yuv420_to_rgb_device, yuv420_to_rgb_host, yuv_to_rgb_device, yuv_to_rgb_host)
 from .stream import group_frames, run_model_inference_stream  # noqa: F401
 from .convnet_common import check_precision
 from .configs import PATCH_CONFIG, ROOT_RESULTS_DIR, ROOT_WEIGHTS_DIR
@@ -386,14 +387,15 @@ def run_model_chain(stages, input_img: np.ndarray, device: torch.device, need_de
 def run_model_inference_yuv(model: Module, planes, device: torch.device, *, fmt, matrix="bt709", full_range=False,
                             siting="left", luma_only=False, patch_size: int | None = None, patch_overlap: int = 32,
                             need_degradation=False, noise_level=None):
-    """Restore one YUV 4:2:0 video frame: returns (planes, inference_time_ms), the planes in the format they came in
+    """Restore one YUV video frame: returns (planes, inference_time_ms), the planes in the format they came in
     and the time from their upload through the download of the result, as run_model_inference's.
 
-    `planes` are numpy arrays, (y, u, v) for fmt "i420" and (y, uv) for "nv12" / "p010" (yuv.py has the layouts).
-    They go up as they are - 1.5 bytes per pixel, 3 for "p010" -, irm_yuv420_to_rgb_f32 makes the float32 RGB frame
-    in [0, 1], the device pipeline of run_model_inference runs on it with the hooks get_model_prediction picks for
-    the model class (unit_range=True, out="float32": the frame is never rounded to 255 RGB levels),
-    irm_rgb_f32_to_yuv420 makes the planes and they come down.  matrix, full_range and siting describe the frame
+    `planes` are numpy arrays in any format of yuv.YUV_LAYOUTS - 4:2:0, 4:2:2 or 4:4:4 at 8, 10 or 12 bit -, (y, u, v)
+    for the planar names ("i420", "i422p10", "i444p12", ..) and (y, uv) for the semi-planar ones ("nv12", "p010",
+    "p210", ..).  They go up as they are - 1.5 bytes per pixel for "nv12", 6 for "i444p10" -, irm_yuv_to_rgb_f32 makes
+    the float32 RGB frame in [0, 1], the device pipeline of run_model_inference runs on it with the hooks
+    get_model_prediction picks for the model class (unit_range=True, out="float32": the frame is never rounded to 255
+    RGB levels), irm_rgb_f32_to_yuv makes the planes and they come down.  matrix, full_range and siting describe the frame
     (DESIGN.md section 16).  A super-resolving model returns the planes of an s H x s W frame.
 
     luma_only=True restores Y alone with a one-channel model (REDNet, the gray DnCNN): the chroma planes are not
@@ -413,8 +415,8 @@ def _run_model_inference_yuv(model, planes, device, *, fmt, matrix="bt709", full
         raise ValueError("run_model_inference_yuv: model must be a model, not None")
     refuse_deblurgan(model, "run_model_inference_yuv",
                      "convert with yuv420_to_rgb_host and run it with get_model_prediction")
-    yuv._check_options(fmt, matrix, siting)
-    yuv._check_planes(planes, fmt, False, np.ndarray, (np.uint16,) if YUV_FORMATS[fmt][1] == 10 else (np.uint8,))
+    yuv._check_layout_options(fmt, matrix, siting)
+    yuv._check_planes(planes, fmt, False, np.ndarray, (yuv._np_dtype(fmt),))
     route = model_route(model, need_degradation, noise_level)
     if luma_only and route.s > 1:
         raise ValueError(f"luma_only with model.upscale = {route.s}: the chroma planes would need a resize")
@@ -423,16 +425,16 @@ def _run_model_inference_yuv(model, planes, device, *, fmt, matrix="bt709", full
     start_time = time.time()
     with torch.no_grad():
         up = tuple(to_device(p, dev) for p in (planes[:1] if luma_only else planes))
-        frame = yuv420_to_rgb_device(up, fmt, **opts)
+        frame = yuv_to_rgb_device(up, fmt, **opts)
         frame, _ = tiled_forward_device(model, frame, patch_size, patch_overlap, route.pad8, route.sigma,
                                         max_batch=route.max_batch, unit_range=True, out="float32")
         if luma_only:
-            rgb_to_yuv420_device(frame, fmt, out=up, **opts)           # same size: Y is overwritten in place
+            rgb_to_yuv_device(frame, fmt, out=up, **opts)              # same size: Y is overwritten in place
             result, planes_dev = (to_host(up[0]),) + tuple(planes[1:]), up
         else:
             # the planes of the result lie behind one another in one buffer, as a decoder lays them out: one download
             buf, (views,), _ = plane_slots(yuv.plane_shapes(frame.shape[0], frame.shape[1], fmt), up[0].dtype, 1, dev, False)
-            rgb_to_yuv420_device(frame, fmt, out=tuple(views), **opts)
+            rgb_to_yuv_device(frame, fmt, out=tuple(views), **opts)
             host = to_host(buf)                                        # and the same views of it on the host
             result, planes_dev = tuple(host[v.storage_offset():][:v.numel()].reshape(v.shape) for v in views), tuple(views)
     return result, (time.time() - start_time) * 1000, planes_dev

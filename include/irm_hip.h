@@ -550,6 +550,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- LPIPS (AlexNet) around the conv trunk: irm_lpips_pack, irm_lpips_head */
 #include "irm_hip_lpips.h"
 
+/* ---- YUV 4:2:0 / 4:2:2 / 4:4:4 frames at 8, 10 and 12 bit: irm_yuv_to_rgb_f32, irm_rgb_f32_to_yuv, irm_yuv_metrics */
+#include "irm_hip_video.h"
+
 #ifdef __cplusplus
 }
 #endif
