@@ -129,6 +129,14 @@ SIGNATURES_VIDEO = {
     "irm_yuv_metrics": [_P, _P, _P, _I, _L, _L, _P, _P, _P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
 }
 
+#: the aligned scoring protocol: gain and planes, the ECC iteration, the warp and its masked scores (align.hip), mirrors
+#: include/irm_hip_align.h one to one
+SIGNATURES_ALIGN = {
+    "irm_align_prepare": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    "irm_ecc_iterate": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P],
+    "irm_aligned_metrics": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+}
+
 _lib = None
 
 
@@ -149,7 +157,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM,
                                **SIGNATURES_YUV, **SIGNATURES_INCEPTION, **SIGNATURES_METRICS,
-                               **SIGNATURES_NOISE, **SIGNATURES_LPIPS, **SIGNATURES_VIDEO}.items():
+                               **SIGNATURES_NOISE, **SIGNATURES_LPIPS, **SIGNATURES_VIDEO,
+                               **SIGNATURES_ALIGN}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

@@ -6,7 +6,8 @@ s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `ev
 by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics).  Where no target exists
 (real captures), `evaluate_blind` scores the frames by NIQE instead; `evaluate_perceptual` adds LPIPS, the perceptual
 distance to the target, to the row of `evaluate`.  `evaluate_stream` is `evaluate` over the frame
-stream (stream.py): several frames per forward, the copies under the forwards.  `evaluate_yuv` takes YUV plane
+stream (stream.py): several frames per forward, the copies under the forwards.  `evaluate_aligned` scores beam-splitter pairs (RealBlur) as published: after an ECC
+alignment, under the mask of the warp (align.py).  `evaluate_yuv` takes YUV plane
 tuples (4:2:0, 4:2:2, 4:4:4; `y4m_pairs` reads them from two YUV4MPEG2 files) and reports PSNR / SSIM per component.  `evaluate_auto_sigma` takes a bank of per-sigma checkpoints and runs, per
 frame, the one trained for the noise level estimated on the GPU."""
 from __future__ import annotations
@@ -19,6 +20,7 @@ import time
 import numpy as np
 
 from . import stream, synth, y4m, yuv
+from .align import calculate_metrics_aligned, calculate_metrics_aligned_device
 from .frames import to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,
                       calculate_metrics_device, calculate_metrics_f32_device, psnr)
@@ -37,6 +39,9 @@ COLUMNS_BLIND = COLUMNS + ['NIQE', 'Std_NIQE']
 COLUMNS_AUTO = COLUMNS + ['Sigma_Est', 'Std_Sigma_Est', 'Sigma_Used']
 #: the columns of an `evaluate_perceptual` row: the reference's plus the perceptual distance to the target
 COLUMNS_PERCEPTUAL = COLUMNS + ['LPIPS', 'Std_LPIPS']
+#: the columns of an `evaluate_aligned` row: the reference's, PSNR / SSIM being the aligned ones, plus the correlation
+#: the alignment reached and the share of the frame under the warp's mask
+COLUMNS_ALIGNED = COLUMNS + ['Rho', 'Coverage', 'Std_Rho', 'Std_Coverage']
 COLUMNS_YUV = COLUMNS + ['PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'Std_PSNR_U', 'Std_PSNR_V', 'Std_SSIM_U', 'Std_SSIM_V']
 
 
@@ -427,6 +432,51 @@ def evaluate_perceptual(model, loader, device, patch_config: dict, *, lpips_para
     if not lpips_list:
         lpips_list = [float('nan')]
     row['LPIPS'], row['Std_LPIPS'] = np.mean(lpips_list), np.std(lpips_list)
+    row['Failed'] = failed
+    return row
+
+
+def evaluate_aligned(model, loader, device, patch_config: dict, *, iterations: int = 100, metrics="device",
+                     task: str = "deblurring", subtask: str = "motion", dataset: str = "RealBlur",
+                     model_name: str | None = None, sigma='N/A', need_degradation=False, noise_level=None,
+                     skip_failed=True) -> dict:
+    """The row of `evaluate` for pairs that are only approximately registered (RealBlur_J, RealBlur_R): PSNR / SSIM are
+    those of the aligned protocol (align.py: gain, ECC homography with `iterations` rounds, bicubic warp, scores under
+    the warp's mask; uint8 / uint16 3-channel frames, both sides at least 11).  The timed region is what `evaluate` times
+    (input upload through output download); alignment and scoring are outside it.  metrics="device" scores the
+    prediction while it is on the GPU (calculate_metrics_aligned_device), metrics="host" the downloaded one with the
+    float64 numpy statement (calculate_metrics_aligned).  model=None scores the inputs themselves (the "before" row; its
+    times are 0).  The row adds 'Rho' and 'Coverage' and their standard deviations (COLUMNS_ALIGNED).  A frame whose
+    alignment failed (flat frames, no overlap) goes to 'Failed' like any other failed frame."""
+    _check_metrics(metrics)
+    if model_name is None:
+        model_name = "Input" if model is None else type(model).__name__
+    scores, time_list, failed = [], [], []
+    for input_img, target_img, name in loader:
+        with _frame_guard(failed, name, skip_failed, model_name, dataset):
+            if model is None:
+                pred, ms, pred_dev = input_img, 0.0, None
+            else:
+                pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
+                                                           need_degradation=need_degradation, noise_level=noise_level)
+            if metrics == "device":
+                if not isinstance(target_img, np.ndarray) or target_img.dtype not in (np.uint8, np.uint16):
+                    raise ValueError("metrics='device' needs uint8 or uint16 target frames")
+                if pred_dev is None:
+                    pred_dev = to_device(pred, device)
+                m = calculate_metrics_aligned_device(pred_dev, to_device(target_img, pred_dev.device), iterations)
+            else:
+                m = calculate_metrics_aligned(pred, target_img, iterations)
+            if not m.ok:
+                raise ValueError(f"the alignment failed (rho {m.rho}, coverage {m.coverage})")
+            scores.append(m)
+            time_list.append(ms)
+    row = aggregate([m.psnr for m in scores], [m.ssim for m in scores], time_list, task=task, subtask=subtask,
+                    dataset=dataset, sigma=sigma, model_name=model_name,
+                    params=0 if model is None else get_model_total_parameters(model))
+    for col, field in (('Rho', 'rho'), ('Coverage', 'coverage')):
+        vals = [getattr(m, field) for m in scores] or [float('nan')]
+        row[col], row['Std_' + col] = np.mean(vals), np.std(vals)
     row['Failed'] = failed
     return row
 

@@ -3,7 +3,7 @@ patch-config lookup and the tiled-patch inference calls.  The device tile
 pipeline they run on (pipeline.py: tile plan, graph cache, extract / forward /
 blend), the metrics (metrics.py), the super-resolution resize (resize.py), NIQE
 (niqe.py), LPIPS (perceptual.py), the YUV 4:2:0 conversions (yuv.py), the frame
-stream (stream.py) and the noise estimator (noise.py) are re-exported: every name this module had is
+stream (stream.py), the noise estimator (noise.py) and the aligned scores (align.py) are re-exported: every name this module had is
 still reachable through it.  The bank of per-sigma checkpoints and the call that
 routes a frame to the one for its estimated noise level live here.
 """
@@ -18,6 +18,8 @@ import torch
 from torch.nn import Module
 
 from . import deblurganv2, dncnn, mair, rednet, restormer, yuv
+from .align import (AlignedMetrics, align_to_target, align_to_target_device, calculate_metrics_aligned,  # noqa: F401
+                    calculate_metrics_aligned_device, ecc_homography_device)
 from .frames import plane_slots, to_device, to_host
 from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_metrics_basicsr_device,  # noqa: F401
                       calculate_metrics_device, calculate_metrics_f32_device, frame_metrics_basicsr_device,

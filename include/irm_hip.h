@@ -553,6 +553,10 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
 /* ---- YUV 4:2:0 / 4:2:2 / 4:4:4 frames at 8, 10 and 12 bit: irm_yuv_to_rgb_f32, irm_rgb_f32_to_yuv, irm_yuv_metrics */
 #include "irm_hip_video.h"
 
+/* ---- aligned scoring of beam-splitter pairs (ECC homography, masked PSNR / SSIM): irm_align_prepare, irm_ecc_iterate,
+ * irm_aligned_metrics */
+#include "irm_hip_align.h"
+
 #ifdef __cplusplus
 }
 #endif
