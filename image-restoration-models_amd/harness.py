@@ -1,15 +1,19 @@
-"""Benchmark-harness aggregate of the reference (scripts/tests.py:389-424): per image PSNR, SSIM and
-inference time, per (dataset, model) their mean and standard deviation, one CSV row per combination with
-the reference's column names.  Dataset file IO is out of scope - `loader` is any iterable yielding
-(input_uint8_hwc, target_uint8_hwc, name), e.g. `synthetic_loader`.  For a super-resolving model (`model.upscale`
-s > 1) the pairs are (low-resolution input, s x larger target); `sr_pairs` / `evaluate_sr` make them from HR frames
-by the super-resolution protocol (MATLAB bicubic LR, border crop, Y-channel metrics).  Where no target exists
-(real captures), `evaluate_blind` scores the frames by NIQE instead; `evaluate_perceptual` adds LPIPS, the perceptual
-distance to the target, to the row of `evaluate`.  `evaluate_stream` is `evaluate` over the frame
-stream (stream.py): several frames per forward, the copies under the forwards.  `evaluate_aligned` scores beam-splitter pairs (RealBlur) as published: after an ECC
-alignment, under the mask of the warp (align.py).  `evaluate_yuv` takes YUV plane
-tuples (4:2:0, 4:2:2, 4:4:4; `y4m_pairs` reads them from two YUV4MPEG2 files) and reports PSNR / SSIM per component.  `evaluate_auto_sigma` takes a bank of per-sigma checkpoints and runs, per
-frame, the one trained for the noise level estimated on the GPU."""
+"""Benchmark-harness aggregate of the reference (scripts/tests.py:389-424): per image PSNR, SSIM and inference time,
+per (dataset, model) their mean and standard deviation, one CSV row per combination with the reference's column names
+(`aggregate`, `save_results`).  Dataset file IO is out of scope: `loader` is any iterable of (input, target, name),
+e.g. `synthetic_loader`.  One function per protocol, each returning one row:
+
+  evaluate             the reference's row: PSNR / SSIM of the prediction against the target
+  evaluate_auto_sigma  the same over a bank of per-sigma checkpoints: per frame, the one for the sigma estimated there
+  evaluate_stream      the same over the frame stream (stream.py): several frames per forward, copies under the forwards
+  evaluate_sr          super-resolution: MATLAB bicubic LR from HR frames (`sr_pairs`), border crop, Y-channel metrics
+  evaluate_yuv         YUV plane tuples (4:2:0, 4:2:2, 4:4:4; `y4m_pairs` reads Y4M files): PSNR / SSIM per component
+  evaluate_blind       no target (real captures): NIQE in place of PSNR / SSIM
+  evaluate_perceptual  `evaluate` plus LPIPS, the perceptual distance to the target
+  evaluate_aligned     beam-splitter pairs (RealBlur) as published: after an ECC alignment, under the warp's mask
+
+A protocol is its per-frame function, which returns one record (psnr, ssim, ms, extra values..); `_sweep` runs it over
+the loader under `_frame_guard`, `_row` makes the row from the records."""
 from __future__ import annotations
 
 import contextlib
@@ -27,22 +31,36 @@ from .metrics import (calculate_metrics, calculate_metrics_basicsr, calculate_me
 from .niqe import calculate_niqe, calculate_niqe_device
 from .perceptual import calculate_lpips, calculate_lpips_device
 from .resize import imresize_device, mod_crop
-from .utils import (SigmaBank, _get_model_prediction, _run_model_inference_auto, _run_model_inference_yuv,
-                    get_model_total_parameters)
+from .utils import (SigmaBank, _get_model_prediction, _is_patch_config, _run_model_inference_auto,
+                    _run_model_inference_yuv, get_model_total_parameters)
 
 COLUMNS = ['Task', 'Type', 'Dataset', 'Sigma', 'Model', 'Model_Params', 'PSNR', 'SSIM', 'Std_PSNR', 'Std_SSIM',
            'Avg_Time_ms', 'Std_Time_ms']
+
+
+def _columns(extras, *more) -> list:
+    """The columns of a protocol whose rows add `extras`: the reference's, the extras, their Std_ forms, then `more`."""
+    return COLUMNS + list(extras) + ['Std_' + col for col in extras] + list(more)
+
+
+# Per protocol, the per-frame values a record holds after (psnr, ssim, ms), in this order; `_row` turns each into a mean
+# and a Std_ column, and the COLUMNS_ list that `save_results` takes is made from the same tuple.
+EXTRA_BLIND = ('NIQE',)
+EXTRA_AUTO = ('Sigma_Est',)
+EXTRA_PERCEPTUAL = ('LPIPS',)
+EXTRA_ALIGNED = ('Rho', 'Coverage')
+EXTRA_YUV = ('PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V')
 #: the columns of an `evaluate_blind` row: the reference's plus the no-reference score
-COLUMNS_BLIND = COLUMNS + ['NIQE', 'Std_NIQE']
-#: the columns of an `evaluate_yuv` row: the reference's, PSNR / SSIM being the luma values, plus the chroma planes'
+COLUMNS_BLIND = _columns(EXTRA_BLIND)
 #: the columns of an `evaluate_auto_sigma` row: the reference's plus the estimated and the used noise levels
-COLUMNS_AUTO = COLUMNS + ['Sigma_Est', 'Std_Sigma_Est', 'Sigma_Used']
+COLUMNS_AUTO = _columns(EXTRA_AUTO, 'Sigma_Used')
 #: the columns of an `evaluate_perceptual` row: the reference's plus the perceptual distance to the target
-COLUMNS_PERCEPTUAL = COLUMNS + ['LPIPS', 'Std_LPIPS']
+COLUMNS_PERCEPTUAL = _columns(EXTRA_PERCEPTUAL)
 #: the columns of an `evaluate_aligned` row: the reference's, PSNR / SSIM being the aligned ones, plus the correlation
 #: the alignment reached and the share of the frame under the warp's mask
-COLUMNS_ALIGNED = COLUMNS + ['Rho', 'Coverage', 'Std_Rho', 'Std_Coverage']
-COLUMNS_YUV = COLUMNS + ['PSNR_U', 'PSNR_V', 'SSIM_U', 'SSIM_V', 'Std_PSNR_U', 'Std_PSNR_V', 'Std_SSIM_U', 'Std_SSIM_V']
+COLUMNS_ALIGNED = _columns(EXTRA_ALIGNED)
+#: the columns of an `evaluate_yuv` row: the reference's, PSNR / SSIM being the luma values, plus the chroma planes'
+COLUMNS_YUV = _columns(EXTRA_YUV)
 
 
 def synthetic_loader(n_images: int, h: int = 720, w: int = 1280, c: int = 3, seed_base: int = 1000, blur: int = 15):
@@ -70,11 +88,93 @@ def _frame_guard(failed: list, name, skip_failed: bool, model_name, dataset):
         print(f"[harness] {model_name} on {dataset}: frame {name} failed ({type(e).__name__}: {e}); skipped")
 
 
+def _triples(loader):
+    """The (input, target, name) items of a loader.  They are unpacked here, outside the guard: an item of another
+    length is the loader's error, not a frame's, and propagates."""
+    for input_img, target_img, name in loader:
+        yield input_img, target_img, name
+
+
+def _sweep(items, frame, skip_failed: bool, model_name, dataset) -> tuple:
+    """Run `frame(*item[:-1])` for every item under `_frame_guard`, item[-1] being the frame's name: returns (records,
+    failed).  `frame` returns one record - a tuple (psnr, ssim, ms, extra values..) of numbers, never an array or a
+    tensor - and returns it last, so a frame adds either a complete record or an entry of `failed`, never a part."""
+    records, failed = [], []
+    for item in items:
+        *args, name = item
+        with _frame_guard(failed, name, skip_failed, model_name, dataset):
+            records.append(frame(*args))
+    return records, failed
+
+
+def _row(records, failed, extras=(), also=None, **labels) -> dict:
+    """The row of a sweep: `aggregate` over the records, then mean and Std_ of every column of `extras` (the record
+    values after psnr, ssim, ms, in that order; NaN for no record), then the keys of `also`, then 'Failed'."""
+    def column(i):
+        return [r[i] for r in records]
+    row = aggregate(column(0), column(1), column(2), **labels)
+    for i, col in enumerate(extras, 3):
+        vals = column(i) or [float('nan')]
+        row[col], row['Std_' + col] = np.mean(vals), np.std(vals)
+    row.update(also or {})
+    row['Failed'] = failed
+    return row
+
+
+def _predict(model, input_img, device, patch_config, need_degradation, noise_level) -> tuple:
+    """(prediction, ms, device output or None) of one frame; model=None is the "before" row: the input itself, 0 ms."""
+    if model is None:
+        return input_img, 0.0, None
+    return _get_model_prediction(model, input_img, device, **patch_config, need_degradation=need_degradation,
+                                 noise_level=noise_level)
+
+
+def _name_of(model, model_name, baseline="Input"):
+    """The row's model name where the caller gave none: the class, or `baseline` for model=None."""
+    if model_name is not None:
+        return model_name
+    return baseline if model is None else type(model).__name__
+
+
+def _params_of(model) -> int:
+    return 0 if model is None else get_model_total_parameters(model)
+
+
+def _on_device(pred, pred_dev, device):
+    """The prediction on the GPU: the pipeline's output tensor, or `pred` uploaded where the host tile loop made it."""
+    return to_device(pred, device) if pred_dev is None else pred_dev
+
+
 def _host_metrics(pred, target_img, with_ssim: bool) -> tuple:
     """(psnr, ssim) of a downloaded prediction: calculate_metrics, or the PSNR alone and NaN."""
     if with_ssim:
         return calculate_metrics(pred, target_img)
     return psnr(target_img, pred, 255 if pred.dtype == np.uint8 else 65535), float('nan')
+
+
+def _is_f32(a, shape=None) -> bool:
+    return isinstance(a, np.ndarray) and a.dtype == np.float32 and (shape is None or a.shape == shape)
+
+
+def _device_metrics(pred, pred_dev, target_img, device, input_img=None):
+    """(psnr, ssim) of one frame on the GPU: pred_dev is the pipeline's output tensor (None after the host tile loop:
+    the prediction is uploaded), the target goes up as the input did (uint16 as its int16 bit pattern).  A float32
+    prediction of a float32 input with a float32 target of its shape is scored by the float kernel."""
+    if _is_f32(input_img) and _is_f32(pred) and _is_f32(target_img, pred.shape):
+        pred_dev = _on_device(pred, pred_dev, device)
+        return calculate_metrics_f32_device(pred_dev, to_device(target_img, pred_dev.device))
+    if not isinstance(target_img, np.ndarray) or target_img.dtype not in (np.uint8, np.uint16):
+        raise ValueError("metrics='device' needs uint8 or uint16 target frames")
+    pred_dev = _on_device(pred, pred_dev, device)
+    return calculate_metrics_device(pred_dev, to_device(target_img, pred_dev.device))
+
+
+def _psnr_ssim(pred, pred_dev, target_img, device, input_img, metrics, with_ssim: bool) -> tuple:
+    """(psnr, ssim) as `evaluate` scores: on the GPU or of the downloaded prediction; NaN for SSIM without with_ssim."""
+    if metrics == "device":
+        p, s = _device_metrics(pred, pred_dev, target_img, device, input_img)
+        return p, s if with_ssim else float('nan')
+    return _host_metrics(pred, target_img, with_ssim)
 
 
 def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: str, dataset: str, model_name: str,
@@ -96,24 +196,14 @@ def evaluate(model, loader, device, patch_config: dict, *, task: str, subtask: s
     the prediction and the timed work (input upload through output download) are the same, and the metrics are not
     timed."""
     _check_metrics(metrics)
-    psnr_list, ssim_list, time_list, failed = [], [], [], []
-    for input_img, target_img, name in loader:
-        with _frame_guard(failed, name, skip_failed, model_name, dataset):
-            pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
-                                                       need_degradation=need_degradation, noise_level=noise_level)
-            if metrics == "device":
-                p, s = _device_metrics(pred, pred_dev, target_img, device, input_img)
-                if not with_ssim:
-                    s = float('nan')
-            else:
-                p, s = _host_metrics(pred, target_img, with_ssim)
-            psnr_list.append(p)
-            ssim_list.append(s)
-            time_list.append(ms)
-    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
-                    model_name=model_name, params=get_model_total_parameters(model))
-    row['Failed'] = failed
-    return row
+
+    def frame(input_img, target_img):
+        pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
+                                                   need_degradation=need_degradation, noise_level=noise_level)
+        return _psnr_ssim(pred, pred_dev, target_img, device, input_img, metrics, with_ssim) + (ms,)
+    records, failed = _sweep(_triples(loader), frame, skip_failed, model_name, dataset)
+    return _row(records, failed, task=task, subtask=subtask, dataset=dataset, sigma=sigma, model_name=model_name,
+                params=get_model_total_parameters(model))
 
 
 def evaluate_auto_sigma(bank, loader, device, patch_config: dict, *, task: str, subtask: str, dataset: str,
@@ -126,32 +216,17 @@ def evaluate_auto_sigma(bank, loader, device, patch_config: dict, *, task: str, 
     _check_metrics(metrics)
     if not isinstance(bank, SigmaBank):
         raise ValueError("evaluate_auto_sigma: bank is a SigmaBank (utils.get_model_bank)")
-    if not isinstance(patch_config, dict) or set(patch_config) != {"patch_size", "patch_overlap"}:
+    if not _is_patch_config(patch_config):
         raise ValueError("evaluate_auto_sigma: patch_config is {'patch_size': .., 'patch_overlap': ..}")
-    psnr_list, ssim_list, time_list, est_list, failed = [], [], [], [], []
-    used = {}
-    for input_img, target_img, name in loader:
-        with _frame_guard(failed, name, skip_failed, model_name, dataset):
-            pred, ms, est, level, pred_dev = _run_model_inference_auto(bank, input_img, device, **patch_config)
-            if metrics == "device":
-                p, s = _device_metrics(pred, pred_dev, target_img, device, input_img)
-                if not with_ssim:
-                    s = float('nan')
-            else:
-                p, s = _host_metrics(pred, target_img, with_ssim)
-            psnr_list.append(p)
-            ssim_list.append(s)
-            time_list.append(ms)
-            est_list.append(est)
-            used[level] = used.get(level, 0) + 1
-    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma='auto',
-                    model_name=model_name, params=get_model_total_parameters(bank.models[bank.levels[0]]))
-    if not est_list:
-        est_list = [float('nan')]
-    row['Sigma_Est'], row['Std_Sigma_Est'] = np.mean(est_list), np.std(est_list)
-    row['Sigma_Used'] = {level: used[level] for level in bank.levels if level in used}
-    row['Failed'] = failed
-    return row
+
+    def frame(input_img, target_img):
+        pred, ms, est, level, pred_dev = _run_model_inference_auto(bank, input_img, device, **patch_config)
+        return _psnr_ssim(pred, pred_dev, target_img, device, input_img, metrics, with_ssim) + (ms, est, level)
+    records, failed = _sweep(_triples(loader), frame, skip_failed, model_name, dataset)
+    levels = [r[4] for r in records]
+    used = {level: levels.count(level) for level in bank.levels if level in levels}
+    return _row(records, failed, EXTRA_AUTO, {'Sigma_Used': used}, task=task, subtask=subtask, dataset=dataset,
+                sigma='auto', model_name=model_name, params=get_model_total_parameters(bank.models[bank.levels[0]]))
 
 
 def evaluate_stream(model, loader, device, patch_config: dict, *, task: str, subtask: str, dataset: str,
@@ -173,7 +248,7 @@ def evaluate_stream(model, loader, device, patch_config: dict, *, task: str, sub
     front = stream._Front(model, patch_config["patch_size"], patch_config["patch_overlap"], need_degradation,
                           noise_level, "same", False, triples=True, with_targets=metrics == "device")
     items = ((inp, tgt, tgt) for inp, tgt, _ in loader)
-    psnr_list, ssim_list, time_list = [], [], []
+    records = []
     frames = stream._stream(front, items, device, k)
     try:
         for pred, ms, target_img, score in frames:
@@ -181,34 +256,11 @@ def evaluate_stream(model, loader, device, patch_config: dict, *, task: str, sub
                 p, s = stream.score_psnr(score[0], pred.shape, pred.dtype), score[1] if with_ssim else float('nan')
             else:
                 p, s = _host_metrics(pred, target_img, with_ssim)
-            psnr_list.append(p)
-            ssim_list.append(s)
-            time_list.append(ms)
+            records.append((p, s, ms))
     finally:
         frames.close()
-    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
-                    model_name=model_name, params=get_model_total_parameters(model))
-    row['Failed'] = []
-    return row
-
-
-def _is_f32(a, shape=None) -> bool:
-    return isinstance(a, np.ndarray) and a.dtype == np.float32 and (shape is None or a.shape == shape)
-
-
-def _device_metrics(pred, pred_dev, target_img, device, input_img=None):
-    """(psnr, ssim) of one frame on the GPU: pred_dev is the pipeline's output tensor (None after the host tile loop:
-    the prediction is uploaded), the target goes up as the input did (uint16 as its int16 bit pattern).  A float32
-    prediction of a float32 input with a float32 target of its shape is scored by the float kernel."""
-    if _is_f32(input_img) and _is_f32(pred) and _is_f32(target_img, pred.shape):
-        if pred_dev is None:
-            pred_dev = to_device(pred, device)
-        return calculate_metrics_f32_device(pred_dev, to_device(target_img, pred_dev.device))
-    if not isinstance(target_img, np.ndarray) or target_img.dtype not in (np.uint8, np.uint16):
-        raise ValueError("metrics='device' needs uint8 or uint16 target frames")
-    if pred_dev is None:
-        pred_dev = to_device(pred, device)
-    return calculate_metrics_device(pred_dev, to_device(target_img, pred_dev.device))
+    return _row(records, [], task=task, subtask=subtask, dataset=dataset, sigma=sigma, model_name=model_name,
+                params=get_model_total_parameters(model))
 
 
 def sr_pairs(hr_loader, scale: int, device):
@@ -249,34 +301,26 @@ def evaluate_sr(model, hr_loader, device, patch_config: dict, scale: int, *, tas
         raise ValueError(f"crop_border must be a non-negative integer, not {crop_border!r}")
     if channel_order not in ("rgb", "bgr"):
         raise ValueError(f"channel_order must be 'rgb' or 'bgr', not {channel_order!r}")
-    if model_name is None:
-        model_name = "Bicubic" if model is None else type(model).__name__
-    psnr_list, ssim_list, time_list, failed = [], [], [], []
-    for lr, hr, name in sr_pairs(hr_loader, scale, device):
-        with _frame_guard(failed, name, skip_failed, model_name, dataset):
-            if model is None:
-                start = time.time()
-                pred_dev = imresize_device(to_device(lr, device), scale, out="same")
-                pred = to_host(pred_dev)
-                ms = (time.time() - start) * 1000
-            else:
-                pred, ms, pred_dev = _get_model_prediction(model, lr, device, **patch_config)
-            if pred.shape != hr.shape:
-                raise ValueError(f"prediction {pred.shape} for an HR frame {hr.shape}")
-            if metrics == "device":
-                if pred_dev is None:
-                    pred_dev = to_device(pred, device)
-                p, s = calculate_metrics_basicsr_device(pred_dev, to_device(hr, pred_dev.device), crop, test_y_channel,
-                                                        channel_order)
-            else:
-                p, s = calculate_metrics_basicsr(pred, hr, crop, test_y_channel, channel_order)
-            psnr_list.append(p)
-            ssim_list.append(s)
-            time_list.append(ms)
-    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask or f"x{scale}", dataset=dataset, sigma=sigma,
-                    model_name=model_name, params=0 if model is None else get_model_total_parameters(model))
-    row['Failed'] = failed
-    return row
+    model_name = _name_of(model, model_name, "Bicubic")
+
+    def frame(lr, hr):
+        if model is None:
+            start = time.time()
+            pred_dev = imresize_device(to_device(lr, device), scale, out="same")
+            pred = to_host(pred_dev)
+            ms = (time.time() - start) * 1000
+        else:
+            pred, ms, pred_dev = _get_model_prediction(model, lr, device, **patch_config)
+        if pred.shape != hr.shape:
+            raise ValueError(f"prediction {pred.shape} for an HR frame {hr.shape}")
+        if metrics == "device":
+            pred_dev = _on_device(pred, pred_dev, device)
+            return calculate_metrics_basicsr_device(pred_dev, to_device(hr, pred_dev.device), crop, test_y_channel,
+                                                    channel_order) + (ms,)
+        return calculate_metrics_basicsr(pred, hr, crop, test_y_channel, channel_order) + (ms,)
+    records, failed = _sweep(sr_pairs(hr_loader, scale, device), frame, skip_failed, model_name, dataset)
+    return _row(records, failed, task=task, subtask=subtask or f"x{scale}", dataset=dataset, sigma=sigma,
+                model_name=model_name, params=_params_of(model))
 
 
 class y4m_pairs:
@@ -318,32 +362,25 @@ def evaluate_yuv(model, loader, device, patch_config: dict, *, fmt, matrix="bt70
     chroma columns are NaN.  Failed frames are handled as in `evaluate`."""
     _check_metrics(metrics)
     yuv._check_layout_options(fmt, matrix, siting)
-    if not isinstance(patch_config, dict) or set(patch_config) != {"patch_size", "patch_overlap"}:
+    if not _is_patch_config(patch_config):
         raise ValueError("evaluate_yuv: patch_config is {'patch_size': .., 'patch_overlap': ..}")
-    scores, time_list, failed = [], [], []
-    for planes, target_planes, name in loader:
-        with _frame_guard(failed, name, skip_failed, model_name, dataset):
-            pred, ms, pred_dev = _run_model_inference_yuv(
-                model, planes, device, fmt=fmt, matrix=matrix, full_range=full_range, siting=siting, luma_only=luma_only,
-                need_degradation=need_degradation, noise_level=noise_level, **patch_config)
-            if metrics == "device":
-                if not isinstance(target_planes, (tuple, list)) or not all(isinstance(t, np.ndarray) for t in target_planes):
-                    raise ValueError("evaluate_yuv: the target planes are numpy arrays")
-                used = target_planes[:1] if luma_only else target_planes
-                target_dev = tuple(to_device(t, pred_dev[0].device) for t in used)
-                m = yuv.calculate_metrics_yuv_device(pred_dev, target_dev, fmt, luma_only)
-            else:
-                m = yuv.calculate_metrics_yuv(pred, target_planes, fmt, luma_only)
-            del pred_dev
-            scores.append(m)
-            time_list.append(ms)
-    row = aggregate([m.psnr_y for m in scores], [m.ssim_y for m in scores], time_list, task=task, subtask=subtask,
-                    dataset=dataset, sigma=sigma, model_name=model_name, params=get_model_total_parameters(model))
-    for col, field in (('PSNR_U', 'psnr_u'), ('PSNR_V', 'psnr_v'), ('SSIM_U', 'ssim_u'), ('SSIM_V', 'ssim_v')):
-        vals = [getattr(m, field) for m in scores] or [float('nan')]
-        row[col], row['Std_' + col] = np.mean(vals), np.std(vals)
-    row['Failed'] = failed
-    return row
+
+    def frame(planes, target_planes):                           # the result planes on the device live no longer than it
+        pred, ms, pred_dev = _run_model_inference_yuv(
+            model, planes, device, fmt=fmt, matrix=matrix, full_range=full_range, siting=siting, luma_only=luma_only,
+            need_degradation=need_degradation, noise_level=noise_level, **patch_config)
+        if metrics == "device":
+            if not (isinstance(target_planes, (tuple, list)) and all(isinstance(t, np.ndarray) for t in target_planes)):
+                raise ValueError("evaluate_yuv: the target planes are numpy arrays")
+            used = target_planes[:1] if luma_only else target_planes
+            target_dev = tuple(to_device(t, pred_dev[0].device) for t in used)
+            m = yuv.calculate_metrics_yuv_device(pred_dev, target_dev, fmt, luma_only)
+        else:
+            m = yuv.calculate_metrics_yuv(pred, target_planes, fmt, luma_only)
+        return m.psnr_y, m.ssim_y, ms, m.psnr_u, m.psnr_v, m.ssim_u, m.ssim_v
+    records, failed = _sweep(_triples(loader), frame, skip_failed, model_name, dataset)
+    return _row(records, failed, EXTRA_YUV, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
+                model_name=model_name, params=get_model_total_parameters(model))
 
 
 def evaluate_blind(model, loader, device, patch_config: dict, *, niqe_params, crop_border: int = 0, metrics="device",
@@ -359,35 +396,21 @@ def evaluate_blind(model, loader, device, patch_config: dict, *, niqe_params, cr
     "before" row; its times are 0).  The row has the reference's columns - PSNR and SSIM are NaN - plus 'NIQE' and
     'Std_NIQE' (COLUMNS_BLIND).  Failed frames are handled as in `evaluate`."""
     _check_metrics(metrics)
-    if model_name is None:
-        model_name = "Input" if model is None else type(model).__name__
-    niqe_list, time_list, failed = [], [], []
-    for item in loader:
-        input_img, name = item[0], item[-1]
-        with _frame_guard(failed, name, skip_failed, model_name, dataset):
-            if model is None:
-                pred, ms, pred_dev = input_img, 0.0, None
-            else:
-                pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
-                                                           need_degradation=need_degradation, noise_level=noise_level)
-            if metrics == "device":
-                if not isinstance(pred, np.ndarray) or pred.dtype not in (np.uint8, np.uint16):
-                    raise ValueError("metrics='device' needs uint8 or uint16 frames")
-                if pred_dev is None:
-                    pred_dev = to_device(pred, device)
-                q = calculate_niqe_device(pred_dev, crop_border, niqe_params, channel_order=channel_order)
-            else:
-                q = calculate_niqe(pred, crop_border, niqe_params, channel_order=channel_order)
-            niqe_list.append(q)
-            time_list.append(ms)
-    nan = [float('nan')] * len(niqe_list)
-    row = aggregate(nan, nan, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
-                    model_name=model_name, params=0 if model is None else get_model_total_parameters(model))
-    if not niqe_list:
-        niqe_list = [float('nan')]
-    row['NIQE'], row['Std_NIQE'] = np.mean(niqe_list), np.std(niqe_list)
-    row['Failed'] = failed
-    return row
+    model_name = _name_of(model, model_name)
+
+    def frame(input_img, *_target):
+        pred, ms, pred_dev = _predict(model, input_img, device, patch_config, need_degradation, noise_level)
+        if metrics == "device":
+            if not isinstance(pred, np.ndarray) or pred.dtype not in (np.uint8, np.uint16):
+                raise ValueError("metrics='device' needs uint8 or uint16 frames")
+            q = calculate_niqe_device(_on_device(pred, pred_dev, device), crop_border, niqe_params,
+                                      channel_order=channel_order)
+        else:
+            q = calculate_niqe(pred, crop_border, niqe_params, channel_order=channel_order)
+        return float('nan'), float('nan'), ms, q
+    records, failed = _sweep(loader, frame, skip_failed, model_name, dataset)
+    return _row(records, failed, EXTRA_BLIND, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
+                model_name=model_name, params=_params_of(model))
 
 
 def evaluate_perceptual(model, loader, device, patch_config: dict, *, lpips_params, metrics="device",
@@ -403,37 +426,21 @@ def evaluate_perceptual(model, loader, device, patch_config: dict, *, lpips_para
     row has the reference's columns plus 'LPIPS' and 'Std_LPIPS' (COLUMNS_PERCEPTUAL).  Failed frames are handled as in
     `evaluate`."""
     _check_metrics(metrics)
-    if model_name is None:
-        model_name = "Input" if model is None else type(model).__name__
-    psnr_list, ssim_list, lpips_list, time_list, failed = [], [], [], [], []
-    for input_img, target_img, name in loader:
-        with _frame_guard(failed, name, skip_failed, model_name, dataset):
-            if model is None:
-                pred, ms, pred_dev = input_img, 0.0, None
-            else:
-                pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
-                                                           need_degradation=need_degradation, noise_level=noise_level)
-            if metrics == "device":
-                if pred_dev is None:
-                    pred_dev = to_device(pred, device)
-                p, s = _device_metrics(pred, pred_dev, target_img, device, input_img)
-                if not with_ssim:
-                    s = float('nan')
-                q = calculate_lpips_device(pred_dev, to_device(target_img, pred_dev.device), lpips_params)
-            else:
-                p, s = _host_metrics(pred, target_img, with_ssim)
-                q = calculate_lpips(pred, target_img, lpips_params)
-            psnr_list.append(p)
-            ssim_list.append(s)
-            lpips_list.append(q)
-            time_list.append(ms)
-    row = aggregate(psnr_list, ssim_list, time_list, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
-                    model_name=model_name, params=0 if model is None else get_model_total_parameters(model))
-    if not lpips_list:
-        lpips_list = [float('nan')]
-    row['LPIPS'], row['Std_LPIPS'] = np.mean(lpips_list), np.std(lpips_list)
-    row['Failed'] = failed
-    return row
+    model_name = _name_of(model, model_name)
+
+    def frame(input_img, target_img):
+        pred, ms, pred_dev = _predict(model, input_img, device, patch_config, need_degradation, noise_level)
+        if metrics == "device":
+            pred_dev = _on_device(pred, pred_dev, device)
+        p, s = _psnr_ssim(pred, pred_dev, target_img, device, input_img, metrics, with_ssim)
+        if metrics == "device":
+            q = calculate_lpips_device(pred_dev, to_device(target_img, pred_dev.device), lpips_params)
+        else:
+            q = calculate_lpips(pred, target_img, lpips_params)
+        return p, s, ms, q
+    records, failed = _sweep(_triples(loader), frame, skip_failed, model_name, dataset)
+    return _row(records, failed, EXTRA_PERCEPTUAL, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
+                model_name=model_name, params=_params_of(model))
 
 
 def evaluate_aligned(model, loader, device, patch_config: dict, *, iterations: int = 100, metrics="device",
@@ -449,36 +456,23 @@ def evaluate_aligned(model, loader, device, patch_config: dict, *, iterations: i
     times are 0).  The row adds 'Rho' and 'Coverage' and their standard deviations (COLUMNS_ALIGNED).  A frame whose
     alignment failed (flat frames, no overlap) goes to 'Failed' like any other failed frame."""
     _check_metrics(metrics)
-    if model_name is None:
-        model_name = "Input" if model is None else type(model).__name__
-    scores, time_list, failed = [], [], []
-    for input_img, target_img, name in loader:
-        with _frame_guard(failed, name, skip_failed, model_name, dataset):
-            if model is None:
-                pred, ms, pred_dev = input_img, 0.0, None
-            else:
-                pred, ms, pred_dev = _get_model_prediction(model, input_img, device, **patch_config,
-                                                           need_degradation=need_degradation, noise_level=noise_level)
-            if metrics == "device":
-                if not isinstance(target_img, np.ndarray) or target_img.dtype not in (np.uint8, np.uint16):
-                    raise ValueError("metrics='device' needs uint8 or uint16 target frames")
-                if pred_dev is None:
-                    pred_dev = to_device(pred, device)
-                m = calculate_metrics_aligned_device(pred_dev, to_device(target_img, pred_dev.device), iterations)
-            else:
-                m = calculate_metrics_aligned(pred, target_img, iterations)
-            if not m.ok:
-                raise ValueError(f"the alignment failed (rho {m.rho}, coverage {m.coverage})")
-            scores.append(m)
-            time_list.append(ms)
-    row = aggregate([m.psnr for m in scores], [m.ssim for m in scores], time_list, task=task, subtask=subtask,
-                    dataset=dataset, sigma=sigma, model_name=model_name,
-                    params=0 if model is None else get_model_total_parameters(model))
-    for col, field in (('Rho', 'rho'), ('Coverage', 'coverage')):
-        vals = [getattr(m, field) for m in scores] or [float('nan')]
-        row[col], row['Std_' + col] = np.mean(vals), np.std(vals)
-    row['Failed'] = failed
-    return row
+    model_name = _name_of(model, model_name)
+
+    def frame(input_img, target_img):
+        pred, ms, pred_dev = _predict(model, input_img, device, patch_config, need_degradation, noise_level)
+        if metrics == "device":
+            if not isinstance(target_img, np.ndarray) or target_img.dtype not in (np.uint8, np.uint16):
+                raise ValueError("metrics='device' needs uint8 or uint16 target frames")
+            pred_dev = _on_device(pred, pred_dev, device)
+            m = calculate_metrics_aligned_device(pred_dev, to_device(target_img, pred_dev.device), iterations)
+        else:
+            m = calculate_metrics_aligned(pred, target_img, iterations)
+        if not m.ok:
+            raise ValueError(f"the alignment failed (rho {m.rho}, coverage {m.coverage})")
+        return m.psnr, m.ssim, ms, m.rho, m.coverage
+    records, failed = _sweep(_triples(loader), frame, skip_failed, model_name, dataset)
+    return _row(records, failed, EXTRA_ALIGNED, task=task, subtask=subtask, dataset=dataset, sigma=sigma,
+                model_name=model_name, params=_params_of(model))
 
 
 def aggregate(psnr_list, ssim_list, time_list, *, task, subtask, dataset, sigma, model_name, params) -> dict:

@@ -101,6 +101,11 @@ def get_patch_config(task, subtask, model_name) -> dict | None:
     return config
 
 
+def _is_patch_config(cfg) -> bool:
+    """Whether cfg is {'patch_size': .., 'patch_overlap': ..}, the dict get_patch_config returns, and nothing else."""
+    return isinstance(cfg, dict) and set(cfg) == {"patch_size", "patch_overlap"}
+
+
 def _restormer_opt(name: str) -> str:
     return os.path.join(_PKG_DIR, 'restormer', 'options', name + '.yml')
 
@@ -362,7 +367,7 @@ def run_model_chain(stages, input_img: np.ndarray, device: torch.device, need_de
     if not stages:
         raise ValueError("run_model_chain: at least one stage")
     for m, cfg in stages:
-        if not callable(m) or set(cfg) != {"patch_size", "patch_overlap"}:
+        if not callable(m) or not _is_patch_config(cfg):
             raise ValueError("run_model_chain: a stage is (model, {'patch_size': .., 'patch_overlap': ..})")
     for m, _ in stages:
         refuse_deblurgan(m, "run_model_chain", "run it on its own with get_model_prediction")
