@@ -137,6 +137,13 @@ SIGNATURES_ALIGN = {
     "irm_aligned_metrics": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
 }
 
+#: resize to any size from per-axis tap tables, and the store rule on its own (resize_any.hip), mirrors
+#: include/irm_hip_resize.h one to one
+SIGNATURES_RESIZE = {
+    "irm_resize_taps": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "irm_unit_quantise": [_P, _P, _I, _L, _P],
+}
+
 _lib = None
 
 
@@ -158,7 +165,7 @@ def load():
         for name, argtypes in {**SIGNATURES, **SIGNATURES_HALF, **SIGNATURES_FRAMES, **SIGNATURES_GRAM,
                                **SIGNATURES_YUV, **SIGNATURES_INCEPTION, **SIGNATURES_METRICS,
                                **SIGNATURES_NOISE, **SIGNATURES_LPIPS, **SIGNATURES_VIDEO,
-                               **SIGNATURES_ALIGN}.items():
+                               **SIGNATURES_ALIGN, **SIGNATURES_RESIZE}.items():
             fn = getattr(lib, name)          # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = _I

@@ -18,10 +18,10 @@ def frame_shape(shape, what="imresize") -> tuple:
     raise ValueError(f"{what} takes HW or HWC frames with 1 or 3 channels, not shape {tuple(shape)}")
 
 
-def device_frames(frames, what: str, host: str, label: str | None = None) -> tuple:
+def device_frames(frames, what: str, host: str, label: str | None = None, float32: bool = False) -> tuple:
     """tensor | list of tensors of one shape | [K][H][W][C] stack -> (items, K, H, W, C, stacked): the checks that
     need no GPU; a 4-D tensor is always read as a stack.  `what` ("the device NIQE") and `host` (what to say about the
-    numpy twin) word the messages; `label` opens the two about an empty call."""
+    numpy twin) word the messages; `label` opens the two about an empty call; `float32`: float32 frames are taken too."""
     as_list = isinstance(frames, (list, tuple))
     items = list(frames) if as_list else [frames]
     if not items:
@@ -30,8 +30,8 @@ def device_frames(frames, what: str, host: str, label: str | None = None) -> tup
     for f in items:
         if not isinstance(f, torch.Tensor):
             raise ValueError(f"{what} takes torch tensors ({host})")
-        if f.dtype not in FRAME_DTYPES:
-            raise ValueError(f"{what} takes uint8 or uint16 frames, not {f.dtype}")
+        if f.dtype not in FRAME_DTYPES and not (float32 and f.dtype == torch.float32):
+            raise ValueError(f"{what} takes uint8{', uint16 or float32' if float32 else ' or uint16'} frames, not {f.dtype}")
         if f.shape != f0.shape or f.dtype != f0.dtype or f.device != f0.device:
             raise ValueError("the frames of one call must share shape, dtype and device")
     stacked = not as_list and f0.dim() == 4

@@ -37,7 +37,8 @@ from .pipeline import (_GRAPH_MAX_BYTES, _GRAPH_MAX_ENTRIES, _MINMAX_WS_FLOATS, 
                        _upscale, _value_kinds, _window_on, cuda_device, get_gaussian_weights, graphed_forward,
                        is_deblurgan, model_route, noise_field, refuse_deblurgan, tile_origins, tile_plan,
                        tiled_forward_device, tiled_forward_device_batch)
-from .resize import imresize_device, imresize_host, mod_crop, resize_table  # noqa: F401
+from .resize import (RESIZE_KERNELS, Resize, imresize_device, imresize_host, mod_crop, resize_device,  # noqa: F401
+                     resize_host, resize_plan, resize_table, resize_taps)
 from .y4m import read_y4m, write_y4m  # noqa: F401
 from .yuv import (YUV_FORMATS, YUV_LAYOUTS, YuvMetrics, calculate_metrics_yuv, calculate_metrics_yuv_device,  # noqa: F401
                   frame_metrics_yuv_device, rgb_to_yuv420_device, rgb_to_yuv420_host, rgb_to_yuv_device,
@@ -348,45 +349,73 @@ def run_model_chain(stages, input_img: np.ndarray, device: torch.device, need_de
     `stages` is a sequence of (model, patch_config) with patch_config = {'patch_size': .., 'patch_overlap': ..} as
     get_patch_config returns it.  Every stage is the device pipeline of run_model_inference with the hooks
     get_model_prediction picks for the model class (reflect pad to 8 for Restormer / MaIR); a DeblurGANv2 model
-    raises ValueError.  The frame is uploaded once and downloaded once.
+    raises ValueError.  A stage may also be a Resize(size=.. | scale=.., kernel, antialias): the frame is brought to
+    that size on the device (resize_device).  The frame is uploaded once and downloaded once.
 
     The reference has no chain; these semantics are this package's own:
       1. the first stage reads the input as run_model_inference does (uint8 / 255, uint16 / 65535); a float32 input is
          taken as in [0, 1] already (unit_range=True of tiled_forward_device: no division by its max);
       2. every frame between two stages is float32, clipped to [0, 1] and never rounded to 255 levels - the next model
          does not see a quantisation step as new noise - and stays on the device;
-      3. need_degradation / noise_level apply to the first stage only;
+      3. need_degradation / noise_level apply to the first stage only, which must then be a model;
       4. the last stage requantises to the input's dtype as run_model_inference does, or returns the float32 frame in
-         [0, 1] for a float32 input or with out="float32".
+         [0, 1] for a float32 input or with out="float32";
+      5. a Resize stage follows the same rules: as first stage it reads the uint8 / uint16 input directly; between two
+         stages it maps the float32 frame to a float32 frame clamped to [0, 1] (out="unit": the overshoot of bicubic and
+         Lanczos does not reach the next model, as a model stage's output is clipped); as last stage it requantises by
+         the resize rule - clamp, x 255 (65535), round half to even - or returns the clamped float32 frame.  It resizes
+         H first, then W, as basicsr's imresize does, not MATLAB's smaller-scale-first rule.  A chain of Resize stages
+         alone is allowed.
     Super-resolving stages enlarge the frame for the stages after them; a 6-channel first stage yields 3 channels.  A
-    one-stage chain on a uint8 / uint16 frame returns exactly what get_model_prediction returns."""
+    one-stage chain on a uint8 / uint16 frame returns exactly what get_model_prediction returns (a model) or what
+    resize_device returns (a Resize)."""
+    def pair(model, cfg):
+        return model, dict(cfg)
     try:
-        stages = [(m, dict(cfg)) for m, cfg in stages]
+        stages = [st if isinstance(st, Resize) else pair(*st) for st in stages]
     except (TypeError, ValueError):
-        raise ValueError("run_model_chain: stages is a sequence of (model, patch_config) pairs") from None
+        raise ValueError("run_model_chain: stages is a sequence of (model, patch_config) pairs or Resize stages") from None
     if not stages:
         raise ValueError("run_model_chain: at least one stage")
-    for m, cfg in stages:
+    models = [st for st in stages if not isinstance(st, Resize)]
+    for m, cfg in models:
         if not callable(m) or not _is_patch_config(cfg):
-            raise ValueError("run_model_chain: a stage is (model, {'patch_size': .., 'patch_overlap': ..})")
-    for m, _ in stages:
+            raise ValueError("run_model_chain: a stage is (model, {'patch_size': .., 'patch_overlap': ..}) or a Resize")
+    for m, _ in models:
         refuse_deblurgan(m, "run_model_chain", "run it on its own with get_model_prediction")
     if out not in ("same", "float32"):
         raise ValueError(f"out must be 'same' or 'float32', not {out!r}")
     if (not isinstance(input_img, np.ndarray) or input_img.ndim != 3
             or input_img.dtype not in (np.uint8, np.uint16, np.float32)):
         raise ValueError("run_model_chain: a uint8, uint16 or float32 [H, W, C] array")
-    routes = [model_route(m, need_degradation and i == 0, noise_level) for i, (m, _) in enumerate(stages)]
+    if need_degradation and isinstance(stages[0], Resize):
+        raise ValueError("run_model_chain: need_degradation applies to the first stage, which is a Resize")
+    routes = [None if isinstance(st, Resize) else model_route(st[0], need_degradation and i == 0, noise_level)
+              for i, st in enumerate(stages)]
+    h, w, c = input_img.shape
+    for st, r in zip(stages, routes):                   # the sizes along the chain: a Resize that cannot run raises here
+        if r is None:
+            if c not in (1, 3):
+                raise ValueError(f"run_model_chain: a Resize stage takes 1 or 3 channels, not {c}")
+            h, w = st.plan(h, w)
+        else:
+            h, w, c = r.s * h, r.s * w, min(3, c)
     dev = cuda_device(device, "run_model_chain")
     start_time = time.time()
     with torch.no_grad():
         frame = to_device(input_img, dev)
         last = len(stages) - 1
         final = "float32" if out == "float32" else str(input_img.dtype)      # the last stage requantises
-        for i, ((m, cfg), r) in enumerate(zip(stages, routes)):
+        for i, (st, r) in enumerate(zip(stages, routes)):
             kind = final if i == last else "float32"
-            frame, _ = tiled_forward_device(m, frame, cfg["patch_size"], cfg["patch_overlap"], r.pad8, r.sigma,
-                                            max_batch=r.max_batch, unit_range=True, out=kind)
+            if r is None:
+                as_is = kind != "float32" and frame.dtype != torch.float32    # an integer frame keeps its type
+                frame = resize_device(frame, st.size, st.scale, st.kernel, st.antialias,
+                                      out="unit" if kind == "float32" else "same" if as_is else kind)
+            else:
+                m, cfg = st
+                frame, _ = tiled_forward_device(m, frame, cfg["patch_size"], cfg["patch_overlap"], r.pad8, r.sigma,
+                                                max_batch=r.max_batch, unit_range=True, out=kind)
         output_img = to_host(frame)
     return output_img, (time.time() - start_time) * 1000
 

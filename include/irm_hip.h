@@ -557,6 +557,9 @@ int irm_losh_combine_f32(float* ysum, const float* gw, const float* gb, float* g
  * irm_aligned_metrics */
 #include "irm_hip_align.h"
 
+/* ---- resize to any size from per-axis tap tables (bicubic, Lanczos, bilinear): irm_resize_taps, irm_unit_quantise */
+#include "irm_hip_resize.h"
+
 #ifdef __cplusplus
 }
 #endif
