@@ -1,11 +1,11 @@
 // PSNR / SSIM of the two kinds of frame that never pass through 255 RGB levels (include/irm_hip_metrics.h):
 //   irm_frame_metrics_f32   K float32 frames [H][W][C] against their targets: fp64 squared error and SSIM;
-//   irm_yuv420_metrics      the planes of one YUV 4:2:0 frame (I420, NV12, P010) against the target's, per component:
-//                           exact integer squared error and SSIM of Y, U and V;
-//   irm_yuv_metrics         the same for 4:2:0, 4:2:2 and 4:4:4 planes at 8, 10 and 12 bit (include/irm_hip_video.h).
+//   irm_yuv_metrics         the planes of one YUV frame (4:2:0, 4:2:2 or 4:4:4 at 8, 10 or 12 bit; include/irm_hip_video.h)
+//                           against the target's, per component: exact integer squared error and SSIM of Y, U and V;
+//   irm_yuv420_metrics      the 4:2:0 entry for I420, NV12 and P010: a depth check and a call of irm_yuv_metrics.
 // The SSIM is that of metrics.hip (skimage's defaults: 7x7 uniform window, K1 = .01, K2 = .03, sample covariance 49/48,
 // mean over the interior), and so are the tile geometry (SsimTile), the workspace slots and the fixed-order sums of
-// irm_frame.h.  One kernel template serves both entries; what differs is a policy (Src) that names the plane pair a
+// irm_frame.h.  One kernel template serves all entries; what differs is a policy (Src) that names the plane pair a
 // workgroup scores, the stored type and the type of the window moments:
 //   float32   moments in fp64.  A float32 product is exact in fp64, the seven-row and then seven-column sums are rounded
 //             in that fixed order;
@@ -295,14 +295,23 @@ static bool yuv_side(YuvSide& s, const void* y, const void* u, const void* v, in
     return true;
 }
 
-// What the two entries share: the checks of the sides and the workspace, and the two launches.  shift: the code is the
-// word shifted right by it.  The extents, depth and flags are checked by the entries.
-static int yuv_metrics_run(const void* pred_y, const void* pred_u, const void* pred_v, int pred_step, long pred_pitch_y,
-                           long pred_pitch_c, const void* target_y, const void* target_u, const void* target_v,
-                           int target_step, long target_pitch_y, long target_pitch_c, int sub_w, int sub_h, int depth,
-                           int shift, int luma_only, int H, int W, unsigned long long* sse, double* ssim, void* ws,
-                           long ws_words, hipStream_t stream) {
-    const int CH = H / sub_h, CW = W / sub_w;
+// The checks of the extents, the sides and the workspace, and the two launches.  The code of an upper-bits word is
+// the word shifted right by 16 - depth.
+extern "C" int irm_yuv_metrics(const void* pred_y, const void* pred_u, const void* pred_v, int pred_step,
+                               long pred_pitch_y, long pred_pitch_c, const void* target_y, const void* target_u,
+                               const void* target_v, int target_step, long target_pitch_y, long target_pitch_c, int sub_w,
+                               int sub_h, int depth, int upper_bits, int luma_only, int H, int W, unsigned long long* sse,
+                               double* ssim, void* ws, long ws_words, hipStream_t stream) {
+    if (!sse || !ssim || !ws) return IRM_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(sse) | reinterpret_cast<uintptr_t>(ssim) | reinterpret_cast<uintptr_t>(ws)) & 7)
+        return IRM_EINVAL;
+    if (!((sub_w == 2 && sub_h == 2) || (sub_w == 2 && sub_h == 1) || (sub_w == 1 && sub_h == 1))) return IRM_EINVAL;
+    if ((depth != 8 && depth != 10 && depth != 12) || !irm_is_flag(upper_bits) || (depth == 8 && upper_bits)
+        || !irm_is_flag(luma_only)) return IRM_EINVAL;
+    if (H <= 0 || W <= 0 || H % sub_h || W % sub_w || H > (1 << 20) || W > (1 << 20)) return IRM_EINVAL;
+    // a chroma plane holds one 7 x 7 window; the luma plane alone with luma_only
+    if (luma_only ? (H < 7 || W < 7) : (H / sub_h < 7 || W / sub_w < 7)) return IRM_EINVAL;
+    const int CH = H / sub_h, CW = W / sub_w, shift = upper_bits ? 16 - depth : 0;
     const uintptr_t es = depth == 8 ? 1 : 2;
     YuvSide p, q;
     if (!yuv_side(p, pred_y, pred_u, pred_v, pred_step, pred_pitch_y, pred_pitch_c, luma_only, W, CW, es)) return IRM_EINVAL;
@@ -334,38 +343,14 @@ static int yuv_metrics_run(const void* pred_y, const void* pred_u, const void* p
     return irm_launch_status();
 }
 
+// The 4:2:0 entry of include/irm_hip_metrics.h: depths 8 and 10 only, as it was (is_p010 is upper_bits at 10 bit)
 extern "C" int irm_yuv420_metrics(const void* pred_y, const void* pred_u, const void* pred_v, int pred_step,
                                   long pred_pitch_y, long pred_pitch_c, const void* target_y, const void* target_u,
                                   const void* target_v, int target_step, long target_pitch_y, long target_pitch_c,
                                   int depth, int is_p010, int luma_only, int H, int W, unsigned long long* sse,
                                   double* ssim, void* ws, long ws_words, hipStream_t stream) {
-    if (!sse || !ssim || !ws) return IRM_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(sse) | reinterpret_cast<uintptr_t>(ssim) | reinterpret_cast<uintptr_t>(ws)) & 7)
-        return IRM_EINVAL;
-    if ((depth != 8 && depth != 10) || !irm_is_flag(is_p010) || (depth == 8 && is_p010) || !irm_is_flag(luma_only))
-        return IRM_EINVAL;
-    const int least = luma_only ? 8 : 14;                  // a chroma plane holds one 7 x 7 window
-    if (H < least || W < least || (H & 1) || (W & 1) || H > (1 << 20) || W > (1 << 20)) return IRM_EINVAL;
-    return yuv_metrics_run(pred_y, pred_u, pred_v, pred_step, pred_pitch_y, pred_pitch_c, target_y, target_u, target_v,
-                           target_step, target_pitch_y, target_pitch_c, 2, 2, depth, is_p010 ? 6 : 0, luma_only, H, W, sse,
-                           ssim, ws, ws_words, stream);
-}
-
-extern "C" int irm_yuv_metrics(const void* pred_y, const void* pred_u, const void* pred_v, int pred_step,
-                               long pred_pitch_y, long pred_pitch_c, const void* target_y, const void* target_u,
-                               const void* target_v, int target_step, long target_pitch_y, long target_pitch_c, int sub_w,
-                               int sub_h, int depth, int upper_bits, int luma_only, int H, int W, unsigned long long* sse,
-                               double* ssim, void* ws, long ws_words, hipStream_t stream) {
-    if (!sse || !ssim || !ws) return IRM_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(sse) | reinterpret_cast<uintptr_t>(ssim) | reinterpret_cast<uintptr_t>(ws)) & 7)
-        return IRM_EINVAL;
-    if (!((sub_w == 2 && sub_h == 2) || (sub_w == 2 && sub_h == 1) || (sub_w == 1 && sub_h == 1))) return IRM_EINVAL;
-    if ((depth != 8 && depth != 10 && depth != 12) || !irm_is_flag(upper_bits) || (depth == 8 && upper_bits)
-        || !irm_is_flag(luma_only)) return IRM_EINVAL;
-    if (H <= 0 || W <= 0 || H % sub_h || W % sub_w || H > (1 << 20) || W > (1 << 20)) return IRM_EINVAL;
-    // a chroma plane holds one 7 x 7 window; the luma plane alone with luma_only
-    if (luma_only ? (H < 7 || W < 7) : (H / sub_h < 7 || W / sub_w < 7)) return IRM_EINVAL;
-    return yuv_metrics_run(pred_y, pred_u, pred_v, pred_step, pred_pitch_y, pred_pitch_c, target_y, target_u, target_v,
-                           target_step, target_pitch_y, target_pitch_c, sub_w, sub_h, depth, upper_bits ? 16 - depth : 0,
-                           luma_only, H, W, sse, ssim, ws, ws_words, stream);
+    if ((depth != 8 && depth != 10) || !irm_is_flag(is_p010)) return IRM_EINVAL;
+    return irm_yuv_metrics(pred_y, pred_u, pred_v, pred_step, pred_pitch_y, pred_pitch_c, target_y, target_u, target_v,
+                           target_step, target_pitch_y, target_pitch_c, 2, 2, depth, is_p010, luma_only, H, W, sse, ssim,
+                           ws, ws_words, stream);
 }

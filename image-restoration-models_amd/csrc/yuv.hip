@@ -1,14 +1,16 @@
-// YUV video frames to the float32 RGB frame of the device pipeline and back: 4:2:0 (I420, NV12, P010;
-// include/irm_hip_yuv.h) and, further down, the whole grid of 4:2:0, 4:2:2 and 4:4:4 at 8, 10 and 12 bit
-// (include/irm_hip_video.h).  The reference has no YUV path: the arithmetic is stated in tests/yuv_model.py and
-// tests/yuv_formats_model.py and restated here with the same float32 operation order, every multiply, add, subtract
-// and divide spelled with a correctly rounded intrinsic so that nothing is contracted into a multiply-add.
+// YUV video frames to the float32 RGB frame of the device pipeline and back: the whole grid of 4:2:0, 4:2:2 and 4:4:4 at
+// 8, 10 and 12 bit (include/irm_hip_video.h) and the 4:2:0 entries for I420, NV12 and P010 (include/irm_hip_yuv.h).
+// The reference has no YUV path: the arithmetic is stated in tests/yuv_model.py and tests/yuv_formats_model.py and
+// restated here with the same float32 operation order, every multiply, add, subtract and divide spelled with a
+// correctly rounded intrinsic so that nothing is contracted into a multiply-add.
 //
-// All kernels are streams.  At 4:2:0 a work item owns four horizontally adjacent 2 x 2 luma blocks (8 x 2 pixels, 4 chroma
-// samples per plane).  Where pointer, pitch and width allow it, it moves its luma rows as one 8- / 16-byte piece, its
-// chroma as 4- to 16-byte pieces and its two rows of the float frame as 16-byte pieces (a float row starts at 12 W y
-// bytes: W % 4 == 0); otherwise, and in a last group that is not full, it moves elements one by one, reads clamped to
-// the frame and stores guarded by it.  No LDS, no atomics; nothing outside [H][W] of a plane is written.
+// One kernel template per direction, instantiated per sample type T and chroma sub-sampling (SW, SH).  All kernels are
+// streams.  A work item owns 8 x SH luma pixels and their NC = 8 / SW chroma samples per plane: at 4:2:0 four
+// horizontally adjacent 2 x 2 luma blocks, otherwise eight pixels of one row.  Where pointer, pitch and width allow it,
+// it moves a luma row as one 8- / 16-byte piece, its chroma as 4- to 16-byte pieces and a row of the float frame as
+// 16-byte pieces (a float row starts at 12 W y bytes: W % 4 == 0); otherwise, and in a last group that is not full, it
+// moves elements one by one, reads clamped to the frame and stores guarded by it.  No LDS, no atomics; nothing outside
+// [H][W] of a plane is written.
 #include "irm_common.h"
 
 // The rounded intrinsics are plain operators to the compiler (inline functions of its headers), which under its default
@@ -77,67 +79,130 @@ __device__ __forceinline__ void store8(uint16_t* p, const int* c) {
     *reinterpret_cast<uint4*>(p) = make_uint4((uint32_t)c[0] | ((uint32_t)c[1] << 16), (uint32_t)c[2] | ((uint32_t)c[3] << 16),
                                               (uint32_t)c[4] | ((uint32_t)c[5] << 16), (uint32_t)c[6] | ((uint32_t)c[7] << 16));
 }
+// N = 4 or 8 samples of one plane: the planar chroma of a group
+template <int N, typename T>
+__device__ __forceinline__ void load_piece(const T* p, int* o) {
+    if (N == 4) load4(p, o);
+    else load8(p, o);
+}
+template <int N, typename T>
+__device__ __forceinline__ void store_piece(T* p, const int* c) {
+    if (N == 4) store4(p, c);
+    else store8(p, c);
+}
 
 __device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+
+// ---- the eight pixels of a group in one row of the float frame, C = 3 (RGB) or 1 (luma_only) values each
+template <int C>
+__device__ __forceinline__ void store_frame_row(const YuvArgs& a, int row, int x0, bool full, const float* px) {
+    float* o = a.rgb + ((long)row * a.W + x0) * C;
+    if (full && a.vec_rgb) {
+#pragma unroll
+        for (int i = 0; i < 2 * C; ++i)
+            reinterpret_cast<f32x4*>(o)[i] = f32x4{px[4 * i], px[4 * i + 1], px[4 * i + 2], px[4 * i + 3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (x0 + j < a.W) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) o[C * j + c] = px[C * j + c];
+            }
+    }
+}
+
+// The mirror image; a pixel outside the frame reads as 0.  Returns the group's first value in the frame.
+template <int C>
+__device__ __forceinline__ const float* load_frame_row(const YuvArgs& a, int row, int x0, bool full, float* px) {
+    const float* p = a.rgb + ((long)row * a.W + x0) * C;
+    if (full && a.vec_rgb) {
+#pragma unroll
+        for (int i = 0; i < 2 * C; ++i) {
+            const f32x4 q = reinterpret_cast<const f32x4*>(p)[i];
+            px[4 * i] = q.x; px[4 * i + 1] = q.y; px[4 * i + 2] = q.z; px[4 * i + 3] = q.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const bool in = x0 + j < a.W;
+#pragma unroll
+            for (int c = 0; c < C; ++c) px[C * j + c] = in ? p[C * j + c] : 0.0f;
+        }
+    }
+    return p;
+}
 
 // ---------------------------------------------------------------------------
 // planes -> rgb
 
-// One chroma row of both planes for the group at cx0: columns cx0 - 1 .. cx0 + 4, clamped to the row.
-template <typename T>
-__device__ __forceinline__ void chroma_row(const YuvArgs& a, int row, int cx0, bool full, int* ou, int* ov) {
+// One chroma row of both planes for the group at cx0, clamped to the row: its NC samples and, where the row is
+// up-sampled (SW == 2), one more on either side - columns cx0 - 1 .. cx0 + 4.
+template <typename T, int SW>
+__device__ __forceinline__ void chroma_taps(const YuvArgs& a, int row, int cx0, bool full, int* ou, int* ov) {
+    constexpr int NC = 8 / SW, E = SW - 1, NT = NC + 2 * E;
     const T* U = static_cast<const T*>(a.u) + (long)row * a.pitch_c;
     const T* V = static_cast<const T*>(a.v) + (long)row * a.pitch_c;
     if (full && a.vec_c) {
-        if (a.step == 2) {                                   // U0 V0 U1 V1 ..: one piece holds both planes
-            int t[8];
-            load8(U + 2 * cx0, t);
+        if (a.step == 2) {                                   // U0 V0 U1 V1 ..: pieces of eight hold both planes
+            int t[2 * NC];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { ou[1 + j] = t[2 * j]; ov[1 + j] = t[2 * j + 1]; }
+            for (int i = 0; i < NC / 4; ++i) load8(U + 2 * cx0 + 8 * i, t + 8 * i);
+#pragma unroll
+            for (int j = 0; j < NC; ++j) { ou[E + j] = t[2 * j]; ov[E + j] = t[2 * j + 1]; }
         } else {
-            load4(U + cx0, ou + 1);
-            load4(V + cx0, ov + 1);
+            load_piece<NC>(U + cx0, ou + E);
+            load_piece<NC>(V + cx0, ov + E);
         }
-        const long cl = (long)a.step * max(cx0 - 1, 0), cr = (long)a.step * min(cx0 + 4, a.CW - 1);
-        ou[0] = (int)U[cl]; ov[0] = (int)V[cl];
-        ou[5] = (int)U[cr]; ov[5] = (int)V[cr];
+        if (SW == 2) {
+            const long cl = (long)a.step * max(cx0 - 1, 0), cr = (long)a.step * min(cx0 + 4, a.CW - 1);
+            ou[0] = (int)U[cl]; ov[0] = (int)V[cl];
+            ou[5] = (int)U[cr]; ov[5] = (int)V[cr];
+        }
     } else {
 #pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const long c = (long)a.step * min(max(cx0 - 1 + j, 0), a.CW - 1);
+        for (int j = 0; j < NT; ++j) {
+            const long c = (long)a.step * min(max(cx0 - E + j, 0), a.CW - 1);
             ou[j] = (int)U[c];
             ov[j] = (int)V[c];
         }
     }
 #pragma unroll
-    for (int j = 0; j < 6; ++j) { ou[j] >>= a.shift; ov[j] >>= a.shift; }
+    for (int j = 0; j < NT; ++j) { ou[j] >>= a.shift; ov[j] >>= a.shift; }
 }
 
-template <typename T>
-__global__ __launch_bounds__(YUV_WG) void yuv420_to_rgb_kernel(YuvArgs a) {
+template <typename T, int SW, int SH>
+__global__ __launch_bounds__(YUV_WG) void yuv_to_rgb_kernel(YuvArgs a) {
+    constexpr int NC = 8 / SW, NT = NC + 2 * (SW - 1);
     const long idx = (long)blockIdx.x * YUV_WG + threadIdx.x;
-    if (idx >= (long)a.CH * a.G) return;
+    if (idx >= (long)a.CH * a.G) return;                     // CH = H / SH rows of groups
     const int g = (int)(idx % a.G), cy = (int)(idx / a.G);
-    const int cx0 = 4 * g, x0 = 8 * g;
-    const bool full = cx0 + 4 <= a.CW;
+    const int cx0 = NC * g, x0 = 8 * g;
+    const bool full = cx0 + NC <= a.CW;
     const YuvConst k = a.k;
 
-    // chroma, blended vertically: row 2 cy lies a quarter above its sample, row 2 cy + 1 a quarter below (both sitings)
-    int tu[2][6], tv[2][6];
+    // chroma, vertical stage: four times the code at each luma row.  SH == 2: row 2 cy lies a quarter above its sample,
+    // row 2 cy + 1 a quarter below (both sitings)
+    int tu[SH][NT], tv[SH][NT];
     if (!a.luma_only) {
-        int mu[6], mv[6], nu[6], nv[6];
-        chroma_row<T>(a, cy, cx0, full, mu, mv);
-        chroma_row<T>(a, max(cy - 1, 0), cx0, full, nu, nv);
+        int mu[NT], mv[NT];
+        chroma_taps<T, SW>(a, cy, cx0, full, mu, mv);
 #pragma unroll
-        for (int j = 0; j < 6; ++j) { tu[0][j] = 3 * mu[j] + nu[j]; tv[0][j] = 3 * mv[j] + nv[j]; }
-        chroma_row<T>(a, min(cy + 1, a.CH - 1), cx0, full, nu, nv);
+        for (int r = 0; r < SH; ++r) {
+            if (SH == 2) {
+                int nu[NT], nv[NT];
+                chroma_taps<T, SW>(a, r ? min(cy + 1, a.CH - 1) : max(cy - 1, 0), cx0, full, nu, nv);
 #pragma unroll
-        for (int j = 0; j < 6; ++j) { tu[1][j] = 3 * mu[j] + nu[j]; tv[1][j] = 3 * mv[j] + nv[j]; }
+                for (int j = 0; j < NT; ++j) { tu[r][j] = 3 * mu[j] + nu[j]; tv[r][j] = 3 * mv[j] + nv[j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NT; ++j) { tu[r][j] = 4 * mu[j]; tv[r][j] = 4 * mv[j]; }
+            }
+        }
     }
 
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int row = 2 * cy + r;
+    for (int r = 0; r < SH; ++r) {
+        const int row = SH * cy + r;
         const T* Y = static_cast<const T*>(a.y) + (long)row * a.pitch_y + x0;
         int yv[8];
         if (full && a.vec_y) {
@@ -151,33 +216,32 @@ __global__ __launch_bounds__(YUV_WG) void yuv420_to_rgb_kernel(YuvArgs a) {
         for (int j = 0; j < 8; ++j) yp[j] = __fdiv_rn(__fsub_rn((float)(yv[j] >> a.shift), k.y0), k.yr);
 
         if (a.luma_only) {
-            float* o = a.rgb + (long)row * a.W + x0;
-            if (full && a.vec_rgb) {
-                reinterpret_cast<float4*>(o)[0] = make_float4(clip01(yp[0]), clip01(yp[1]), clip01(yp[2]), clip01(yp[3]));
-                reinterpret_cast<float4*>(o)[1] = make_float4(clip01(yp[4]), clip01(yp[5]), clip01(yp[6]), clip01(yp[7]));
-            } else {
 #pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (x0 + j < a.W) o[j] = clip01(yp[j]);
-            }
+            for (int j = 0; j < 8; ++j) yp[j] = clip01(yp[j]);
+            store_frame_row<1>(a, row, x0, full, yp);
             continue;
         }
 
         float px[24];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int b = 1 + (j >> 1);                      // this pixel's chroma column in tu / tv
-            int su, sv;                                      // sixteen times the up-sampled code
-            if (a.center) {                                  // a quarter left (even column) or right (odd) of its sample
-                const int n = (j & 1) ? b + 1 : b - 1;
-                su = 3 * tu[r][b] + tu[r][n];
-                sv = 3 * tv[r][b] + tv[r][n];
-            } else if (j & 1) {                              // midway between two samples
-                su = 2 * tu[r][b] + 2 * tu[r][b + 1];
-                sv = 2 * tv[r][b] + 2 * tv[r][b + 1];
-            } else {                                         // on its sample
-                su = 4 * tu[r][b];
-                sv = 4 * tv[r][b];
+            int su, sv;                                      // horizontal stage: sixteen times the up-sampled code
+            if (SW == 1) {
+                su = 4 * tu[r][j];
+                sv = 4 * tv[r][j];
+            } else {
+                const int b = 1 + (j >> 1);                  // this pixel's chroma column in tu / tv
+                if (a.center) {                              // a quarter left (even column) or right (odd) of its sample
+                    const int n = (j & 1) ? b + 1 : b - 1;
+                    su = 3 * tu[r][b] + tu[r][n];
+                    sv = 3 * tv[r][b] + tv[r][n];
+                } else if (j & 1) {                          // midway between two samples
+                    su = 2 * tu[r][b] + 2 * tu[r][b + 1];
+                    sv = 2 * tv[r][b] + 2 * tv[r][b + 1];
+                } else {                                     // on its sample
+                    su = 4 * tu[r][b];
+                    sv = 4 * tv[r][b];
+                }
             }
             const float cb = __fdiv_rn(__fsub_rn(__fmul_rn((float)su, 0.0625f), k.c0), k.cr);
             const float cr = __fdiv_rn(__fsub_rn(__fmul_rn((float)sv, 0.0625f), k.c0), k.cr);
@@ -185,16 +249,7 @@ __global__ __launch_bounds__(YUV_WG) void yuv420_to_rgb_kernel(YuvArgs a) {
             px[3 * j + 1] = clip01(__fsub_rn(__fsub_rn(yp[j], __fmul_rn(k.g_cb, cb)), __fmul_rn(k.g_cr, cr)));
             px[3 * j + 2] = clip01(__fadd_rn(yp[j], __fmul_rn(k.b_cb, cb)));
         }
-        float* o = a.rgb + ((long)row * a.W + x0) * 3;
-        if (full && a.vec_rgb) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-                reinterpret_cast<float4*>(o)[i] = make_float4(px[4 * i], px[4 * i + 1], px[4 * i + 2], px[4 * i + 3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (x0 + j < a.W) { o[3 * j] = px[3 * j]; o[3 * j + 1] = px[3 * j + 1]; o[3 * j + 2] = px[3 * j + 2]; }
-        }
+        store_frame_row<3>(a, row, x0, full, px);
     }
 }
 
@@ -205,54 +260,32 @@ __device__ __forceinline__ int to_code(float off, float range, float v, float ma
     return (int)rintf(fminf(fmaxf(__fadd_rn(off, __fmul_rn(range, v)), 0.0f), maxcode));      // half to even
 }
 
-template <typename T>
-__global__ __launch_bounds__(YUV_WG) void rgb_to_yuv420_kernel(YuvArgs a) {
+template <typename T, int SW, int SH>
+__global__ __launch_bounds__(YUV_WG) void rgb_to_yuv_kernel(YuvArgs a) {
+    constexpr int NC = 8 / SW;
     const long idx = (long)blockIdx.x * YUV_WG + threadIdx.x;
-    if (idx >= (long)a.CH * a.G) return;
+    if (idx >= (long)a.CH * a.G) return;                     // CH = H / SH rows of groups
     const int g = (int)(idx % a.G), cy = (int)(idx / a.G);
-    const int cx0 = 4 * g, x0 = 8 * g;
-    const bool full = cx0 + 4 <= a.CW;
+    const int cx0 = NC * g, x0 = 8 * g;
+    const bool full = cx0 + NC <= a.CW;
     const YuvConst k = a.k;
 
-    // per row: slot 0 is the pixel left of the group (clamped to the row: the left siting's filter), 1..8 the group's
-    float cb[2][9], cr[2][9];
+    // per row: slot 0 is the pixel left of the group (clamped to the row: the left siting's filter at SW == 2), 1..8 the
+    // group's
+    float cb[SH][9], cr[SH][9];
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int row = 2 * cy + r;
-        T* Y = static_cast<T*>(a.y) + (long)row * a.pitch_y + x0;
+    for (int r = 0; r < SH; ++r) {
+        const int row = SH * cy + r;
         int code[8];
         if (a.luma_only) {
-            const float* p = a.rgb + (long)row * a.W + x0;
             float yp[8];
-            if (full && a.vec_rgb) {
-                const float4 q0 = reinterpret_cast<const float4*>(p)[0], q1 = reinterpret_cast<const float4*>(p)[1];
-                yp[0] = q0.x; yp[1] = q0.y; yp[2] = q0.z; yp[3] = q0.w;
-                yp[4] = q1.x; yp[5] = q1.y; yp[6] = q1.z; yp[7] = q1.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) yp[j] = x0 + j < a.W ? p[j] : 0.0f;
-            }
+            load_frame_row<1>(a, row, x0, full, yp);
 #pragma unroll
             for (int j = 0; j < 8; ++j) code[j] = to_code(k.y0, k.yr, yp[j], k.maxcode) << a.shift;
         } else {
-            const float* p = a.rgb + ((long)row * a.W + x0) * 3;
             float px[27];
-            if (full && a.vec_rgb) {
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const float4 q = reinterpret_cast<const float4*>(p)[i];
-                    px[3 + 4 * i] = q.x; px[4 + 4 * i] = q.y; px[5 + 4 * i] = q.z; px[6 + 4 * i] = q.w;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const bool in = x0 + j < a.W;
-                    px[3 + 3 * j] = in ? p[3 * j] : 0.0f;
-                    px[4 + 3 * j] = in ? p[3 * j + 1] : 0.0f;
-                    px[5 + 3 * j] = in ? p[3 * j + 2] : 0.0f;
-                }
-            }
-            const int l = x0 > 0 ? -3 : 0;                   // x0 < W always: the group exists
+            const float* p = load_frame_row<3>(a, row, x0, full, px + 3);
+            const int l = SW == 2 && x0 > 0 ? -3 : 0;        // x0 < W always: the group exists
             px[0] = p[l]; px[1] = p[l + 1]; px[2] = p[l + 2];
 #pragma unroll
             for (int j = 0; j < 9; ++j) {
@@ -263,6 +296,7 @@ __global__ __launch_bounds__(YUV_WG) void rgb_to_yuv420_kernel(YuvArgs a) {
                 if (j > 0) code[j - 1] = to_code(k.y0, k.yr, yp, k.maxcode) << a.shift;
             }
         }
+        T* Y = static_cast<T*>(a.y) + (long)row * a.pitch_y + x0;
         if (full && a.vec_y) {
             store8(Y, code);
         } else {
@@ -273,19 +307,33 @@ __global__ __launch_bounds__(YUV_WG) void rgb_to_yuv420_kernel(YuvArgs a) {
     }
     if (a.luma_only) return;
 
-    int cu[4], cv[4];
+    // The chroma filter.  Its three spellings fix the order of the additions (the float32 models): none is written in
+    // terms of another, halving is not exact for subnormals.
+    constexpr int r1 = SH - 1;                               // the group's second row at SH == 2
+    int cu[NC], cv[NC];
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const int l = 2 * b, m = 2 * b + 1, n = 2 * b + 2;   // left neighbour, even column, odd column
+    for (int b = 0; b < NC; ++b) {
+        const int l = 2 * b, m = 2 * b + 1, n = 2 * b + 2;   // SW == 2: left neighbour, even column, odd column
         float fu, fv;
-        if (a.center) {
-            fu = __fmul_rn(__fadd_rn(__fadd_rn(cb[0][m], cb[0][n]), __fadd_rn(cb[1][m], cb[1][n])), 0.25f);
-            fv = __fmul_rn(__fadd_rn(__fadd_rn(cr[0][m], cr[0][n]), __fadd_rn(cr[1][m], cr[1][n])), 0.25f);
+        if (SW == 1) {
+            fu = cb[0][b + 1];
+            fv = cr[0][b + 1];
+        } else if (SH == 1) {
+            if (a.center) {
+                fu = __fmul_rn(__fadd_rn(cb[0][m], cb[0][n]), 0.5f);
+                fv = __fmul_rn(__fadd_rn(cr[0][m], cr[0][n]), 0.5f);
+            } else {
+                fu = __fmul_rn(__fadd_rn(__fadd_rn(cb[0][l], __fadd_rn(cb[0][m], cb[0][m])), cb[0][n]), 0.25f);
+                fv = __fmul_rn(__fadd_rn(__fadd_rn(cr[0][l], __fadd_rn(cr[0][m], cr[0][m])), cr[0][n]), 0.25f);
+            }
+        } else if (a.center) {
+            fu = __fmul_rn(__fadd_rn(__fadd_rn(cb[0][m], cb[0][n]), __fadd_rn(cb[r1][m], cb[r1][n])), 0.25f);
+            fv = __fmul_rn(__fadd_rn(__fadd_rn(cr[0][m], cr[0][n]), __fadd_rn(cr[r1][m], cr[r1][n])), 0.25f);
         } else {
             const float u0 = __fmul_rn(__fadd_rn(__fadd_rn(cb[0][l], __fadd_rn(cb[0][m], cb[0][m])), cb[0][n]), 0.25f);
-            const float u1 = __fmul_rn(__fadd_rn(__fadd_rn(cb[1][l], __fadd_rn(cb[1][m], cb[1][m])), cb[1][n]), 0.25f);
+            const float u1 = __fmul_rn(__fadd_rn(__fadd_rn(cb[r1][l], __fadd_rn(cb[r1][m], cb[r1][m])), cb[r1][n]), 0.25f);
             const float v0 = __fmul_rn(__fadd_rn(__fadd_rn(cr[0][l], __fadd_rn(cr[0][m], cr[0][m])), cr[0][n]), 0.25f);
-            const float v1 = __fmul_rn(__fadd_rn(__fadd_rn(cr[1][l], __fadd_rn(cr[1][m], cr[1][m])), cr[1][n]), 0.25f);
+            const float v1 = __fmul_rn(__fadd_rn(__fadd_rn(cr[r1][l], __fadd_rn(cr[r1][m], cr[r1][m])), cr[r1][n]), 0.25f);
             fu = __fmul_rn(__fadd_rn(u0, u1), 0.5f);
             fv = __fmul_rn(__fadd_rn(v0, v1), 0.5f);
         }
@@ -295,236 +343,15 @@ __global__ __launch_bounds__(YUV_WG) void rgb_to_yuv420_kernel(YuvArgs a) {
     T* U = static_cast<T*>(a.u) + (long)cy * a.pitch_c;
     T* V = static_cast<T*>(a.v) + (long)cy * a.pitch_c;
     if (full && a.vec_c) {
-        if (a.step == 2) {
-            const int uv[8] = {cu[0], cv[0], cu[1], cv[1], cu[2], cv[2], cu[3], cv[3]};
-            store8(U + 2 * cx0, uv);
-        } else {
-            store4(U + cx0, cu);
-            store4(V + cx0, cv);
-        }
-    } else {
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-            if (cx0 + b < a.CW) {
-                U[(long)a.step * (cx0 + b)] = (T)cu[b];
-                V[(long)a.step * (cx0 + b)] = (T)cv[b];
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// 4:2:2 and 4:4:4 (include/irm_hip_video.h): rows are independent, a work item owns eight pixels of one row and their
-// SW == 2 ? four : eight chroma samples per plane.  The pieces, the element path and the arithmetic are those above.
-
-// One chroma row of both planes at full horizontal resolution: columns x0 .. x0 + 7, clamped to the row.
-template <typename T>
-__device__ __forceinline__ void chroma_row8(const YuvArgs& a, int row, int x0, bool full, int* ou, int* ov) {
-    const T* U = static_cast<const T*>(a.u) + (long)row * a.pitch_c;
-    const T* V = static_cast<const T*>(a.v) + (long)row * a.pitch_c;
-    if (full && a.vec_c) {
-        if (a.step == 2) {                                   // U0 V0 U1 V1 ..: two pieces hold both planes
-            int t[16];
-            load8(U + 2 * x0, t);
-            load8(U + 2 * x0 + 8, t + 8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { ou[j] = t[2 * j]; ov[j] = t[2 * j + 1]; }
-        } else {
-            load8(U + x0, ou);
-            load8(V + x0, ov);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const long c = (long)a.step * min(x0 + j, a.CW - 1);
-            ou[j] = (int)U[c];
-            ov[j] = (int)V[c];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { ou[j] >>= a.shift; ov[j] >>= a.shift; }
-}
-
-template <typename T, int SW>
-__global__ __launch_bounds__(YUV_WG) void yuv_rows_to_rgb_kernel(YuvArgs a) {
-    const long idx = (long)blockIdx.x * YUV_WG + threadIdx.x;
-    if (idx >= (long)a.H * a.G) return;
-    const int g = (int)(idx % a.G), row = (int)(idx / a.G);
-    const int x0 = 8 * g;
-    const bool full = x0 + 8 <= a.W;
-    const YuvConst k = a.k;
-
-    const T* Y = static_cast<const T*>(a.y) + (long)row * a.pitch_y + x0;
-    int yv[8];
-    if (full && a.vec_y) {
-        load8(Y, yv);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) yv[j] = x0 + j < a.W ? (int)Y[j] : 0;
-    }
-    float yp[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) yp[j] = __fdiv_rn(__fsub_rn((float)(yv[j] >> a.shift), k.y0), k.yr);
-
-    if (a.luma_only) {
-        float* o = a.rgb + (long)row * a.W + x0;
-        if (full && a.vec_rgb) {
-            reinterpret_cast<float4*>(o)[0] = make_float4(clip01(yp[0]), clip01(yp[1]), clip01(yp[2]), clip01(yp[3]));
-            reinterpret_cast<float4*>(o)[1] = make_float4(clip01(yp[4]), clip01(yp[5]), clip01(yp[6]), clip01(yp[7]));
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (x0 + j < a.W) o[j] = clip01(yp[j]);
-        }
-        return;
-    }
-
-    int su[8], sv[8];                                        // sixteen times the up-sampled code
-    if (SW == 2) {
-        int tu[6], tv[6];                                    // chroma columns 4 g - 1 .. 4 g + 4
-        chroma_row<T>(a, row, 4 * g, full, tu, tv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int b = 1 + (j >> 1);
-            if (a.center) {                                  // a quarter left (even column) or right (odd) of its sample
-                const int n = (j & 1) ? b + 1 : b - 1;
-                su[j] = 12 * tu[b] + 4 * tu[n];
-                sv[j] = 12 * tv[b] + 4 * tv[n];
-            } else if (j & 1) {                              // midway between two samples
-                su[j] = 8 * tu[b] + 8 * tu[b + 1];
-                sv[j] = 8 * tv[b] + 8 * tv[b + 1];
-            } else {                                         // on its sample
-                su[j] = 16 * tu[b];
-                sv[j] = 16 * tv[b];
-            }
-        }
-    } else {
-        chroma_row8<T>(a, row, x0, full, su, sv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { su[j] *= 16; sv[j] *= 16; }
-    }
-
-    float px[24];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float cb = __fdiv_rn(__fsub_rn(__fmul_rn((float)su[j], 0.0625f), k.c0), k.cr);
-        const float cr = __fdiv_rn(__fsub_rn(__fmul_rn((float)sv[j], 0.0625f), k.c0), k.cr);
-        px[3 * j + 0] = clip01(__fadd_rn(yp[j], __fmul_rn(k.r_cr, cr)));
-        px[3 * j + 1] = clip01(__fsub_rn(__fsub_rn(yp[j], __fmul_rn(k.g_cb, cb)), __fmul_rn(k.g_cr, cr)));
-        px[3 * j + 2] = clip01(__fadd_rn(yp[j], __fmul_rn(k.b_cb, cb)));
-    }
-    float* o = a.rgb + ((long)row * a.W + x0) * 3;
-    if (full && a.vec_rgb) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-            reinterpret_cast<float4*>(o)[i] = make_float4(px[4 * i], px[4 * i + 1], px[4 * i + 2], px[4 * i + 3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (x0 + j < a.W) { o[3 * j] = px[3 * j]; o[3 * j + 1] = px[3 * j + 1]; o[3 * j + 2] = px[3 * j + 2]; }
-    }
-}
-
-template <typename T, int SW>
-__global__ __launch_bounds__(YUV_WG) void rgb_to_yuv_rows_kernel(YuvArgs a) {
-    const long idx = (long)blockIdx.x * YUV_WG + threadIdx.x;
-    if (idx >= (long)a.H * a.G) return;
-    const int g = (int)(idx % a.G), row = (int)(idx / a.G);
-    const int x0 = 8 * g;
-    const bool full = x0 + 8 <= a.W;
-    const YuvConst k = a.k;
-
-    // slot 0 is the pixel left of the group (clamped to the row: the left siting's filter at 4:2:2), 1..8 the group's
-    float cb[9], cr[9];
-    T* Y = static_cast<T*>(a.y) + (long)row * a.pitch_y + x0;
-    int code[8];
-    if (a.luma_only) {
-        const float* p = a.rgb + (long)row * a.W + x0;
-        float yp[8];
-        if (full && a.vec_rgb) {
-            const float4 q0 = reinterpret_cast<const float4*>(p)[0], q1 = reinterpret_cast<const float4*>(p)[1];
-            yp[0] = q0.x; yp[1] = q0.y; yp[2] = q0.z; yp[3] = q0.w;
-            yp[4] = q1.x; yp[5] = q1.y; yp[6] = q1.z; yp[7] = q1.w;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) yp[j] = x0 + j < a.W ? p[j] : 0.0f;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) code[j] = to_code(k.y0, k.yr, yp[j], k.maxcode) << a.shift;
-    } else {
-        const float* p = a.rgb + ((long)row * a.W + x0) * 3;
-        float px[27];
-        if (full && a.vec_rgb) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const float4 q = reinterpret_cast<const float4*>(p)[i];
-                px[3 + 4 * i] = q.x; px[4 + 4 * i] = q.y; px[5 + 4 * i] = q.z; px[6 + 4 * i] = q.w;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const bool in = x0 + j < a.W;
-                px[3 + 3 * j] = in ? p[3 * j] : 0.0f;
-                px[4 + 3 * j] = in ? p[3 * j + 1] : 0.0f;
-                px[5 + 3 * j] = in ? p[3 * j + 2] : 0.0f;
-            }
-        }
-        const int l = SW == 2 && x0 > 0 ? -3 : 0;            // x0 < W always: the group exists
-        px[0] = p[l]; px[1] = p[l + 1]; px[2] = p[l + 2];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const float R = px[3 * j], G = px[3 * j + 1], B = px[3 * j + 2];
-            const float yp = __fadd_rn(__fadd_rn(__fmul_rn(k.kr, R), __fmul_rn(k.kg, G)), __fmul_rn(k.kb, B));
-            cb[j] = __fdiv_rn(__fsub_rn(B, yp), k.b_cb);
-            cr[j] = __fdiv_rn(__fsub_rn(R, yp), k.r_cr);
-            if (j > 0) code[j - 1] = to_code(k.y0, k.yr, yp, k.maxcode) << a.shift;
-        }
-    }
-    if (full && a.vec_y) {
-        store8(Y, code);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (x0 + j < a.W) Y[j] = (T)code[j];
-    }
-    if (a.luma_only) return;
-
-    constexpr int NC = 8 / SW;                               // chroma samples of the group, per plane
-    const int cx0 = NC * g;
-    int cu[NC], cv[NC];
-#pragma unroll
-    for (int b = 0; b < NC; ++b) {
-        float fu, fv;
-        if (SW == 1) {
-            fu = cb[b + 1];
-            fv = cr[b + 1];
-        } else {
-            const int l = 2 * b, m = 2 * b + 1, n = 2 * b + 2;   // left neighbour, even column, odd column
-            if (a.center) {
-                fu = __fmul_rn(__fadd_rn(cb[m], cb[n]), 0.5f);
-                fv = __fmul_rn(__fadd_rn(cr[m], cr[n]), 0.5f);
-            } else {
-                fu = __fmul_rn(__fadd_rn(__fadd_rn(cb[l], __fadd_rn(cb[m], cb[m])), cb[n]), 0.25f);
-                fv = __fmul_rn(__fadd_rn(__fadd_rn(cr[l], __fadd_rn(cr[m], cr[m])), cr[n]), 0.25f);
-            }
-        }
-        cu[b] = to_code(k.c0, k.cr, fu, k.maxcode) << a.shift;
-        cv[b] = to_code(k.c0, k.cr, fv, k.maxcode) << a.shift;
-    }
-    T* U = static_cast<T*>(a.u) + (long)row * a.pitch_c;
-    T* V = static_cast<T*>(a.v) + (long)row * a.pitch_c;
-    if (full && a.vec_c) {
-        if (a.step == 2) {
+        if (a.step == 2) {                                   // U0 V0 U1 V1 ..: pieces of eight hold both planes
             int uv[2 * NC];
 #pragma unroll
             for (int b = 0; b < NC; ++b) { uv[2 * b] = cu[b]; uv[2 * b + 1] = cv[b]; }
 #pragma unroll
             for (int i = 0; i < NC / 4; ++i) store8(U + 2 * cx0 + 8 * i, uv + 8 * i);
-        } else if (SW == 1) {
-            store8(U + cx0, cu);
-            store8(V + cx0, cv);
         } else {
-            store4(U + cx0, cu);
-            store4(V + cx0, cv);
+            store_piece<NC>(U + cx0, cu);
+            store_piece<NC>(V + cx0, cv);
         }
     } else {
 #pragma unroll
@@ -588,23 +415,16 @@ static int yuv_plan(const void* y, const void* u, const void* v, const float* rg
     return IRM_OK;
 }
 
-// The launches of the two directions: (2, 2) is the 8 x 2 block kernel, the other two the row kernel
-template <typename T>
-static void launch_to_rgb(const YuvArgs& a, int sub_w, int sub_h, hipStream_t stream) {
-    const long items = (long)(sub_h == 2 ? a.CH : a.H) * a.G;
+// One work item per group of 8 x SH luma pixels: CH = H / SH rows of G groups
+template <typename T, bool TO_RGB>
+static void yuv_launch(const YuvArgs& a, int sub_w, int sub_h, hipStream_t stream) {
+    const long items = (long)a.CH * a.G;
     const dim3 grid((unsigned)((items + YUV_WG - 1) / YUV_WG)), wg(YUV_WG);
-    if (sub_h == 2) hipLaunchKernelGGL(yuv420_to_rgb_kernel<T>, grid, wg, 0, stream, a);
-    else if (sub_w == 2) hipLaunchKernelGGL((yuv_rows_to_rgb_kernel<T, 2>), grid, wg, 0, stream, a);
-    else hipLaunchKernelGGL((yuv_rows_to_rgb_kernel<T, 1>), grid, wg, 0, stream, a);
-}
-
-template <typename T>
-static void launch_to_yuv(const YuvArgs& a, int sub_w, int sub_h, hipStream_t stream) {
-    const long items = (long)(sub_h == 2 ? a.CH : a.H) * a.G;
-    const dim3 grid((unsigned)((items + YUV_WG - 1) / YUV_WG)), wg(YUV_WG);
-    if (sub_h == 2) hipLaunchKernelGGL(rgb_to_yuv420_kernel<T>, grid, wg, 0, stream, a);
-    else if (sub_w == 2) hipLaunchKernelGGL((rgb_to_yuv_rows_kernel<T, 2>), grid, wg, 0, stream, a);
-    else hipLaunchKernelGGL((rgb_to_yuv_rows_kernel<T, 1>), grid, wg, 0, stream, a);
+    void (*kernel)(YuvArgs) =
+        sub_h == 2   ? (TO_RGB ? yuv_to_rgb_kernel<T, 2, 2> : rgb_to_yuv_kernel<T, 2, 2>)
+        : sub_w == 2 ? (TO_RGB ? yuv_to_rgb_kernel<T, 2, 1> : rgb_to_yuv_kernel<T, 2, 1>)
+                     : (TO_RGB ? yuv_to_rgb_kernel<T, 1, 1> : rgb_to_yuv_kernel<T, 1, 1>);
+    hipLaunchKernelGGL(kernel, grid, wg, 0, stream, a);
 }
 
 extern "C" int irm_yuv_to_rgb_f32(const void* y, const void* u, const void* v, int chroma_step, long pitch_y,
@@ -615,8 +435,8 @@ extern "C" int irm_yuv_to_rgb_f32(const void* y, const void* u, const void* v, i
     const int rc = yuv_plan(y, u, v, rgb, chroma_step, pitch_y, pitch_c, sub_w, sub_h, depth, upper_bits, matrix,
                             full_range, siting, luma_only, H, W, &a);
     if (rc != IRM_OK) return rc;
-    if (depth == 8) launch_to_rgb<uint8_t>(a, sub_w, sub_h, stream);
-    else launch_to_rgb<uint16_t>(a, sub_w, sub_h, stream);
+    if (depth == 8) yuv_launch<uint8_t, true>(a, sub_w, sub_h, stream);
+    else yuv_launch<uint16_t, true>(a, sub_w, sub_h, stream);
     return irm_launch_status();
 }
 
@@ -627,8 +447,8 @@ extern "C" int irm_rgb_f32_to_yuv(const float* rgb, void* y, void* u, void* v, i
     const int rc = yuv_plan(y, u, v, rgb, chroma_step, pitch_y, pitch_c, sub_w, sub_h, depth, upper_bits, matrix,
                             full_range, siting, luma_only, H, W, &a);
     if (rc != IRM_OK) return rc;
-    if (depth == 8) launch_to_yuv<uint8_t>(a, sub_w, sub_h, stream);
-    else launch_to_yuv<uint16_t>(a, sub_w, sub_h, stream);
+    if (depth == 8) yuv_launch<uint8_t, false>(a, sub_w, sub_h, stream);
+    else yuv_launch<uint16_t, false>(a, sub_w, sub_h, stream);
     return irm_launch_status();
 }
 

@@ -157,7 +157,7 @@ def estimate_noise_sigma_device(frames):
 def _yuv_span(fmt, full_range: bool) -> tuple:
     """(shift, sat_lo, sat_hi, span) of the Y plane of `fmt`."""
     depth = yuv.YUV_FORMATS[fmt][1]
-    shift = 6 if fmt == "p010" else 0
+    shift = yuv._shift(fmt)
     if full_range:
         peak = 2 ** depth - 1
         return shift, 0, peak, peak

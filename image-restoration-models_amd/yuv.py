@@ -1,11 +1,10 @@
-"""YUV 4:2:0 video frames: I420, NV12 and P010 planes to the float32 RGB frame in [0, 1] of the
-device pipeline and back, on the GPU (irm_yuv420_to_rgb_f32, irm_rgb_f32_to_yuv420) and restated in numpy float32 on
-the host with the same operation order.  The reference has no YUV path; tests/yuv_model.py states the arithmetic.
-Their PSNR / SSIM per component, on the host in float64 and on the GPU (irm_yuv420_metrics).
+"""YUV video frames (DESIGN.md sections 16 and 23): planes to the float32 RGB frame in [0, 1] of the device pipeline and
+back, on the GPU (irm_yuv_to_rgb_f32, irm_rgb_f32_to_yuv) and restated in numpy float32 on the host with the same
+operation order, for the whole grid of YUV_LAYOUTS: 4:2:0, 4:2:2 and 4:4:4 at 8, 10 and 12 bit, planar and semi-planar.
+The reference has no YUV path; tests/yuv_model.py and tests/yuv_formats_model.py state the arithmetic.  Their PSNR /
+SSIM per component, on the host in float64 and on the GPU (irm_yuv_metrics, irm_yuv420_metrics).
 
-The whole grid of formats: 4:2:0, 4:2:2 and 4:4:4 at 8, 10 and 12 bit, planar and semi-planar
-(YUV_LAYOUTS), through yuv_to_rgb_* / rgb_to_yuv_* and the metrics functions (irm_yuv_to_rgb_f32, irm_rgb_f32_to_yuv,
-irm_yuv_metrics; tests/yuv_formats_model.py states the arithmetic).  The yuv420_* functions keep their three names."""
+The yuv420_* functions are the general ones behind a check of their three names, "i420", "nv12" and "p010"."""
 from __future__ import annotations
 
 from typing import NamedTuple
@@ -17,8 +16,6 @@ from . import _hip
 from .frames import psnr_from_error
 from .metrics import psnr, ssim
 
-#: format -> (planes, bit depth); "p010" keeps its 10-bit code in the upper bits of a 16-bit word
-YUV_FORMATS = {"i420": (3, 8), "nv12": (2, 8), "p010": (2, 10)}
 #: format -> (sub_w, sub_h, planes, bit depth, upper_bits): chroma planes are [H / sub_h][W / sub_w]; 3 planes are
 #: (y, u, v), 2 are (y, uv [CH][CW][2]); 8-bit samples are uint8, the others uint16 with the code in the low bits, or,
 #: with upper_bits, stored as code << (16 - depth)
@@ -30,6 +27,8 @@ YUV_LAYOUTS = {
     "i444": (1, 1, 3, 8, 0), "nv24": (1, 1, 2, 8, 0), "i444p10": (1, 1, 3, 10, 0), "p410": (1, 1, 2, 10, 1),
     "i444p12": (1, 1, 3, 12, 0), "p412": (1, 1, 2, 12, 1),
 }
+#: the three names of the yuv420_* functions -> (planes, bit depth)
+YUV_FORMATS = {fmt: YUV_LAYOUTS[fmt][2:4] for fmt in ("i420", "nv12", "p010")}
 _SAMPLING = {(2, 2): "4:2:0", (2, 1): "4:2:2", (1, 1): "4:4:4"}
 #: matrix -> (Kr, Kb)
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
@@ -137,14 +136,21 @@ def _split_planes(planes, fmt, luma_only):
     return y, planes[1][:, :, 0].astype(np.int64) >> shift, planes[1][:, :, 1].astype(np.int64) >> shift
 
 
-def _upsample16(c: np.ndarray, siting: str) -> np.ndarray:
-    """Sixteen times the linearly up-sampled chroma codes, [H/2][W/2] -> [H][W], edges clamped: integers."""
-    p = np.pad(c, 1, mode="edge")
-    rows = np.empty((2 * c.shape[0], p.shape[1]), np.int64)
-    rows[0::2] = 3 * p[1:-1] + p[:-2]                   # a quarter above the sample
-    rows[1::2] = 3 * p[1:-1] + p[2:]                    # a quarter below
-    left, mid, right = rows[:, :-2], rows[:, 1:-1], rows[:, 2:]
-    out = np.empty((rows.shape[0], 2 * c.shape[1]), np.int64)
+def _upsample16_of(c: np.ndarray, fmt, siting: str) -> np.ndarray:
+    """Sixteen times the linearly up-sampled chroma codes of a `fmt` frame, [H / sub_h][W / sub_w] -> [H][W], edges
+    clamped, in two integer stages of a factor four each: down the columns if sub_h == 2, along the rows if sub_w == 2."""
+    sub_w, sub_h = YUV_LAYOUTS[fmt][:2]
+    t = 4 * c
+    if sub_h == 2:
+        p = np.pad(c, ((1, 1), (0, 0)), mode="edge")
+        t = np.empty((2 * c.shape[0], c.shape[1]), np.int64)
+        t[0::2] = 3 * p[1:-1] + p[:-2]                  # a quarter above the sample
+        t[1::2] = 3 * p[1:-1] + p[2:]                   # a quarter below
+    if sub_w == 1:
+        return 4 * t
+    p = np.pad(t, ((0, 0), (1, 1)), mode="edge")
+    left, mid, right = p[:, :-2], p[:, 1:-1], p[:, 2:]
+    out = np.empty((t.shape[0], 2 * t.shape[1]), np.int64)
     if siting == "center":
         out[:, 0::2] = 3 * mid + left
         out[:, 1::2] = 3 * mid + right
@@ -152,25 +158,6 @@ def _upsample16(c: np.ndarray, siting: str) -> np.ndarray:
         out[:, 0::2] = 4 * mid                          # on the sample
         out[:, 1::2] = 2 * mid + 2 * right              # midway between two
     return out
-
-
-def _upsample16_row(c: np.ndarray, siting: str) -> np.ndarray:
-    """Sixteen times the chroma codes up-sampled horizontally alone (4:2:2), [H][W/2] -> [H][W], edges clamped."""
-    p = np.pad(c, ((0, 0), (1, 1)), mode="edge")
-    left, mid, right = p[:, :-2], p[:, 1:-1], p[:, 2:]
-    out = np.empty((c.shape[0], 2 * c.shape[1]), np.int64)
-    if siting == "center":
-        out[:, 0::2] = 12 * mid + 4 * left
-        out[:, 1::2] = 12 * mid + 4 * right
-    else:
-        out[:, 0::2] = 16 * mid
-        out[:, 1::2] = 8 * mid + 8 * right
-    return out
-
-
-def _upsample16_of(c: np.ndarray, fmt, siting: str) -> np.ndarray:
-    sub = YUV_LAYOUTS[fmt][:2]
-    return _upsample16(c, siting) if sub == (2, 2) else _upsample16_row(c, siting) if sub == (2, 1) else 16 * c
 
 
 def yuv420_to_rgb_host(planes, fmt, matrix="bt709", full_range=False, siting="left", luma_only=False) -> np.ndarray:
@@ -232,6 +219,13 @@ def _codes(off, rng, v, top) -> np.ndarray:
     return np.rint(np.clip(off + rng * v, np.float32(0), top)).astype(np.int64)
 
 
+def _out_planes(out, luma_only: bool, h: int, w: int, fmt, empty) -> tuple:
+    """The planes an rgb_to_yuv_* call writes: `out`, required with luma_only, or new ones from empty(shape)."""
+    if out is None and luma_only:
+        raise ValueError("luma_only writes the Y plane alone: pass the frame's planes as out, their chroma is kept")
+    return tuple(empty(s) for s in plane_shapes(h, w, fmt)) if out is None else out
+
+
 def rgb_to_yuv420_host(rgb, fmt, matrix="bt709", full_range=False, siting="left", luma_only=False, out=None) -> tuple:
     """float32 [H][W][3] RGB -> the planes of a 4:2:0 frame in `fmt`, the numpy twin of rgb_to_yuv420_device, bit for
     bit; values outside [0, 1] are legal (the codes are clipped).  With luma_only the frame is [H][W][1] and only Y is
@@ -248,14 +242,11 @@ def rgb_to_yuv_host(rgb, fmt, matrix="bt709", full_range=False, siting="left", l
     n, depth = YUV_LAYOUTS[fmt][2:4]
     h, w = _check_rgb(rgb, luma_only, np.ndarray, fmt)
     dt = _np_dtype(fmt)
-    if out is None and luma_only:
-        raise ValueError("luma_only writes the Y plane alone: pass the frame's planes as out, their chroma is kept")
-    if out is not None and _check_planes(out, fmt, False, np.ndarray, (dt,)) != (h, w):
+    out = _out_planes(out, luma_only, h, w, fmt, lambda s: np.empty(s, dt))
+    if _check_planes(out, fmt, False, np.ndarray, (dt,)) != (h, w):
         raise ValueError(f"out holds the planes of another frame size than {h} x {w}")
     k = _constants(matrix, full_range, depth)
     shift = _shift(fmt)
-    if out is None:
-        out = tuple(np.empty(s, dt) for s in plane_shapes(h, w, fmt))
     if luma_only:
         out[0][...] = _codes(k["y0"], k["yr"], rgb[:, :, 0], k["top"]) << shift
         return tuple(out)
@@ -313,11 +304,7 @@ def yuv420_to_rgb_device(planes, fmt, matrix="bt709", full_range=False, siting="
     They may be row-pitched views: unit stride inside a row (2 inside UV), any row stride of at least the width.
     Enqueued on the current stream; ValueError before any GPU call for everything else."""
     _check_options(fmt, matrix, siting)
-    h, w, y, u, v, step, pitch_y, pitch_c = _device_planes(planes, fmt, luma_only)
-    rgb = torch.empty(h, w, 1 if luma_only else 3, dtype=torch.float32, device=y.device)
-    _hip.call("irm_yuv420_to_rgb_f32", _hip.ptr(y), _hip.ptr(u), _hip.ptr(v), step, pitch_y, pitch_c,
-              *_kernel_options(fmt, matrix, full_range, siting, luma_only), h, w, _hip.ptr(rgb))
-    return rgb
+    return yuv_to_rgb_device(planes, fmt, matrix, full_range, siting, luma_only)
 
 
 def yuv_to_rgb_device(planes, fmt, matrix="bt709", full_range=False, siting="left", luma_only=False) -> torch.Tensor:
@@ -339,20 +326,7 @@ def rgb_to_yuv420_device(rgb, fmt, matrix="bt709", full_range=False, siting="lef
     legal.  With luma_only the frame is [H][W][1] and only the Y plane of `out` - required - is written; its chroma
     planes come back as they are."""
     _check_options(fmt, matrix, siting)
-    depth = YUV_FORMATS[fmt][1]
-    h, w = _check_rgb(rgb, luma_only, torch.Tensor)
-    if out is None and luma_only:
-        raise ValueError("luma_only writes the Y plane alone: pass the frame's planes as out, their chroma is kept")
-    if out is None:
-        dt = torch.int16 if depth == 10 else torch.uint8
-        out = tuple(torch.empty(s, dtype=dt, device=rgb.device) for s in plane_shapes(h, w, fmt))
-    oh, ow, y, u, v, step, pitch_y, pitch_c = _device_planes(out, fmt, luma_only)
-    if (oh, ow) != (h, w) or y.device != rgb.device:
-        raise ValueError(f"out holds the planes of another device or frame size than {h} x {w}")
-    rgb = rgb.contiguous()
-    _hip.call("irm_rgb_f32_to_yuv420", _hip.ptr(rgb), _hip.ptr(y), _hip.ptr(u), _hip.ptr(v), step, pitch_y,
-              pitch_c, *_kernel_options(fmt, matrix, full_range, siting, luma_only), h, w)
-    return tuple(out)
+    return rgb_to_yuv_device(rgb, fmt, matrix, full_range, siting, luma_only, out)
 
 
 def rgb_to_yuv_device(rgb, fmt, matrix="bt709", full_range=False, siting="left", luma_only=False, out=None) -> tuple:
@@ -361,11 +335,8 @@ def rgb_to_yuv_device(rgb, fmt, matrix="bt709", full_range=False, siting="left",
     _check_layout_options(fmt, matrix, siting)
     depth = YUV_LAYOUTS[fmt][3]
     h, w = _check_rgb(rgb, luma_only, torch.Tensor, fmt)
-    if out is None and luma_only:
-        raise ValueError("luma_only writes the Y plane alone: pass the frame's planes as out, their chroma is kept")
-    if out is None:
-        dt = torch.uint8 if depth == 8 else torch.int16
-        out = tuple(torch.empty(s, dtype=dt, device=rgb.device) for s in plane_shapes(h, w, fmt))
+    dt = torch.uint8 if depth == 8 else torch.int16
+    out = _out_planes(out, luma_only, h, w, fmt, lambda s: torch.empty(s, dtype=dt, device=rgb.device))
     oh, ow, y, u, v, step, pitch_y, pitch_c = _device_planes(out, fmt, luma_only)
     if (oh, ow) != (h, w) or y.device != rgb.device:
         raise ValueError(f"out holds the planes of another device or frame size than {h} x {w}")

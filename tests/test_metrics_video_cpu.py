@@ -279,8 +279,11 @@ def test_kernel_file_keeps_the_repository_rules():
     assert "atomic" not in code.lower()
     assert "__dmul_rn(__dadd_rn(" in code and "ssim_reduce_kernel<true>" in code
     make = open(os.path.join(csrc, "Makefile")).read()
-    assert re.search(r"^yuv\.o metrics_video\.o: CXXFLAGS \+= -ffp-contract=off", make, flags=re.M)
-    assert "$(filter yuv.hip metrics_video.hip,$<),-ffp-contract=off" in make
+    listed = re.search(r"^NO_CONTRACT := (.*)$", make, flags=re.M).group(1).split()
+    assert "yuv" in listed and "metrics_video" in listed
+    assert "$(if $(filter $(NO_CONTRACT),$(basename $(notdir $1))),-ffp-contract=off)" in make
+    assert "$(HIPCC) $(strip $(CXXFLAGS) $(call extra,$<)) -c" in make
+    assert "$(HIPCC) $(strip $(ASAN_FLAGS) $(call extra,$<)) -c" in make
 
 
 # --------------------------------------------------------------------------- harness

@@ -216,7 +216,7 @@ def test_422_upsampling_weights_of_an_impulse(fn):
     sample itself there, half of it on the odd columns beside it; the last odd column takes its right neighbour from the
     clamped edge and so is the last sample whole.  "center": sample i lies midway between columns 2 i and 2 i + 1 -
     3/4 on those two, 1/4 on the next column outwards; at the edges the quarter from outside comes from the edge sample."""
-    up = (lambda c, s: fm.upsample16(c, "i422", s)) if fn == "model" else yuv._upsample16_row
+    up = (lambda c, s: fm.upsample16(c, "i422", s)) if fn == "model" else (lambda c, s: yuv._upsample16_of(c, "i422", s))
     want = {"left": ([16, 8, 0, 0, 0, 0], [0, 8, 16, 8, 0, 0], [0, 0, 0, 8, 16, 16]),
             "center": ([16, 12, 4, 0, 0, 0], [0, 4, 12, 12, 4, 0], [0, 0, 0, 4, 12, 16])}
     for siting, rows in want.items():

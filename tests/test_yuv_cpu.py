@@ -242,7 +242,7 @@ COSITED = ([4, 2, 0, 0], [0, 2, 4, 4])
 def test_upsampling_weights_of_an_impulse(siting, fn):
     """A 4 x 4 frame has 2 x 2 chroma samples, every one at an edge.  A one in one of them spreads, in sixteenths, with
     the outer product of the per-axis weights above."""
-    up = yuv_model.upsample16 if fn == "model" else yuv._upsample16
+    up = yuv_model.upsample16 if fn == "model" else (lambda c, s: yuv._upsample16_of(c, "i420", s))
     horizontal = MIDWAY if siting == "center" else COSITED
     for cy in range(2):
         for cx in range(2):

@@ -7,11 +7,13 @@ Three groups, one JSON line each (--out FILE appends them: profiles/bench_yuv_fo
              replays; the graphs of all formats take turns, round after round.  bytes = the planes plus the float frame
              (12 H W) for a conversion, both sides' planes for the scores; the rate as a share of the 8.0 TB/s HBM peak.
              At this size a frame fits the 256 MiB Infinity Cache: a streaming kernel's rate, not proof of HBM traffic.
-  old_entry  irm_yuv420_to_rgb_f32, irm_rgb_f32_to_yuv420 and irm_yuv420_metrics for "i420", "nv12" and "p010" from this
-             build against the same symbols of `--parent-lib`, the library built from the parent commit, loaded into the
-             same process with ctypes (the package itself cannot bind it through IRM_HIP_LIB: it lacks the new symbols).
-             Legs `this`, `parent` and `parent_again` alternate; `parent_again` against `parent` is the spread that
-             `this` against `parent` is held to.  Skipped without --parent-lib.
+  against_parent
+             irm_yuv420_to_rgb_f32, irm_rgb_f32_to_yuv420 and irm_yuv420_metrics for "i420", "nv12" and "p010", and
+             irm_yuv_to_rgb_f32 and irm_rgb_f32_to_yuv for a planar and a semi-planar format of each sampling structure
+             (NEW_FORMATS), from this build against the same symbols of `--parent-lib`, the library built from the parent
+             commit, loaded into the same process with ctypes.  Legs `this`, `parent` and `parent_again` alternate;
+             `parent_again` against `parent` is the spread that `this` against `parent` is held to
+             (`inside_parent_min_max`).  Skipped without --parent-lib.
   whole_call utils.run_model_inference_yuv on "p210" and on "i444p10" planes against utils.get_model_prediction on the
              uint16 RGB frame (Restormer, motion deblurring, patch 512 / overlap 96, synthetic weights), host clocks
              around calls that end in a download, the legs in every order in turn, as tools/bench_yuv.py does for NV12.
@@ -33,6 +35,10 @@ from irm_amd import _hip, restormer, synth, utils, yuv
 
 HBM_PEAK = 8.0e12
 OLD = ("irm_yuv420_to_rgb_f32", "irm_rgb_f32_to_yuv420", "irm_yuv420_metrics")
+OLD_FORMATS = ("i420", "nv12", "p010")
+NEW = ("irm_yuv_to_rgb_f32", "irm_rgb_f32_to_yuv")
+#: one planar and one semi-planar format of each sampling structure, both sample types in each
+NEW_FORMATS = ("i420", "p010", "i422p10", "nv16", "i444", "p410")
 
 
 def _graph(fn, batch):
@@ -118,18 +124,19 @@ def kernels(a, dev, rgb_unit):
 
 def _bind(path):
     lib = ctypes.CDLL(os.path.abspath(path))
-    for name in OLD:
+    for name in OLD + NEW:
         fn = getattr(lib, name)
-        fn.argtypes = {**_hip.SIGNATURES_YUV, **_hip.SIGNATURES_METRICS}[name]
+        fn.argtypes = {**_hip.SIGNATURES_YUV, **_hip.SIGNATURES_VIDEO, **_hip.SIGNATURES_METRICS}[name]
         fn.restype = ctypes.c_int
     return lib
 
 
-def old_entry(a, dev, rgb_unit):
+def against_parent(a, dev, rgb_unit):
     h, w = rgb_unit.shape[:2]
     this, parent = _hip.load(), _bind(a.parent_lib)
-    fns, keep = {}, []
-    for fmt in ("i420", "nv12", "p010"):
+    fns, keep, keys = {}, [], []
+    for fmt in dict.fromkeys(OLD_FORMATS + NEW_FORMATS):
+        sw, sh = yuv.YUV_LAYOUTS[fmt][:2]
         _, up = _planes(rgb_unit, fmt, dev)
         other = tuple(p.clone() for p in up)
         frame = yuv.yuv_to_rgb_device(up, fmt)
@@ -138,7 +145,7 @@ def old_entry(a, dev, rgb_unit):
         oy, ou, ov = yuv._device_planes(out, fmt, False)[2:5]
         ty, tu, tv = yuv._device_planes(other, fmt, False)[2:5]
         opt = yuv._kernel_options(fmt, "bt709", False, "left", False)
-        words = 2 * (yuv._metric_tiles(h, w) + 2 * yuv._metric_tiles(h // 2, w // 2))
+        words = 2 * (yuv._metric_tiles(h, w) + 2 * yuv._metric_tiles(h // sh, w // sw))
         ws = torch.empty(words, dtype=torch.float64, device=dev)
         sse = torch.empty(3, dtype=torch.int64, device=dev)
         ssim = torch.empty(3, dtype=torch.float64, device=dev)
@@ -147,8 +154,11 @@ def old_entry(a, dev, rgb_unit):
         args = {"irm_yuv420_to_rgb_f32": (P(y), P(u), P(v), step, py, pc, *opt, h, w, P(frame)),
                 "irm_rgb_f32_to_yuv420": (P(frame), P(oy), P(ou), P(ov), step, py, pc, *opt, h, w),
                 "irm_yuv420_metrics": (P(y), P(u), P(v), step, py, pc, P(ty), P(tu), P(tv), step, py, pc, opt[0], opt[1],
-                                       0, h, w, P(sse), P(ssim), P(ws), words)}
-        for name in OLD:
+                                       0, h, w, P(sse), P(ssim), P(ws), words),
+                "irm_yuv_to_rgb_f32": (P(y), P(u), P(v), step, py, pc, sw, sh, *opt, h, w, P(frame)),
+                "irm_rgb_f32_to_yuv": (P(frame), P(oy), P(ou), P(ov), step, py, pc, sw, sh, *opt, h, w)}
+        for name in (OLD if fmt in OLD_FORMATS else ()) + (NEW if fmt in NEW_FORMATS else ()):
+            keys.append(f"{fmt}:{name}")
             for leg, lib in (("this", this), ("parent", parent), ("parent_again", parent)):
                 def call(fn=getattr(lib, name), args=args[name]):
                     rc = fn(*args, torch.cuda.current_stream().cuda_stream)
@@ -156,13 +166,12 @@ def old_entry(a, dev, rgb_unit):
                 fns[f"{fmt}:{name}:{leg}"] = call
     us = _alternate_graphs(fns, a.kernel_batch, a.reps)
     rows = {}
-    for fmt in ("i420", "nv12", "p010"):
-        for name in OLD:
-            t, p, q = (us[f"{fmt}:{name}:{leg}"] for leg in ("this", "parent", "parent_again"))
-            rows[f"{fmt}:{name}"] = {"this": t, "parent": p, "parent_again": q, "this_minus_parent_us": t[0] - p[0],
-                                     "parent_spread_us": abs(q[0] - p[0]),
-                                     "inside_parent_min_max": min(p[1], q[1]) <= t[0] <= max(p[2], q[2])}
-    return {"group": "old_entry", "frame": f"{h}x{w}", "kernel_batch": a.kernel_batch, "reps": a.reps, "rows": rows}
+    for key in keys:
+        t, p, q = (us[f"{key}:{leg}"] for leg in ("this", "parent", "parent_again"))
+        rows[key] = {"this": t, "parent": p, "parent_again": q, "this_minus_parent_us": t[0] - p[0],
+                     "parent_spread_us": abs(q[0] - p[0]),
+                     "inside_parent_min_max": min(p[1], q[1]) <= t[0] <= max(p[2], q[2])}
+    return {"group": "against_parent", "frame": f"{h}x{w}", "kernel_batch": a.kernel_batch, "reps": a.reps, "rows": rows}
 
 
 def whole_call(a, dev, blurred):
@@ -194,7 +203,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kernel-batch", type=int, default=50)
     ap.add_argument("--parent-lib", default=None, help="libirm_hip.so built from the parent commit")
-    ap.add_argument("--groups", default="kernels,old_entry,whole_call")
+    ap.add_argument("--groups", default="kernels,against_parent,whole_call")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -206,8 +215,8 @@ def main():
     for group in a.groups.split(","):
         if group == "kernels":
             lines.append(kernels(a, dev, unit))
-        elif group == "old_entry" and a.parent_lib:
-            lines.append(old_entry(a, dev, unit))
+        elif group == "against_parent" and a.parent_lib:
+            lines.append(against_parent(a, dev, unit))
         elif group == "whole_call":
             lines.append(whole_call(a, dev, blurred))
     for res in lines:

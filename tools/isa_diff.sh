@@ -4,6 +4,9 @@
 # __hip_cuid_* symbol, and the name, linkage and data definition (not the uses) of the per-translation-unit zero page and
 # noinline activation wrapper, which were global symbols under per-file names once.
 # Instructions, .amdhsa_* directives and the kernel metadata (register counts, segment and kernarg sizes) are compared.
+# The flags of a file are those csrc/Makefile gives it (`make flags F=<file>`: CXXFLAGS and the per-file extras such as
+# -ffp-contract=off).  Both sides are compiled with the flags of the working tree's Makefile, so a revision is compared
+# as the working tree would build it.
 #   tools/isa_diff.sh [REV] [WORKDIR]     REV defaults to HEAD^; a WORKDIR is kept and its REV-side assembly reused.
 # Prints one line per file; exit status 1 if any file differs (the diffs are left in WORKDIR/<file>.diff).
 set -euo pipefail
@@ -18,9 +21,8 @@ git -C "$ROOT" archive "$REV" "$CSRC" | tar -x -C "$WORK/old/src"
 compile() {  # <source dir> <output dir>: one .s per .hip that has none yet
     (cd "$1" && ls *.hip | xargs -P "${JOBS:-8}" -I{} sh -c '
         [ -s "$1/{}.s" ] && exit 0
-        case {} in fused_block.hip|fused_tail.hip|fused_qkv_cm.hip|dw_gram.hip) X=-fno-slp-vectorize;; *) X=;; esac
-        "$0" -O3 -std=c++17 -fPIC --offload-arch=gfx950 --cuda-device-only -Wno-unused-command-line-argument -S $X {} -o "$1/{}.s.tmp" && mv "$1/{}.s.tmp" "$1/{}.s"' \
-        "$HIPCC" "$2")
+        "$0" $(make -s -C "$2" flags F={}) --cuda-device-only -Wno-unused-command-line-argument -S {} -o "$1/{}.s.tmp" && mv "$1/{}.s.tmp" "$1/{}.s"' \
+        "$HIPCC" "$2" "$ROOT/$CSRC")
 }
 normalise() {
     sed -E -e 's/[[:space:]]*;.*$//' -e '/^[[:space:]]*$/d' -e 's/__hip_cuid_[0-9a-f]+/__hip_cuid/g' \
